@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- k-mers merged/sec of the glistcompare intersection hot path on MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one complete two-list intersection (merge-path partition + merge kernel + totals
@@ -12,7 +12,14 @@ default is the SAME job (`"scaling": "strong"`): every rank keeps its key range 
 (n_words, total_count) header totals are all-gathered over RCCL inside every step.  `--scaling weak`
 gives every GPU an independent pair instead (no exchange; a reference line, not the metric's job).
 
-The default line also carries a `"union8"` record -- BASELINE configs[3], the 8-way union of eight
+A plain run does what the headline needs and nothing else: it builds the lists, warms up, times --steps steps, and
+prints the line (`ms_per_step` = wall time of the timed steps / --steps; `roofline` from the same steps' kernel times;
+`self_check` against the generator's closed forms).  Everything below that costs runs of its own -- the CPU baselines
+and their verification against the reference binary, and the records the default line embeds -- runs only with
+`--full`.  `--dump-outputs DIR` (pair workloads) writes what the last timed step computed as float64 .npy files, a fixed
+seeded sample of the output records (see dump_outputs); the inputs are the same from run to run.
+
+With --full the default line also carries a `"union8"` record -- BASELINE configs[3], the 8-way union of eight
 5x10^8-entry lists as ONE job sharded by key range over the ranks: `merge_only` (what the shards sustain when every
 rank keeps / writes its own extent, the C host's default; measured FIRST) and `value_with_gather` (the gatherv of the
 payload to rank 0 inside the step: gt4hip_comm_gatherv over RCCL, or -- if that fails on any rank at first contact -- on
@@ -30,7 +37,7 @@ distinct keys of the eight lists) and the totals committed for the default sizes
 (default; one key per stride of the key space), iid, clustered, genomic.
 
 Prints ONE JSON line on rank 0.  `roofline` is computed from the merge kernel's own HIP-event time
-(recorded by the library on the stream it launches on); `cpu_baseline` times the REFERENCE binary
+(recorded by the library on the stream it launches on); with --full, `cpu_baseline` times the REFERENCE binary
 (oracle/_ref/glistcompare, `kind: reference`) or, when that is absent, the C oracle (`kind: port`)
 on a bounded prefix sample of the same lists -- `--count_only` (the pure merge loop) and, on a
 smaller prefix, the file-writing variant (BASELINE.md protocol).  `verified`: after the timed loop
@@ -358,6 +365,48 @@ def csrc_sha16():
     return h.hexdigest()[:16]
 
 
+DUMP_RECORDS = 1 << 20  # records sampled over all output streams of --dump-outputs: 4 float64 arrays -> 32 MB
+
+
+def dump_sample(n, m):
+    """Positions --dump-outputs writes out of an n-record output: all of them up to m, else m distinct positions drawn
+    with a fixed seed, ascending -- the same in every run with the same arguments."""
+    import numpy as np
+    if n <= m:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(0).choice(n, size=m, replace=False))
+
+
+def write_dump(d, name, n_words, total_count, idx, rec):
+    """DIR/<name>_totals.npy ([n_words, total_count]) and, for the records at positions idx: <name>_index.npy,
+    <name>_key_hi.npy / <name>_key_lo.npy (the packed k-mer's upper and lower 32 bits: exact in float64 for any k) and
+    <name>_count.npy -- all float64."""
+    import numpy as np
+    key = rec["key"].astype(np.uint64)
+    arrays = {"totals": np.array([n_words, total_count], dtype=np.float64), "index": idx.astype(np.float64),
+              "key_hi": (key >> np.uint64(32)).astype(np.float64), "key_lo": (key & np.uint64(0xFFFFFFFF)).astype(np.float64),
+              "count": rec["count"].astype(np.float64)}
+    os.makedirs(d, exist_ok=True)
+    for what, a in arrays.items():
+        np.save(os.path.join(d, "%s_%s.npy" % (name, what)), a)
+
+
+def dump_outputs(d, streams):
+    """--dump-outputs: streams = [(name, device list, (n_words, total_count)), ...] as the last timed step left them; the
+    sampled records are gathered on the device (a zero-copy view of the list) and written by write_dump."""
+    import numpy as np
+    import torch
+    from genometester4_amd import distributed as D
+    from genometester4_amd.listio import RECORD_DTYPE
+    for name, lst, (n, total) in streams:
+        idx = dump_sample(n, DUMP_RECORDS // len(streams))
+        rec = np.empty(0, dtype=RECORD_DTYPE)
+        if len(idx):
+            rows = D.list_as_tensor(lst, n).view(-1, 3)[torch.from_numpy(idx).to("cuda")]
+            rec = rows.cpu().numpy().view(RECORD_DTYPE).reshape(-1)
+        write_dump(d, name, n, total, idx, rec)
+
+
 def load_traffic(workload, n, kernel=None):
     """HBM bytes per launch of the dominant kernel from the PMC passes committed under profiles/
     (tools/collect_profiles.sh: FETCH_SIZE and WRITE_SIZE cannot be collected inside this run).
@@ -617,7 +666,7 @@ def bench_multi(args, ctx, capi, rank, local_rank, world, kind="union8", progres
         except Exception as e:
             projection = {"error": "%s: %s" % (type(e).__name__, e)}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.union8_no_cpu:
+    if rank == 0 and world == 1 and args.cpu_legs and not args.union8_no_cpu:
         try:
             cpu = multi_cpu_leg(args, ctx, capi, kind, full)
         except Exception as e:  # the GPU number stands on its own; say why the CPU leg is missing
@@ -833,7 +882,7 @@ def bench_sort(args, ctx, capi):
                         "traffic": sort_traffic, "traffic_source": sort_traffic_source, "traffic_note": "per launch of k_radix_scatter = one pass (16 B x words algorithmic)",
                         "algorithmic_bytes_per_launch": alg, "kernel_ms_avg": s_ms, "fold_ms_avg": statistics.mean(fold_ms),
                         "note": "achieved = 16 B x passes x words / time of the sort (HIP events: histogram kernel + passes); the histogram kernel reads the words once more (8 B per word, once)"}}
-    if not args.no_cpu_baseline:
+    if args.cpu_legs:
         m = min(n, args.cpu_sample // 4)
         host = pristine[:m].cpu().numpy().astype(np.uint64)
         t0 = time.perf_counter()
@@ -887,7 +936,7 @@ def bench_table(args, ctx, capi):
                         "traffic": table_traffic, "traffic_source": table_traffic_source, "traffic_note": "the table launch of the tile kernel (the call's only pass over the records)",
                         "algorithmic_bytes_per_launch": alg, "kernel_ms_avg": t_ms,
                         "note": "algorithmic = every input record read once + the table's rows written once; achieved is over the whole call (sampling, partition, the tile kernel's launch, the ragged table's index)"}}
-    if not args.no_cpu_baseline:
+    if args.cpu_legs:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as O
         m = min(n, args.cpu_sample // (16 * nl))  # (the reference formats every row as text: ~1e7 rows keep the leg at ~10 s)
@@ -1005,6 +1054,7 @@ def bench_pair(args, ctx, capi, rank, world, torch, dist, extras=False):
         ops = capi.OP_INTRSEC if workload == "intersect" else (capi.OP_UNION | capi.OP_DIFF1)
         cutoff = 1 if workload == "intersect" else 3
         op_bits = [bit for bit in all_bits if ops & bit]
+        names = {1: "union", 2: "intrsec", 4: "diff1"}
         outs = {bit: ctx.alloc(max(1, {1: a.n_words + b.n_words, 2: min(a.n_words, b.n_words), 4: a.n_words}[bit]), args.k) for bit in op_bits}
         exchange_ms = []
         job_stat = {}  # strong scaling: the job-wide header totals of the last step
@@ -1056,6 +1106,9 @@ def bench_pair(args, ctx, capi, rank, world, torch, dist, extras=False):
                 g = [torch.zeros(2, dtype=torch.int64, device=_xdev()) for _ in range(world)]
                 dist.all_gather(g, torch.tensor(totals, dtype=torch.int64, device=_xdev()))
                 totals = [int(sum(x[0].item() for x in g)), int(sum(x[1].item() for x in g))]
+            if args.dump_outputs and rank == 0 and workload == args.workload:
+                # what the last timed step left in the output lists (rank 0's key range of a sharded job)
+                dump_outputs(args.dump_outputs, [(names[bit], outs[bit], stat[bit]) for bit in op_bits])
             res = None
             if rank == 0:
                 n_out = sum(stat[bit][0] for bit in op_bits)
@@ -1063,7 +1116,6 @@ def bench_pair(args, ctx, capi, rank, world, torch, dist, extras=False):
                 alg_bytes = 12 * (n_a + n_b) + 12 * n_out
                 achieved = alg_bytes / (k_ms * 1e-3) / 1e9
                 traffic, traffic_source = load_traffic(workload if args.dist == "stride" else "%s_%s" % (workload, args.dist), n)
-                names = {1: "union", 2: "intrsec", 4: "diff1"}
                 shape = "two %d-entry k=%d lists (%.1f GB each, %s keys)" % (n, args.k, 12 * n / 1e9, args.dist)
                 if workload == "intersect":
                     metric = "k-mers merged/sec, 2-list k=%d intersection (glistcompare -i), lists resident in HBM" % args.k
@@ -1123,7 +1175,7 @@ def bench_pair(args, ctx, capi, rank, world, torch, dist, extras=False):
                 if workload == "intersect" and (strong or world == 1):
                     bad = self_check("intersect", args.dist, n, args.k, totals[0], totals[1])
                     res["self_check"] = "ok" if bad is None else "FAILED: " + bad
-                if world == 1 and not args.no_cpu_baseline:
+                if world == 1 and args.cpu_legs:
                     try:
                         res["cpu_baseline"], res["verified"], res["verified_totals"] = cpu_baseline(ctx, capi, a, b, args.k, cpu_sample, ops, cutoff)
                     except Exception as e:  # the GPU number stands on its own; say why the CPU leg is missing
@@ -1151,7 +1203,7 @@ def bench_pair(args, ctx, capi, rank, world, torch, dist, extras=False):
             except Exception as e:
                 res["c2"] = {"error": "%s: %s" % (type(e).__name__, e)}
             PROGRESS["headline"] = res
-            if not args.no_cpu_baseline:
+            if args.cpu_legs:
                 GUARD.arm("e2e", args.leg_timeout)
                 try:
                     res["e2e"] = e2e_leg(args, ctx, a, b)
@@ -1176,14 +1228,20 @@ def main():
                     help="entries per list (--entries: the spelling to use under torch.distributed.run, whose own parser takes --n for an abbreviation)")
     ap.add_argument("--k", type=int, default=25)
     ap.add_argument("--cpu-sample", type=int, default=200_000_000, help="records per list timed on the CPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline does not need: the CPU baselines and their verification against the reference binary (every "
+                         "workload), and in the default line the union8 record and, at N = 1, the c2, e2e and shard_projection records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="pair workloads: after the timed steps, write what the last step computed to DIR/*.npy (float64; totals and a fixed "
+                         "seeded sample of the output records, at most 32 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--two-pass", action="store_true", help="count+scan+write instead of the single-pass kernel")
     ap.add_argument("--ns", type=int, default=1_000_000_000, help="sort: words")
     ap.add_argument("--nt", type=int, default=100_000_000, help="table: entries per list")
     ap.add_argument("--nt-lists", type=int, default=6, help="table: lists")
     ap.add_argument("--kway-max", type=int, default=0, choices=[0, 8, 32, 33], help="table: library option kway_max (8: lists beyond eight by merges, as in round 4)")
     ap.add_argument("--workload", choices=["intersect", "c2", "union8", "union32", "intersect8", "sort", "table"], default="intersect",
-                    help="intersect: BASELINE configs[1] (default, the headline metric; the line also embeds a union8 record); c2: configs[2], "
+                    help="intersect: BASELINE configs[1] (default, the headline metric; with --full the line also embeds a union8 record); c2: configs[2], "
                          "union + first complement with cutoff 3 on the same pair; union8: configs[3] alone, 8-way union sharded by key range "
                          "over the ranks with an RCCL gatherv to rank 0 (strong scaling); union32: 32 lists (glistmaker's collation width); "
                          "intersect8: eight lists, MakeIntersection.pl's job")
@@ -1196,8 +1254,8 @@ def main():
     ap.add_argument("--project-shards", type=int, default=0, metavar="N",
                     help="ONE GPU: run each of the N key-range shards of the job (union8 or intersect) as its own timed call and project the N-GPU speed-up")
     ap.add_argument("--exchange-ms", type=float, default=None, help="--project-shards: totals-exchange latency per step to add (default: measured with a one-rank RCCL all-gather)")
-    ap.add_argument("--no-union8", action="store_true", help="intersect: leave the union8 record out of the line")
-    ap.add_argument("--no-extras", action="store_true", help="intersect at N = 1: leave the c2, e2e and shard_projection records out of the line")
+    ap.add_argument("--no-union8", action="store_true", help="intersect with --full: leave the union8 record out of the line")
+    ap.add_argument("--no-extras", action="store_true", help="intersect at N = 1 with --full: leave the c2, e2e and shard_projection records out of the line")
     ap.add_argument("--e2e-n", type=int, default=200_000_000, help="e2e record: records of list A written to the sample files (list B: the same key range)")
     ap.add_argument("--leg-timeout", type=float, default=420.0, help="wall-clock bound per leg (pair, c2, e2e, union8): beyond it the line is printed as far as it got and the run exits 4")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong",
@@ -1205,6 +1263,9 @@ def main():
                          "(gt4hip_shard_first_key) and the header totals are all-gathered inside every step; weak = one independent pair of "
                          "--n entries per GPU, no exchange")
     args = ap.parse_args()
+    if args.dump_outputs and (args.workload not in ("intersect", "c2") or args.project_shards):
+        ap.error("--dump-outputs: the pair workloads (intersect, c2) only")
+    args.cpu_legs = args.full and not args.no_cpu_baseline
     args.union8_no_cpu = False
 
     own_stdout()
@@ -1233,7 +1294,7 @@ def main():
         ctx.set_option("two_pass", 1)
     res = None
     default_line = args.workload == "intersect" and not args.project_shards
-    extras = default_line and world == 1 and not args.no_extras
+    extras = default_line and world == 1 and args.full and not args.no_extras
     GUARD.arm(args.workload, args.leg_timeout)
     if args.project_shards:
         res = project_shards(args, ctx, capi)
@@ -1246,7 +1307,7 @@ def main():
     else:
         res = bench_pair(args, ctx, capi, rank, world, torch, dist, extras=extras)
         PROGRESS["headline"] = res
-        if default_line and not args.no_union8:
+        if default_line and args.full and not args.no_union8:
             # the other north-star number in the same line: the 8-way union as ONE job over the same ranks.  Whatever
             # happens in here -- an exception on every rank, a gather that fails at first contact -- the intersection
             # line above is printed, with what the union had measured by then.

@@ -17,6 +17,20 @@ OP_FILES = {1: "union", 2: "intrsec", 4: "0_diff1", 8: "0_diff2"}
 _cache = {}
 
 
+def c1_lists(n=10_000_000):
+    """The two k=16 lists of BASELINE configs[0] (tests/test_config_c1.py), rebuilt from their seed; c1_golden.json holds
+    what the reference binary made of them.  A shared universe of 1.5 n ascending unique keys < 4^16: every third key
+    is in both lists, the others alternate between A and B -> |A| = |B| = n, |A n B| = n / 2."""
+    from genometester4_amd.listio import make_records
+    rng = np.random.default_rng(16)
+    idx = np.arange(3 * n // 2, dtype=np.uint64)
+    keys = idx * np.uint64(200) + rng.integers(0, 200, size=len(idx), dtype=np.uint64)
+    in_a, in_b = idx % 3 != 2, idx % 3 != 1
+    a = make_records(keys[in_a], rng.integers(1, 9, size=int(in_a.sum()), dtype=np.uint32))
+    b = make_records(keys[in_b], rng.integers(1, 9, size=int(in_b.sum()), dtype=np.uint32))
+    return a, b
+
+
 def load():
     if not _cache:
         with open(os.path.join(GOLDEN, "cases.json")) as f:

@@ -51,8 +51,14 @@ def workdir():
 def _run(binary, argv, cwd, env_extra, timeout=120):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=97", UBSAN_OPTIONS="print_stacktrace=1:exitcode=98",
                TSAN_OPTIONS="exitcode=99:halt_on_error=0", **env_extra)
+    cmd = [binary] + argv
+    if binary.endswith("_tsan"):
+        # ThreadSanitizer (gcc 11) fits the program into a fixed memory layout: on kernels that randomise mappings with
+        # more bits than that layout allows it dies at start-up ("unexpected memory mapping"), so this process alone
+        # runs without address-space randomisation (what newer ThreadSanitizers do by re-executing themselves)
+        cmd = ["setarch", os.uname().machine, "-R"] + cmd
     before = set(os.listdir(cwd))
-    p = subprocess.run([binary] + argv, cwd=cwd, capture_output=True, timeout=timeout, env=env)
+    p = subprocess.run(cmd, cwd=cwd, capture_output=True, timeout=timeout, env=env)
     created = sorted(set(os.listdir(cwd)) - before)
     data = {}
     for f in created:

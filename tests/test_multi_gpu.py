@@ -59,7 +59,7 @@ def _bench(n_ranks, args, env_extra=None):
 
 
 SMALL_PAIR = ["--workload", "intersect", "--entries", "6000000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-union8"]
-SMALL_BOTH = ["--entries", "6000000", "--entries8", "1500000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras"]
+SMALL_BOTH = ["--full", "--entries", "6000000", "--entries8", "1500000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras"]
 SMALL_UNION = ["--workload", "union8", "--entries8", "1500000", "--steps", "2", "--warmup", "1"]
 
 
@@ -73,7 +73,7 @@ def test_weak_scaling_line_equals_the_default_line_on_one_gpu():
 
 
 def test_default_line_carries_the_union8_record_and_checks_itself():
-    """what the driver runs: no workload flags -> the intersection line with the 8-way union embedded, both
+    """no workload flags, --full -> the intersection line with the 8-way union embedded, both
     checked against the generator's closed forms (|A n B| = n / 2, 5 n distinct keys)"""
     r = _bench(1, SMALL_BOTH)
     assert r["self_check"] == "ok" and r["config"]["output_records"]["intrsec"] == 3000000
@@ -99,7 +99,7 @@ def test_two_ranks_on_one_device_default_line():
 def test_eight_ranks_on_one_device_default_line():
     """the driver's N = 8 command with all eight ranks on device 0 (gloo): the totals of one GPU, every record in
     exactly one shard, empty shards included (equal-width ranges of a clustered list leave ranks without records)"""
-    small = ["--entries", "1600000", "--entries8", "400000", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extras"]
+    small = ["--full", "--entries", "1600000", "--entries8", "400000", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extras"]
     one = _bench(1, small)
     eight = _bench(8, small, {"GT4_BENCH_ONE_DEVICE": "1"})
     assert eight["scaling"] == "strong" and eight["n_gpus"] == 8 and eight["self_check"] == "ok"
@@ -219,7 +219,7 @@ def test_default_line_at_one_gpu_carries_config2_the_projection_and_the_file_to_
     """VERDICT round 5, next 2 b: what only the builder's own runs showed is in the driver's line -- BASELINE configs[2] on the
     same resident pair (verified against the reference binary), the eight shards of the union one after another, the
     C command-line tool file -> file against the reference binary (byte-identical outputs), file-writing CPU leg = median of 3"""
-    r = _bench(1, ["--entries", "6000000", "--entries8", "1500000", "--steps", "2", "--warmup", "1", "--cpu-sample", "4000000", "--e2e-n", "1000000"])
+    r = _bench(1, ["--full", "--entries", "6000000", "--entries8", "1500000", "--steps", "2", "--warmup", "1", "--cpu-sample", "4000000", "--e2e-n", "1000000"])
     assert r["self_check"] == "ok" and r["verified"] is True
     assert "median of 3" in r["cpu_baseline"]["file_writing"]["sample"]
     c2 = r["c2"]
@@ -232,7 +232,7 @@ def test_default_line_at_one_gpu_carries_config2_the_projection_and_the_file_to_
     assert r["union8"]["self_check"] == "ok" and "error" not in r["union8"]
 
 
-SMALL_GATHER = ["--entries", "3000000", "--entries8", "800000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+SMALL_GATHER = ["--full", "--entries", "3000000", "--entries8", "800000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
 
 
 @pytest.mark.parametrize("ranks", [2, 8])
@@ -292,3 +292,41 @@ def test_device_lists_as_torch_tensors_without_a_copy():
         assert not h.is_cuda and h.numpy().view(RECORD_DTYPE).tobytes() == rec[:100].tobytes()
     finally:
         ctx.close()
+
+
+def test_plain_line_is_the_headline_alone():
+    """`bench.py --gpus 1 --steps N --warmup W`: N timed steps, the headline fields, and none of the legs --full adds"""
+    r = _bench(1, ["--entries", "6000000", "--entries8", "1500000", "--steps", "3", "--warmup", "1"])
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["value"] > 0
+    assert r["unit"] == "k-mers/s" and r["higher_is_better"] is True and r["dtype"] == "u64 keys + u32 counts"
+    assert r["metric"].startswith("k-mers merged/sec, 2-list k=25 intersection") and r["self_check"] == "ok"
+    assert r["config"]["output_records"]["intrsec"] == 3000000 and r["roofline"]["frac"] > 0
+    assert not {"cpu_baseline", "verified", "union8", "c2", "e2e", "shard_projection"} & set(r)
+
+
+def test_dump_outputs_are_what_the_timed_steps_computed_and_the_same_every_run(tmp_path):
+    """--dump-outputs: the totals of the last timed step and a seeded sample of its records, float64, identical in two
+    runs with the same arguments; c2 writes both of its output streams"""
+    import numpy as np
+    args = ["--entries", "6000000", "--steps", "2", "--warmup", "1"]
+    one, two = tmp_path / "one", tmp_path / "two"
+    r = _bench(1, args + ["--dump-outputs", str(one)])
+    _bench(1, args + ["--dump-outputs", str(two)])
+    names = sorted(p.name for p in one.iterdir())
+    assert names == sorted("intrsec_%s.npy" % w for w in ("totals", "index", "key_hi", "key_lo", "count"))
+    assert sum((one / f).stat().st_size for f in names) <= 64 << 20
+    for f in names:
+        a, b = np.load(one / f), np.load(two / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b), f
+    d = {f[len("intrsec_"):-len(".npy")]: np.load(one / f) for f in names}
+    assert list(d["totals"]) == [r["config"]["output_records"]["intrsec"], r["config"]["output_total_count"]["intrsec"]]
+    idx = d["index"]
+    assert 0 < len(idx) < 3000000 and (np.diff(idx) > 0).all() and idx[-1] < 3000000
+    keys = d["key_hi"] * 2.0 ** 32 + d["key_lo"]
+    assert (np.diff(keys) > 0).all() and keys[-1] < 4.0 ** 25 and (d["count"] >= 1).all()
+    c2 = tmp_path / "c2"
+    r2 = _bench(1, ["--workload", "c2"] + args + ["--dump-outputs", str(c2)])
+    for name in ("union", "diff1"):
+        t = np.load(c2 / ("%s_totals.npy" % name))
+        assert list(t) == [r2["config"]["output_records"][name], r2["config"]["output_total_count"][name]]
+        assert len(np.load(c2 / ("%s_count.npy" % name))) == len(np.load(c2 / ("%s_key_lo.npy" % name))) > 0
