@@ -90,3 +90,30 @@ def list_file_bytes(word_length, n_words, total_count, records):
 def input_records(inputs, filename):
     rec, k, _ = inputs[filename[:-5]]
     return rec, k
+
+
+COUNT_EDGE_K = 16
+COUNT_EDGE_VALUES = (0, 1, 2, 3, (1 << 31) - 1, 1 << 31, (1 << 31) + 1, (1 << 32) - 2, (1 << 32) - 1)
+
+
+def count_edge_lists(n=200_000, n_lists=33):
+    """The inputs of tests/golden/count_edges.json, rebuilt from their seed: n_lists k=16 lists of about n records out
+    of one universe, every list holding about 62 % of it.  Counts: half small (0..4), half from COUNT_EDGE_VALUES -- pair
+    sums of exactly 2^32 and 2^32 + 1, and N-way sums of eight 2^31 that wrap."""
+    from genometester4_amd.listio import make_records
+    rng = np.random.default_rng(20261016)
+    universe = np.unique(rng.integers(0, 1 << 32, size=int(n * 1.62), dtype=np.uint64))
+    edges = np.array(COUNT_EDGE_VALUES, dtype=np.uint64).astype(np.uint32)
+    lists = []
+    for _ in range(n_lists):
+        keys = universe[rng.random(len(universe)) < 0.62]
+        counts = edges[rng.integers(0, len(edges), size=len(keys))]
+        small = rng.random(len(keys)) < 0.5
+        counts[small] = rng.integers(0, 5, size=int(small.sum()), dtype=np.uint32)
+        lists.append(make_records(keys, counts))
+    return lists
+
+
+def load_count_edges():
+    with open(os.path.join(GOLDEN, "count_edges.json")) as f:
+        return json.load(f)
