@@ -31,6 +31,20 @@ class CompareResult(C.Structure):
                 ("merge_kernel_ms", C.c_double), ("device_ms", C.c_double), ("merge_tiles", C.c_uint64)]
 
 
+class MismatchParams(C.Structure):
+    _fields_ = [("ops", C.c_uint32), ("cutoff", C.c_uint32), ("subtract", C.c_int32), ("n_mismatch", C.c_uint32),
+                ("count_only", C.c_int32)]
+
+
+MM_MAX_LEVELS = 32
+
+
+class MismatchStats(C.Structure):
+    _fields_ = [("prepass_words", C.c_uint64 * 2), ("prepass_ms", C.c_double), ("n_levels", C.c_uint32),
+                ("level_ms", C.c_double * MM_MAX_LEVELS), ("level_words", C.c_uint64 * MM_MAX_LEVELS),
+                ("level_probes", C.c_uint64 * MM_MAX_LEVELS), ("probes", C.c_uint64)]
+
+
 class MultiResult(C.Structure):
     _fields_ = [("n_words", C.c_uint64), ("total_count", C.c_uint64), ("out", C.c_void_p), ("device_ms", C.c_double),
                 ("records_read", C.c_uint64), ("records_written", C.c_uint64)]
@@ -53,7 +67,7 @@ SYMBOLS = [
     "gt4hip_get_counter", "gt4hip_device_memory", "gt4hip_list_upload_fd", "gt4hip_list_load_fd", "gt4hip_list_load",
     "gt4hip_list_write_fd", "gt4hip_lists_write_fd", "gt4hip_shard_first_key", "gt4hip_shard_cuts", "gt4hip_comm_unique_id", "gt4hip_comm_create", "gt4hip_comm_destroy", "gt4hip_comm_allgather_totals", "gt4hip_comm_allgather_u64", "gt4hip_context_device", "gt4hip_trim",
     "gt4hip_comm_rank", "gt4hip_comm_size", "gt4hip_comm_last_error", "gt4hip_comm_gatherv", "gt4hip_sort_words", "gt4hip_words_to_list",
-    "gt4hip_device_words_to_list",
+    "gt4hip_device_words_to_list", "gt4hip_compare_mismatch", "gt4hip_mismatch_stats_get",
 ]
 
 _lib = None
@@ -97,6 +111,8 @@ def lib():
             "gt4hip_list_lower_bound": (C.c_int, [vp, vp, u64, C.POINTER(u64)]),
             "gt4hip_list_get_word": (C.c_int, [vp, vp, u64, C.POINTER(u64), C.POINTER(u32)]),
             "gt4hip_compare": (C.c_int, [vp, vp, vp, C.POINTER(CompareParams), C.POINTER(CompareResult)]),
+            "gt4hip_compare_mismatch": (C.c_int, [vp, vp, vp, C.POINTER(MismatchParams), C.POINTER(CompareResult)]),
+            "gt4hip_mismatch_stats_get": (C.c_int, [vp, C.POINTER(MismatchStats)]),
             "gt4hip_union_multi": (C.c_int, [vp, C.POINTER(vp), u32, u32, i32, u32, i32, C.POINTER(MultiResult)]),
             "gt4hip_intersect_multi": (C.c_int, [vp, C.POINTER(vp), u32, u32, i32, u32, i32, C.POINTER(MultiResult)]),
             "gt4hip_union_table": (C.c_int, [vp, C.POINTER(vp), u32, C.POINTER(CountTable)]),
@@ -376,6 +392,35 @@ class Context:
                     else:
                         lists[1 << k] = DeviceList(self, C.c_void_p(res.out[k]))
         timing = dict(merge_kernel_ms=res.merge_kernel_ms, device_ms=res.device_ms, merge_tiles=res.merge_tiles)
+        return stats, lists, timing
+
+    def compare_mismatch(self, a: DeviceList, b: DeviceList, ops, n_mismatch, cutoff=1, subtract=0, count_only=False,
+                         out=None):
+        """glistcompare -mm: returns (stats, lists, timing) as compare() does, for the bits OP_DIFF1 / OP_DIFF2;
+        timing also holds the pre-pass and per-level device times, table sizes and probe counts."""
+        prm = MismatchParams(ops, cutoff, 1 if subtract else 0, n_mismatch, 1 if count_only else 0)
+        res = CompareResult()
+        if out:
+            for k in (2, 3):
+                if out.get(1 << k) is not None:
+                    res.out[k] = out[1 << k].h.value
+        self._chk(lib().gt4hip_compare_mismatch(self.h, a.h, b.h, C.byref(prm), C.byref(res)))
+        st = MismatchStats()
+        self._chk(lib().gt4hip_mismatch_stats_get(self.h, C.byref(st)))
+        stats, lists = {}, {}
+        for k in (2, 3):
+            if ops >> k & 1:
+                stats[1 << k] = (res.n_words[k], res.total_count[k])
+                if not count_only:
+                    if out and out.get(1 << k) is not None:
+                        lists[1 << k] = out[1 << k]
+                    else:
+                        lists[1 << k] = DeviceList(self, C.c_void_p(res.out[k]))
+        n = min(st.n_levels, MM_MAX_LEVELS)
+        timing = dict(merge_kernel_ms=res.merge_kernel_ms, device_ms=res.device_ms, prepass_ms=st.prepass_ms,
+                      prepass_words=(st.prepass_words[0], st.prepass_words[1]),
+                      level_ms=[st.level_ms[i] for i in range(n)], level_words=[st.level_words[i] for i in range(n)],
+                      level_probes=[st.level_probes[i] for i in range(n)], probes=st.probes)
         return stats, lists, timing
 
     def _multi(self, fn, lists, cutoff, rule, count_override, count_only, out=None):

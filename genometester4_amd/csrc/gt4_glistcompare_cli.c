@@ -7,8 +7,14 @@
  * as the reference's main() (reference src/glistcompare.c:84-429, naming :814-834, :907-953).
  * Deliberate differences, all loud:
  *   - a file that cannot be opened is an error message + exit 1 (the reference dereferences NULL);
- *   - -mm and --subset are outside the GPU path: error + exit 1 (GT4I index inputs are read as
- *     the sorted k-mer lists they contain, as in the reference);
+ *   - --subset is outside the GPU path: error + exit 1 (GT4I index inputs are read as the sorted
+ *     k-mer lists they contain, as in the reference);
+ *   - -mm N (difference up to N mismatches, gt4hip_compare_mismatch) runs on one GPU with both lists
+ *     resident: with --gpus N > 1 or GT4HIP_HBM_LIMIT it is an error + exit 1, and inputs that do not fit
+ *     the device memory are an out-of-memory error, not a chunked run.  An empty lookup list holds no
+ *     neighbour (the reference crashes there); -dd -du computes diff2 as the reference does, without its
+ *     assertion message per lookup; -D prints the reference's level-1 lines, not the per-word and
+ *     per-probe traces of -D -D and more;
  *   - --stream and --disable_scouts are accepted and ignored (the whole list is uploaded to HBM;
  *     results are identical for well-formed files);
  *   - GT4HIP_VERBOSE=1 prints the device, kernel times and the chunk plan on stderr (-D prints exactly
@@ -35,6 +41,11 @@
 #include "gt4hip.h"
 
 #define MAX_FILES 1024
+
+/* Weak: the product links libgt4hip.so, which defines both; the host-only sanitizer build of this file
+ * (tests/harness, a CPU stand-in for the device layer) has no -mm path and leaves them NULL. */
+#pragma weak gt4hip_compare_mismatch
+#pragma weak gt4hip_mismatch_stats_get
 
 enum { OPT_PLAIN, OPT_VERSION, OPT_HELP, OPT_OUT, OPT_CUTOFF, OPT_MM, OPT_UNION, OPT_INTRSEC, OPT_DIFF, OPT_DDIFF, OPT_DU,
        OPT_COUNT_ONLY, OPT_RULE, OPT_SUBSET, OPT_SEED, OPT_PRINT_OP, OPT_NOSCOUTS, OPT_STREAM, OPT_DEBUG, OPT_GPUS };
@@ -159,6 +170,146 @@ static uint64_t parse_bytes (const char *s)
   else if (*end == 'M' || *end == 'm') v *= 1024.0 * 1024.0;
   else if (*end == 'G' || *end == 'g') v *= 1024.0 * 1024.0 * 1024.0;
   return v > 0 ? (uint64_t) v : 0;
+}
+
+/* compare_wordmaps_mm (reference :958-1093): two lists, diff1 and / or diff2 up to nmm mismatches */
+static int mismatch_main (GT4ListFile *files, unsigned int wlen, int find_diff, int find_ddiff, int subtraction, int countonly,
+                          const char *outputname, unsigned int cutoff, unsigned int nmm, int debug, int verbose, int n_gpus, uint64_t hbm_limit,
+                          const char *const *fnames)
+{
+  if (debug) {
+    fprintf (stderr, "compare_wordmaps: List 1: %llu entries\n", (unsigned long long) files[0].header.n_words);
+    fprintf (stderr, "compare_wordmaps; List 2: %llu entries\n", (unsigned long long) files[1].header.n_words);
+    fprintf (stderr, "Table 1: %llu entries\n", (unsigned long long) files[0].header.n_words);
+    fprintf (stderr, "Table 2: %llu entries\n", (unsigned long long) files[1].header.n_words);
+  }
+  /* without -d / -dd / -du the reference takes this path all the same and writes nothing */
+  if (!find_diff) {
+    for (unsigned int f = 0; f < 2; f++) gt4_listfile_close (&files[f]);
+    return 0;
+  }
+  if (n_gpus > 1 || hbm_limit) {
+    fprintf (stderr, "Error: -mm needs both lists resident on one GPU: it cannot be combined with %s\n",
+             n_gpus > 1 ? "--gpus N > 1 (GT4HIP_GPUS)" : "GT4HIP_HBM_LIMIT");
+    return 1;
+  }
+  if (!gt4hip_compare_mismatch || !gt4hip_mismatch_stats_get) {
+    fprintf (stderr, "Error: this build has no -mm (mismatch difference) path\n");
+    return 1;
+  }
+  gt4hip_context *ctx = NULL;
+  const char *dev = getenv ("GT4HIP_DEVICE");
+  if (gt4hip_create (dev ? atoi (dev) : 0, &ctx)) {
+    fprintf (stderr, "Error: %s\n", gt4hip_last_error (NULL));
+    return 1;
+  }
+  if (verbose) fprintf (stderr, "Device: %s\n", gt4hip_device_info (ctx));
+  /* inputs, outputs and the lookup tables (~48 bytes per record of each side) must fit: there is no chunked -mm */
+  uint64_t free_b = 0, total_b = 0;
+  gt4hip_device_memory (ctx, &free_b, &total_b);
+  const uint64_t na = files[0].header.n_words, nb = files[1].header.n_words;
+  const uint64_t need = 12 * (na + nb) + 60 * na + (find_ddiff ? 60 * nb : 0);
+  if (free_b && need > free_b / 100 * 90) {
+    fprintf (stderr, "Error: %s: -mm needs about %llu bytes of device memory, %llu are free (both lists stay resident on one GPU)\n",
+             gt4hip_strerror (GT4HIP_ENOMEM), (unsigned long long) need, (unsigned long long) free_b);
+    gt4hip_destroy (ctx);
+    return 1;
+  }
+  gt4hip_list *lists[2];
+  for (unsigned int f = 0; f < 2; f++) {
+    if (files[f].index_kmers ? gt4hip_list_upload_index (ctx, files[f].index_kmers, files[f].header.n_words, files[f].index_locations, wlen, &lists[f])
+                             : gt4hip_list_upload (ctx, files[f].records, files[f].header.n_words, wlen, &lists[f])) {
+      fprintf (stderr, "Error: uploading %s to the GPU failed: %s\n", fnames[f], gt4hip_last_error (ctx));
+      return 1;
+    }
+    if (getenv ("GT4HIP_CHECK_SORTED") && atoi (getenv ("GT4HIP_CHECK_SORTED"))) {
+      int sorted = 0;
+      if (gt4hip_list_is_sorted (ctx, lists[f], &sorted) || !sorted) {
+        fprintf (stderr, "Error: File %s is not sorted by k-mer (strictly ascending, unique)\n", fnames[f]);
+        return 1;
+      }
+    }
+  }
+  gt4hip_mismatch_params prm;
+  memset (&prm, 0, sizeof prm);
+  prm.ops = GT4HIP_OP_DIFF1 | (find_ddiff ? GT4HIP_OP_DIFF2 : 0);
+  prm.cutoff = cutoff;
+  prm.subtract = subtraction;
+  prm.n_mismatch = nmm;
+  prm.count_only = countonly;
+  gt4hip_compare_result res;
+  memset (&res, 0, sizeof res);
+  if (gt4hip_compare_mismatch (ctx, lists[0], lists[1], &prm, &res)) {
+    fprintf (stderr, "Error: %s\n", gt4hip_last_error (ctx));
+    return 1;
+  }
+  gt4hip_mismatch_stats st;
+  gt4hip_mismatch_stats_get (ctx, &st);
+  if (debug) fprintf (stderr, "Finding diff with mismatches (%llu entries)\n", (unsigned long long) st.prepass_words[0]);
+  if (verbose) {
+    fprintf (stderr, "GPU mismatch pre-pass: %.3f ms, device total %.3f ms, %llu probes\n", res.merge_kernel_ms, res.device_ms,
+             (unsigned long long) st.probes);
+    for (uint32_t l = 0; l < st.n_levels; l++)
+      fprintf (stderr, "  level %u: %llu words, %llu probes, %.3f ms\n", l + 1, (unsigned long long) st.level_words[l],
+               (unsigned long long) st.level_probes[l], st.level_ms[l]);
+  }
+  int bad = 0;
+  if (countonly) {
+    for (int s = 2; s < 4; s++)
+      if ((prm.ops >> s) & 1u) fprintf (stdout, "NUnique\t%llu\nNTotal\t%llu\n", (unsigned long long) res.n_words[s], (unsigned long long) res.total_count[s]);
+  } else {
+    /* "<out>_<k>_<N>_diff1.list" / "_diff2.list", written as ".tmp" and renamed (reference :1072-1091) */
+    char name[4][2048], tmp_name[4][2100];
+    GT4ListWriter w[4];
+    const gt4hip_list *wl[2];
+    uint64_t wfirst[2], wcount[2], woff[2];
+    int wfd[2], ws[2];
+    uint32_t nw = 0;
+    for (int s = 2; s < 4 && !bad; s++) {
+      if (!((prm.ops >> s) & 1u)) continue;
+      snprintf (name[s], sizeof name[s], "%s_%u_%u_%s.list", outputname, wlen, nmm, s == 2 ? "diff1" : "diff2");
+      snprintf (tmp_name[s], sizeof tmp_name[s], "%s.tmp", name[s]);
+      if (gt4_listwriter_begin (&w[s], tmp_name[s], wlen, 0666)) {
+        fprintf (stderr, "Error: Cannot create output file %s\n", tmp_name[s]);
+        bad = 1;
+        break;
+      }
+      wl[nw] = res.out[s];
+      wfirst[nw] = 0;
+      wcount[nw] = res.n_words[s];
+      wfd[nw] = w[s].fd;
+      woff[nw] = 48;
+      ws[nw] = s;
+      nw++;
+    }
+    if (!bad && nw && gt4hip_lists_write_fd (ctx, nw, wl, wfirst, wcount, wfd, woff)) {
+      fprintf (stderr, "Error: writing the results failed: %s\n", gt4hip_last_error (ctx));
+      bad = 1;
+    }
+    for (uint32_t q = 0; q < nw; q++) {
+      const int s = ws[q];
+      if (bad) {
+        gt4_listwriter_abort (&w[s]);
+        unlink (tmp_name[s]);
+        continue;
+      }
+      if (gt4_listwriter_finish (&w[s], res.n_words[s], res.total_count[s])) {
+        fprintf (stderr, "Error: writing %s failed: %s\n", tmp_name[s], strerror (errno));
+        unlink (tmp_name[s]);
+        bad = 1;
+      } else if (rename (tmp_name[s], name[s])) {
+        fprintf (stderr, "Error: Cannot rename %s to %s\n", tmp_name[s], name[s]);
+        bad = 1;
+      }
+    }
+    for (int s = 2; s < 4; s++) gt4hip_list_free (res.out[s]);
+  }
+  for (unsigned int f = 0; f < 2; f++) {
+    gt4hip_list_free (lists[f]);
+    gt4_listfile_close (&files[f]);
+  }
+  gt4hip_destroy (ctx);
+  return bad;
 }
 
 int main (int argc, const char *argv[])
@@ -371,10 +522,8 @@ int main (int argc, const char *argv[])
              find_ddiff ? "X" : "", rule, nfiles);
     for (unsigned int f = 0; f < nfiles; f++) fprintf (stdout, "%u\t%s\n", f, fnames[f]);
   }
-  if (nmm) {
-    fprintf (stderr, "Error: -mm (mismatch difference) is not part of the GPU set-operation path\n");
-    exit (1);
-  }
+  if (nmm) return mismatch_main (files, wlen, find_diff, find_ddiff, subtraction, countonly, outputname, cutoff, nmm, debug, verbose, n_gpus,
+                                 parse_bytes (getenv ("GT4HIP_HBM_LIMIT")), fnames);
 
 
   /* ---- key-range shards: several GPUs and / or chunks streamed through the device memory */

@@ -66,6 +66,7 @@ struct gt4hip_context {
   uint64_t nway_tiles;
   int last_multi_one_pass;   /* the last gt4hip_union_multi was done by the one-pass tile kernel (counter "nway_one_pass") */
   gt4hip_io *io;            /* file <-> HBM staging (gt4hip_io.hip), NULL until first used */
+  gt4hip_mismatch_stats mm_stats; /* the last gt4hip_compare_mismatch (gt4hip_mismatch.hip) */
   char err[512];
   char info[256];
 };

@@ -183,6 +183,41 @@ typedef struct {
 int gt4hip_compare (gt4hip_context *ctx, const gt4hip_list *a, const gt4hip_list *b,
                     const gt4hip_compare_params *params, gt4hip_compare_result *result);
 
+/* ---------------------------------------------------------------- (ii b) difference up to N mismatches */
+
+/* Arguments of compare_wordmaps_mm (glistcompare -mm N, src/glistcompare.c:958-1093). */
+typedef struct {
+  uint32_t ops;          /* GT4HIP_OP_DIFF1 and/or GT4HIP_OP_DIFF2 only             */
+  uint32_t cutoff;
+  int32_t  subtract;     /* -du                                                    */
+  uint32_t n_mismatch;   /* N >= 1                                                 */
+  int32_t  count_only;
+} gt4hip_mismatch_params;
+
+/* Per-call measurements of the last gt4hip_compare_mismatch on a context (gt4hip_mismatch_stats_get). */
+#define GT4HIP_MM_MAX_LEVELS 32
+typedef struct {
+  uint64_t prepass_words[2];                    /* table sizes after the pre-pass: diff1, diff2 (0 if not requested) */
+  double prepass_ms;                            /* device time of the pre-pass (= result.merge_kernel_ms)          */
+  uint32_t n_levels;                            /* levels run: min(n_mismatch, GT4HIP_MM_MAX_LEVELS)               */
+  double level_ms[GT4HIP_MM_MAX_LEVELS];        /* device time of level c + 1, both tables                         */
+  uint64_t level_words[GT4HIP_MM_MAX_LEVELS];   /* words that entered level c + 1, both tables                     */
+  uint64_t level_probes[GT4HIP_MM_MAX_LEVELS];  /* index lookups level c + 1 performed (after early exits)          */
+  uint64_t probes;                              /* all lookups of the call, the pre-pass's included                */
+} gt4hip_mismatch_stats;
+
+/* The difference of a and b "up to N mismatches" (fetch_relevant_words, src/glistcompare.c:1134-1168): the
+ * pre-pass table of compare_wordmaps_mm, then levels c = 1..N in which a word survives while the number of its
+ * exactly-c-substitution variants (canonicalised) PRESENT in the other list -- not their counts -- stays below the
+ * cutoff (with subtract: present in b and not in a count -1 each, and any variant in b but not in a drops the word).
+ * Results go to slots 2 and 3 of `result` under the rules of gt4hip_compare (caller-provided lists, count_only);
+ * merge_kernel_ms is the pre-pass, device_ms the whole call.  An empty lookup list holds no neighbour (the
+ * reference crashes there).  Any op bit other than DIFF1 / DIFF2, or n_mismatch 0, is GT4HIP_EINVAL. */
+int gt4hip_compare_mismatch (gt4hip_context *ctx, const gt4hip_list *a, const gt4hip_list *b,
+                             const gt4hip_mismatch_params *params, gt4hip_compare_result *result);
+/* The measurements of the context's last successful gt4hip_compare_mismatch. */
+int gt4hip_mismatch_stats_get (gt4hip_context *ctx, gt4hip_mismatch_stats *stats);
+
 /* ---------------------------------------------------------------- (iii) N-way operations */
 
 typedef struct {
