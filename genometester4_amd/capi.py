@@ -45,6 +45,17 @@ class MismatchStats(C.Structure):
                 ("level_probes", C.c_uint64 * MM_MAX_LEVELS), ("probes", C.c_uint64)]
 
 
+class QueryParams(C.Structure):
+    _fields_ = [("n_mm", C.c_uint32), ("pm_3", C.c_uint32), ("canonize", C.c_int32)]
+
+
+class QueryHit(C.Structure):
+    _fields_ = [("query", C.c_uint64), ("rank", C.c_uint64), ("word", C.c_uint64), ("count", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+QUERY_HIT_DTYPE = np.dtype([("query", "<u8"), ("rank", "<u8"), ("word", "<u8"), ("count", "<u4"), ("reserved", "<u4")])
+
+
 class MultiResult(C.Structure):
     _fields_ = [("n_words", C.c_uint64), ("total_count", C.c_uint64), ("out", C.c_void_p), ("device_ms", C.c_double),
                 ("records_read", C.c_uint64), ("records_written", C.c_uint64)]
@@ -68,6 +79,9 @@ SYMBOLS = [
     "gt4hip_list_write_fd", "gt4hip_lists_write_fd", "gt4hip_shard_first_key", "gt4hip_shard_cuts", "gt4hip_comm_unique_id", "gt4hip_comm_create", "gt4hip_comm_destroy", "gt4hip_comm_allgather_totals", "gt4hip_comm_allgather_u64", "gt4hip_context_device", "gt4hip_trim",
     "gt4hip_comm_rank", "gt4hip_comm_size", "gt4hip_comm_last_error", "gt4hip_comm_gatherv", "gt4hip_sort_words", "gt4hip_words_to_list",
     "gt4hip_device_words_to_list", "gt4hip_compare_mismatch", "gt4hip_mismatch_stats_get",
+    "gt4hip_query_index_create", "gt4hip_query_index_free", "gt4hip_query_index_last_ms", "gt4hip_query_variants",
+    "gt4hip_query_variant_mask", "gt4hip_query_lookup", "gt4hip_query_lookup_all", "gt4hip_list_count_stats",
+    "gt4hip_list_count_split", "gt4hip_list_count_histogram", "gt4hip_list_gc",
 ]
 
 _lib = None
@@ -146,6 +160,17 @@ def lib():
             "gt4hip_sort_words": (C.c_int, [vp, vp, u64, u32]),
             "gt4hip_words_to_list": (C.c_int, [vp, vp, u64, u32, C.POINTER(vp)]),
             "gt4hip_device_words_to_list": (C.c_int, [vp, vp, u64, u32, C.POINTER(vp)]),
+            "gt4hip_query_index_create": (C.c_int, [vp, vp, C.POINTER(vp)]),
+            "gt4hip_query_index_free": (None, [vp]),
+            "gt4hip_query_index_last_ms": (C.c_double, [vp]),
+            "gt4hip_query_variants": (C.c_int, [u32, C.POINTER(QueryParams), C.POINTER(u64)]),
+            "gt4hip_query_variant_mask": (C.c_int, [u32, C.POINTER(QueryParams), u64, C.POINTER(u64)]),
+            "gt4hip_query_lookup": (C.c_int, [vp, vp, vp, u64, C.POINTER(QueryParams), vp, vp]),
+            "gt4hip_query_lookup_all": (C.c_int, [vp, vp, vp, u64, C.POINTER(QueryParams), vp, u64, C.POINTER(u64)]),
+            "gt4hip_list_count_stats": (C.c_int, [vp, vp, C.POINTER(u32), C.POINTER(u32)]),
+            "gt4hip_list_count_split": (C.c_int, [vp, vp, u32, C.POINTER(u64), C.POINTER(u64)]),
+            "gt4hip_list_count_histogram": (C.c_int, [vp, vp, u32, vp]),
+            "gt4hip_list_gc": (C.c_int, [vp, vp, C.POINTER(u64)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -217,6 +242,33 @@ class DeviceList:
         self.ctx._chk(lib().gt4hip_list_get_word(self.ctx.h, self.h, idx, C.byref(w), C.byref(c)))
         return w.value, c.value
 
+    def count_stats(self):
+        """(smallest, largest) count: one pass on the device (gt4hip_list_count_stats)."""
+        lo, hi = C.c_uint32(), C.c_uint32()
+        self.ctx._chk(lib().gt4hip_list_count_stats(self.ctx.h, self.h, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
+    def count_split(self, med):
+        """(records with count < med, records with count > med) (gt4hip_list_count_split)."""
+        b, a = C.c_uint64(), C.c_uint64()
+        self.ctx._chk(lib().gt4hip_list_count_split(self.ctx.h, self.h, med, C.byref(b), C.byref(a)))
+        return b.value, a.value
+
+    def count_histogram(self, max_count) -> np.ndarray:
+        """hist[c - 1] = records with count c, 1 <= c <= max_count (gt4hip_list_count_histogram)."""
+        hist = np.zeros(max_count, dtype=np.uint64)
+        self.ctx._chk(lib().gt4hip_list_count_histogram(self.ctx.h, self.h, max_count, hist.ctypes.data if max_count else None))
+        return hist
+
+    def gc(self) -> int:
+        """sum of count x (G and C bases of the word) (gt4hip_list_gc)."""
+        v = C.c_uint64()
+        self.ctx._chk(lib().gt4hip_list_gc(self.ctx.h, self.h, C.byref(v)))
+        return v.value
+
+    def query_index(self) -> "QueryIndex":
+        return QueryIndex(self)
+
     def slice(self, first, count) -> "DeviceList":
         h = C.c_void_p()
         self.ctx._chk(lib().gt4hip_list_slice(self.ctx.h, self.h, first, count, C.byref(h)))
@@ -228,6 +280,72 @@ class DeviceList:
         # lists return their storage to the context's pool, so they must not outlive it
         if self.h and self.ctx.h:
             lib().gt4hip_list_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def query_variants(word_length, n_mm, pm_3=0) -> int:
+    """V, the variants per query (gt4hip_query_variants; no device needed)."""
+    prm, v = QueryParams(n_mm, pm_3, 1), C.c_uint64()
+    rc = lib().gt4hip_query_variants(word_length, C.byref(prm), C.byref(v))
+    if rc:
+        raise Gt4HipError(rc, "gt4hip_query_variants (%d, %d, %d)" % (word_length, n_mm, pm_3))
+    return v.value
+
+
+def query_variant_mask(word_length, n_mm, pm_3, rank) -> int:
+    """XOR mask of variant `rank` (gt4hip_query_variant_mask; no device needed)."""
+    prm, m = QueryParams(n_mm, pm_3, 1), C.c_uint64()
+    rc = lib().gt4hip_query_variant_mask(word_length, C.byref(prm), rank, C.byref(m))
+    if rc:
+        raise Gt4HipError(rc, "gt4hip_query_variant_mask (%d, %d, %d, %d)" % (word_length, n_mm, pm_3, rank))
+    return m.value
+
+
+class QueryIndex:
+    """Owning handle of a gt4hip_query_index: the bucket index of a resident list, reused by every batch."""
+
+    def __init__(self, lst: DeviceList):
+        self.list = lst  # the index reads the list's records: keep it alive
+        self.ctx = lst.ctx
+        self.h = C.c_void_p()
+        self.ctx._chk(lib().gt4hip_query_index_create(self.ctx.h, lst.h, C.byref(self.h)))
+        self.ctx._lists.add(self)  # freed with the lists when the context closes
+
+    @property
+    def last_ms(self) -> float:
+        return lib().gt4hip_query_index_last_ms(self.h)
+
+    def lookup(self, words, n_mm=0, pm_3=0, canonize=True):
+        """(values u32, found bool) per query word (gt4hip_query_lookup)."""
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        values, found = np.zeros(len(w), dtype=np.uint32), np.zeros(len(w), dtype=np.uint8)
+        prm = QueryParams(n_mm, pm_3, 1 if canonize else 0)
+        self.ctx._chk(lib().gt4hip_query_lookup(self.ctx.h, self.h, w.ctypes.data if len(w) else None, len(w), C.byref(prm),
+                                                 values.ctypes.data if len(w) else None, found.ctypes.data if len(w) else None))
+        return values, found.astype(bool)
+
+    def lookup_all(self, words, n_mm=0, pm_3=0, canonize=True, capacity=0) -> np.ndarray:
+        """Every variant found, in (query, rank) order, as a QUERY_HIT_DTYPE array (gt4hip_query_lookup_all; a second
+        call when the hits do not fit `capacity`)."""
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        prm, n = QueryParams(n_mm, pm_3, 1 if canonize else 0), C.c_uint64()
+        while True:
+            hits = np.zeros(capacity, dtype=QUERY_HIT_DTYPE)
+            self.ctx._chk(lib().gt4hip_query_lookup_all(self.ctx.h, self.h, w.ctypes.data if len(w) else None, len(w), C.byref(prm),
+                                                         hits.ctypes.data if capacity else None, capacity, C.byref(n)))
+            if n.value <= capacity:
+                return hits[:n.value]
+            capacity = n.value
+
+    def free(self):
+        if self.h and self.ctx.h:
+            lib().gt4hip_query_index_free(self.h)
         self.h = None
 
     def __del__(self):

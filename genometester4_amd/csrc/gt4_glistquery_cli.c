@@ -1,0 +1,920 @@
+/*
+ * gt4_glistquery_cli.c -- `glistquery`, the drop-in command line for looking words up in a list and for
+ * the list statistics.  Host C; every lookup and every pass over a list's counts runs in the HIP kernels
+ * behind include/gt4hip.h (gt4hip_query.hip), the multi-list forms in those behind
+ * include/gt4_set_operations.h.
+ *
+ * Same argv grammar, defaults, validation order, messages, stdout and exit codes as the reference's
+ * main() (reference src/glistquery.c:108-437; search_one_word :543-568, search_n_query_strings :609-662,
+ * print_median :831-889, print_distro :891-909, print_gc :911-932; the FastA / FastQ state machine of
+ * src/fasta.c:87-300 for plain text).  Query words are collected on the host in batches of QUERY_BATCH,
+ * looked up in one call per batch and printed in input order.
+ * Deliberate differences, all loud:
+ *   - gzip-compressed sequence files (-s) are refused: error + exit 1;
+ *   - --locations, --files and --sequences are refused (the location tables of a GT4I index are not
+ *     resident): error + exit 1.  A GT4I index given as a list is read as the sorted k-mer list it
+ *     contains, as glistcompare here does;
+ *   - --bloom and --disable_scouts are accepted and ignored;
+ *   - --distribution skips a record whose count is 0 (the reference writes before its array there);
+ *   - more than 1024 lists are an error (the reference overruns its array);
+ *   - -D prints "List ... loaded" and print_median's trace lines, nothing else is promised;
+ *   - --stat reads headers only and -v / -h nothing at all: they work without a GPU.  The dump of ONE
+ *     list (no query option) is file I/O: it prints the mapped records and opens no device either.
+ *     Everything else fails without a usable GPU: there is no CPU path;
+ *   - the list must fit one device (as for glistcompare -mm); larger is an out-of-memory error;
+ *   - --words-only (not in the reference) prints the packed query words -q / -f / -s / -l would look up,
+ *     one decimal number per line, and opens no device: for tests of the parsers.
+ */
+#define _GNU_SOURCE
+#include <errno.h>
+#include <limits.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "gt4_listfile.h"
+#include "gt4_set_operations.h"
+#include "gt4hip.h"
+
+#define MAX_LISTS 1024
+#define QUERY_BATCH (1u << 20)
+
+enum { CMD_QUERY, CMD_STATS, CMD_GC, CMD_MEDIAN, CMD_DISTRO, CMD_FILES, CMD_SEQUENCES };
+
+enum { OPT_VERSION, OPT_HELP, OPT_SEQFILE, OPT_LISTFILE, OPT_QUERYFILE, OPT_QUERY, OPT_PM, OPT_MM, OPT_MIN, OPT_MAX, OPT_DEBUG, OPT_ALL,
+       OPT_STATS, OPT_MEDIAN, OPT_DISTRO, OPT_GC, OPT_FILES, OPT_SEQUENCES, OPT_LOCATIONS, OPT_3P, OPT_5P, OPT_HEADER, OPT_BLOOM,
+       OPT_IS_UNION, OPT_NOSCOUTS, OPT_WORDS_ONLY };
+
+static const struct {
+  const char *name;
+  int opt;
+} OPTIONS[] = {
+  { "-v", OPT_VERSION }, { "--version", OPT_VERSION }, { "-h", OPT_HELP }, { "--help", OPT_HELP }, { "-?", OPT_HELP },
+  { "-s", OPT_SEQFILE }, { "--seqfile", OPT_SEQFILE }, { "-l", OPT_LISTFILE }, { "--listfile", OPT_LISTFILE },
+  { "-f", OPT_QUERYFILE }, { "--queryfile", OPT_QUERYFILE }, { "-q", OPT_QUERY }, { "--query", OPT_QUERY },
+  { "-p", OPT_PM }, { "--perfectmatch", OPT_PM }, { "-mm", OPT_MM }, { "--mismatch", OPT_MM },
+  { "-min", OPT_MIN }, { "--minfreq", OPT_MIN }, { "-max", OPT_MAX }, { "--maxfreq", OPT_MAX }, { "-D", OPT_DEBUG },
+  { "--all", OPT_ALL }, { "-all", OPT_ALL }, { "--stats", OPT_STATS }, { "--stat", OPT_STATS }, { "-stat", OPT_STATS },
+  { "--median", OPT_MEDIAN }, { "-median", OPT_MEDIAN }, { "--distribution", OPT_DISTRO }, { "-distribution", OPT_DISTRO },
+  { "-gc", OPT_GC }, { "--gc", OPT_GC }, { "--files", OPT_FILES }, { "--sequences", OPT_SEQUENCES }, { "--locations", OPT_LOCATIONS },
+  { "--3p", OPT_3P }, { "--5p", OPT_5P }, { "--header", OPT_HEADER }, { "--bloom", OPT_BLOOM }, { "--is_union", OPT_IS_UNION },
+  { "--disable_scouts", OPT_NOSCOUTS },
+  { "--words-only", OPT_WORDS_ONLY }, /* not in the reference: print the parsed query words, no device */
+};
+
+static const char *const HELP_LINES[] = {
+  "Usage: glistquery INPUT_LIST [OPTIONS]",
+  "Options:",
+  "    -v, --version             - print version information and exit",
+  "    -h, --help                - print this usage screen and exit",
+  "    -stat, --stats            - print statistics of the list file and exit",
+  "    --median                  - print min/max/median/average and exit",
+  "    --distribution MAX        - print distribution up to MAX",
+  "    --gc                      - print average GC content of all words",
+  "    -q, --query               - single query word",
+  "    -f, --queryfile           - list of query words in a file",
+  "    -s, --seqfile             - FastA/FastQ file",
+  "    -l, --listfile            - list file made by glistmaker",
+  "    -mm, --mismatch NUMBER    - specify number of mismatches (0-16; default 0)",
+  "    -p, --perfectmatch NUMBER - specify number of 3' perfect matches (0-32; default 0)",
+  "    -min, --minfreq NUMBER    - minimum frequency of the printed words (default 0)",
+  "    -max, --maxfreq NUMBER    - maximum frequency of the printed words (default MAX_UINT)",
+  "    --files                   - Print indexed files",
+  "    --sequences               - Print indexed subsequences",
+  "    --bloom                   - use bloom filter to speed up lookups",
+  "    --all                     - in case of mismatches prints all found words",
+  "    --locations               - in case of index print all word locations",
+  "    --3p                      - if query is longer than word use 3' end",
+  "    --5p                      - if query is longer than word use 5' end",
+  "    -D                        - increase debug level",
+};
+
+static int debug = 0;
+static unsigned int use_3p = 0, use_5p = 0;
+static int words_only = 0;
+
+static void print_help (int exit_value)
+{
+  fprintf (stderr, "glistquery version %u.%u.%u (%s)\n", GT4_VERSION_MAJOR, GT4_VERSION_MINOR, GT4_VERSION_MICRO, GT4_VERSION_QUALIFIER);
+  for (size_t i = 0; i < sizeof HELP_LINES / sizeof HELP_LINES[0]; i++) fprintf (stderr, "%s\n", HELP_LINES[i]);
+  exit (exit_value);
+}
+
+static int find_option (const char *arg)
+{
+  for (size_t i = 0; i < sizeof OPTIONS / sizeof OPTIONS[0]; i++)
+    if (!strcmp (arg, OPTIONS[i].name)) return OPTIONS[i].opt;
+  return -1;
+}
+
+/* ------------------------------------------------------------------ words */
+
+/* get_nucl_value, src/sequence.c:43-52: any character maps to two bits */
+static uint64_t nucl_value (char nucl)
+{
+  if (nucl & 4) return (uint64_t) (((nucl >> 4) | 2) & 3);
+  return (uint64_t) ((nucl & 6) >> 1);
+}
+
+/* string_to_word, src/sequence.c:116-130 */
+static uint64_t string_to_word (const char *s, unsigned int wordlength)
+{
+  const unsigned int l = wordlength < 32 ? wordlength : 32;
+  uint64_t word = 0;
+  for (unsigned int i = 0; i < l; i++) {
+    if (strchr ("ACGTUacgtu", s[i]) == NULL) fprintf (stderr, "Invalid character %c in string!\n", s[i]);
+    word = (word << 2) | nucl_value (s[i]);
+  }
+  return word;
+}
+
+static uint64_t reverse_complement (uint64_t w, unsigned int k)
+{
+  uint64_t r = 0;
+  w = ~w;
+  for (unsigned int i = 0; i < k; i++) {
+    r = (r << 2) | (w & 3);
+    w >>= 2;
+  }
+  return r;
+}
+
+static uint64_t canonical_word (uint64_t w, unsigned int k)
+{
+  const uint64_t r = reverse_complement (w, k);
+  return r < w ? r : w;
+}
+
+/* ------------------------------------------------------------------ the lists on the command line */
+
+typedef struct {
+  const char *name;
+  int is_index;
+  GT4ListFile file;
+  uint32_t version_major, version_minor;
+} Input;
+
+static uint64_t input_word (const Input *in, uint64_t i)
+{
+  uint64_t w;
+  memcpy (&w, in->is_index ? in->file.index_kmers + 16 * i : in->file.records + 12 * i, 8);
+  return w;
+}
+
+static uint32_t input_count (const Input *in, uint64_t i)
+{
+  if (!in->is_index) {
+    uint32_t c;
+    memcpy (&c, in->file.records + 12 * i + 8, 4);
+    return c;
+  }
+  uint64_t here, next = in->file.index_locations;
+  memcpy (&here, in->file.index_kmers + 16 * i + 8, 8);
+  if (i + 1 < in->file.header.n_words) memcpy (&next, in->file.index_kmers + 16 * (i + 1) + 8, 8);
+  return (uint32_t) (next - here);
+}
+
+/* 0: mapped; 1: the reference's "invalid" state */
+static int input_open (Input *in, const char *name, uint32_t code)
+{
+  memset (in, 0, sizeof *in);
+  in->name = name;
+  in->is_index = code == GT4_INDEX_CODE_VALUE;
+  if (in->is_index ? gt4_indexfile_open (name, GT4_VERSION_MAJOR, &in->file) : gt4_listfile_open (name, GT4_VERSION_MAJOR, &in->file)) return 1;
+  in->version_major = in->file.header.version_major;
+  in->version_minor = in->file.header.version_minor;
+  if (in->is_index && in->file.file_size >= 12) {
+    memcpy (&in->version_major, in->file.file_map + 4, 4);
+    memcpy (&in->version_minor, in->file.file_map + 8, 4);
+  }
+  return 0;
+}
+
+static void print_list_header (const Input *in)
+{
+  fprintf (stdout, "%s %s: built with glistmaker version %d.%d\n", in->is_index ? "Index" : "List", in->name, (int) in->version_major, (int) in->version_minor);
+  fprintf (stdout, "Wordlength\t%u\n", in->file.header.word_length);
+  fprintf (stdout, "NUnique\t%llu\n", (unsigned long long) in->file.header.n_words);
+  fprintf (stdout, "NTotal\t%llu\n", (unsigned long long) in->file.header.total_count);
+}
+
+/* the list in device memory, or exit 1 */
+static GT4HipWordList *to_device (const char *name, gt4hip_context **ctx, const gt4hip_list **dev)
+{
+  *ctx = gt4_hip_default_context ();
+  if (!*ctx) exit (1);
+  GT4HipWordList *l = gt4_hip_word_list_new (name, GT4_VERSION_MAJOR);
+  if (!l) {
+    fprintf (stderr, "Error: %s could not be loaded into device memory\n", name);
+    exit (1);
+  }
+  if (dev) {
+    *dev = gt4_hip_word_list_device (l);
+    if (!*dev) {
+      fprintf (stderr, "Error: %s does not fit the device memory (out of memory)\n", name);
+      exit (1);
+    }
+  }
+  return l;
+}
+
+#define CHK(ctx, call)                                                            \
+  do {                                                                            \
+    if ((call) != GT4HIP_OK) {                                                    \
+      fprintf (stderr, "Error: %s: %s\n", #call, gt4hip_last_error (ctx));        \
+      exit (1);                                                                   \
+    }                                                                             \
+  } while (0)
+
+/* ------------------------------------------------------------------ statistics */
+
+static void print_median (const Input *in)
+{
+  gt4hip_context *ctx;
+  const gt4hip_list *dev;
+  GT4HipWordList *l = to_device (in->name, &ctx, &dev);
+  const uint64_t num_words = in->file.header.n_words;
+  uint32_t min, max, med, gmin, gmax;
+  if (debug > 0) fprintf (stderr, "Finding min/max...");
+  CHK (ctx, gt4hip_list_count_stats (ctx, dev, &gmin, &gmax));
+  if (debug > 0) fprintf (stderr, "done (%u %u)\n", gmin, gmax);
+  min = gmin;
+  max = gmax;
+  med = (uint32_t) (((uint64_t) min + max) / 2);
+  /* the reference's bisection, step for step (it does not always end on the true median) */
+  while (max > min) {
+    uint64_t above = 0, below = 0, equal;
+    CHK (ctx, gt4hip_list_count_split (ctx, dev, med, &below, &above));
+    equal = num_words - above - below;
+    if (debug > 0) fprintf (stderr, "Trying median %u - equal %llu, below %llu, above %llu\n", med, (unsigned long long) equal, (unsigned long long) below,
+                            (unsigned long long) above);
+    if (max == min + 1) {
+      if (above > below + equal) med = max;
+      break;
+    }
+    if (above > below) {
+      if (above - below < equal) break;
+      min = med;
+    } else if (below > above) {
+      if (below - above < equal) break;
+      max = med;
+    } else {
+      break;
+    }
+    med = (min + max) / 2; /* 32-bit, as the reference */
+  }
+  print_list_header (in);
+  fprintf (stdout, "Min %u Max %u Median %u Average %.2f\n", gmin, gmax, med, (double) in->file.header.total_count / num_words);
+  gt4_hip_word_list_delete (l);
+}
+
+static void print_distro (const Input *in, unsigned int max)
+{
+  gt4hip_context *ctx;
+  const gt4hip_list *dev;
+  GT4HipWordList *l = to_device (in->name, &ctx, &dev);
+  uint64_t *d = (uint64_t *) calloc (max ? max : 1, 8);
+  if (!d) {
+    fprintf (stderr, "Error: out of memory (distribution of %u)\n", max);
+    exit (1);
+  }
+  CHK (ctx, gt4hip_list_count_histogram (ctx, dev, max, d));
+  for (unsigned int i = 0; i < max; i++) fprintf (stdout, "%u\t%llu\n", i + 1, (unsigned long long) d[i]);
+  free (d);
+  gt4_hip_word_list_delete (l);
+}
+
+static void print_gc (const Input *in)
+{
+  gt4hip_context *ctx;
+  const gt4hip_list *dev;
+  GT4HipWordList *l = to_device (in->name, &ctx, &dev);
+  uint64_t count = 0;
+  CHK (ctx, gt4hip_list_gc (ctx, dev, &count));
+  printf ("GC\t%g\n", (double) count / (in->file.header.total_count * in->file.header.word_length));
+  gt4_hip_word_list_delete (l);
+}
+
+static void print_full_map (const Input *in)
+{
+  const unsigned int k = in->file.header.word_length;
+  char b[64];
+  for (uint64_t i = 0; i < in->file.header.n_words; i++) {
+    gt4_word2string (b, input_word (in, i), k);
+    fprintf (stdout, "%s\t%u\n", b, input_count (in, i));
+  }
+}
+
+/* ------------------------------------------------------------------ multi-list forms (include/gt4_set_operations.h) */
+
+static unsigned int g_wlen, g_n_lists;
+
+static unsigned int dump_cb (uint64_t word, uint32_t *counts, void *data)
+{
+  char b[64];
+  (void) data;
+  gt4_word2string (b, word, g_wlen);
+  fputs (b, stdout);
+  for (unsigned int j = 0; j < g_n_lists; j++) fprintf (stdout, "\t%u", counts[j]);
+  fputc ('\n', stdout);
+  return 0;
+}
+
+static uint64_t multi_last;
+static int multi_open;
+
+static unsigned int multi_cb (uint64_t word, unsigned int list, uint32_t count, void *data)
+{
+  (void) data;
+  if (!multi_open || word != multi_last) {
+    char b[64];
+    if (multi_open) fputc ('\n', stdout);
+    gt4_word2string (b, word, g_wlen);
+    fputs (b, stdout);
+    multi_open = 1;
+    multi_last = word;
+  }
+  fprintf (stdout, "\t%u:%u", list, count);
+  return 0;
+}
+
+static unsigned int zipper_cb (uint64_t word, uint32_t count, void *data)
+{
+  char b[64];
+  (void) data;
+  gt4_word2string (b, word, g_wlen);
+  fprintf (stdout, "%s\t%u\n", b, count);
+  return 0;
+}
+
+static GT4HipWordList *word_list_or_die (const char *name)
+{
+  if (!gt4_hip_default_context ()) exit (1);
+  GT4HipWordList *l = gt4_hip_word_list_new (name, GT4_VERSION_MAJOR);
+  if (!l) {
+    fprintf (stderr, "Error: %s could not be loaded into device memory\n", name);
+    exit (1);
+  }
+  return l;
+}
+
+/* ------------------------------------------------------------------ batched lookups */
+
+typedef struct {
+  gt4hip_context *ctx;
+  gt4hip_query_index *qindex;
+  gt4hip_query_params prm;
+  unsigned int k, min_freq, max_freq;
+  int print_all;
+  uint64_t *words; /* canonical query words of the batch */
+  uint64_t n;
+  uint32_t *values;
+  uint8_t *found;
+  gt4hip_query_hit *hits;
+  uint64_t hit_capacity;
+} Searcher;
+
+/* The place of a variant in the pre-order of gt4_word_table_generate_mismatches (src/word-table.c:360-382): the
+ * substitutions (position i ascending, XOR value m) as bytes 4 i + m, compared as strings: a prefix sorts before
+ * its extensions. */
+typedef struct {
+  unsigned char key[36];
+  const gt4hip_query_hit *hit;
+} OrderedHit;
+
+static int ordered_cmp (const void *a, const void *b) { return strcmp ((const char *) ((const OrderedHit *) a)->key, (const char *) ((const OrderedHit *) b)->key); }
+
+static void flush_batch (Searcher *s)
+{
+  char b[64];
+  if (!s->n) return;
+  if (words_only) {
+    for (uint64_t i = 0; i < s->n; i++) fprintf (stdout, "%llu\n", (unsigned long long) s->words[i]);
+    s->n = 0;
+    return;
+  }
+  if (!s->print_all) {
+    CHK (s->ctx, gt4hip_query_lookup (s->ctx, s->qindex, s->words, s->n, &s->prm, s->values, s->found));
+    for (uint64_t i = 0; i < s->n; i++) {
+      if (s->found[i]) {
+        if (s->values[i] < s->min_freq || s->values[i] > s->max_freq) continue;
+        gt4_word2string (b, s->words[i], s->k);
+        fprintf (stdout, "%s\t%u\n", b, s->values[i]);
+      } else if (!s->min_freq) {
+        gt4_word2string (b, s->words[i], s->k);
+        fprintf (stdout, "%s\t0\n", b);
+      }
+    }
+    s->n = 0;
+    return;
+  }
+  uint64_t n_hits = 0;
+  CHK (s->ctx, gt4hip_query_lookup_all (s->ctx, s->qindex, s->words, s->n, &s->prm, s->hits, s->hit_capacity, &n_hits));
+  if (n_hits > s->hit_capacity) {
+    free (s->hits);
+    s->hit_capacity = n_hits;
+    s->hits = (gt4hip_query_hit *) malloc ((size_t) n_hits * sizeof (gt4hip_query_hit));
+    if (!s->hits) {
+      fprintf (stderr, "Error: out of memory (%llu hits)\n", (unsigned long long) n_hits);
+      exit (1);
+    }
+    CHK (s->ctx, gt4hip_query_lookup_all (s->ctx, s->qindex, s->words, s->n, &s->prm, s->hits, s->hit_capacity, &n_hits));
+  }
+  OrderedHit *ord = NULL;
+  size_t ord_cap = 0;
+  uint64_t h = 0;
+  for (uint64_t i = 0; i < s->n; i++) {
+    uint64_t e = h;
+    while (e < n_hits && s->hits[e].query == i) e++;
+    const size_t m = (size_t) (e - h);
+    if (m > ord_cap) {
+      ord_cap = m * 2;
+      ord = (OrderedHit *) realloc (ord, ord_cap * sizeof *ord);
+      if (!ord) {
+        fprintf (stderr, "Error: out of memory (%llu hits of one query)\n", (unsigned long long) m);
+        exit (1);
+      }
+    }
+    uint32_t sum = 0;
+    for (size_t j = 0; j < m; j++) {
+      uint64_t mask = 0;
+      CHK (s->ctx, gt4hip_query_variant_mask (s->k, &s->prm, s->hits[h + j].rank, &mask));
+      unsigned int len = 0;
+      for (unsigned int p = 0; p < s->k; p++) {
+        const unsigned int x = (unsigned int) (mask >> (2 * p)) & 3u;
+        if (x) ord[j].key[len++] = (unsigned char) (4 * p + x);
+      }
+      ord[j].key[len] = 0;
+      ord[j].hit = &s->hits[h + j];
+      sum += s->hits[h + j].count;
+    }
+    if (m > 1) qsort (ord, m, sizeof *ord, ordered_cmp);
+    for (size_t j = 0; j < m; j++) {
+      gt4_word2string (b, ord[j].hit->word, s->k);
+      fprintf (stdout, "%s\t%u\n", b, ord[j].hit->count);
+    }
+    /* the reference's return value: with mismatches the summed count, without them "found" */
+    const int none = s->prm.n_mm ? sum == 0 : m == 0;
+    if (none && !s->min_freq) {
+      gt4_word2string (b, s->words[i], s->k);
+      fprintf (stdout, "%s\t0\n", b);
+    }
+    h = e;
+  }
+  free (ord);
+  s->n = 0;
+}
+
+/* search_one_word: the query is looked up as its canonical form */
+static void search_one_word (Searcher *s, uint64_t word)
+{
+  s->words[s->n++] = words_only ? word : canonical_word (word, s->k);
+  if (s->n == QUERY_BATCH) flush_batch (s);
+}
+
+/* the length rules of search_one_query_string / search_n_query_strings; 0: *word set */
+static int query_string_word (const char *who, const char *c, unsigned int k, uint64_t *word)
+{
+  const unsigned int len = (unsigned int) strlen (c);
+  if (len != k) {
+    if (len < k) {
+      fprintf (stderr, "%s: Word too short (%u < %u)\n", who, k, len);
+      return 1;
+    } else if (use_3p) {
+      *word = string_to_word (c + (len - k), k);
+    } else if (use_5p) {
+      *word = string_to_word (c, k);
+    } else {
+      fprintf (stderr, "%s: Wrong query length (%u != %u) - use --3p or --5p\n", who, k, len);
+      return 1;
+    }
+  } else {
+    *word = string_to_word (c, k);
+  }
+  return 0;
+}
+
+static int search_n_query_strings (Searcher *s, const char *queryfile)
+{
+  FILE *ifs = fopen (queryfile, "r");
+  if (ifs == NULL) {
+    fprintf (stderr, "search_n_query_strings: Cannot open file %s.\n", queryfile);
+    return 1;
+  }
+  int val = fgetc (ifs);
+  while (val > 0) {
+    char c[256];
+    unsigned int i = 0;
+    uint64_t word;
+    while (val > 0 && i < 255 && val != '\n') {
+      c[i++] = (char) val;
+      val = fgetc (ifs);
+    }
+    c[i] = 0;
+    while (val > 0 && val != '\n') val = fgetc (ifs);
+    while (val > 0 && val < 'A') val = fgetc (ifs);
+    if (query_string_word ("search_n_query_strings", c, s->k, &word)) {
+      flush_batch (s); /* what the reference had printed before it stopped */
+      return 1;        /* (the reference leaves the file open too) */
+    }
+    search_one_word (s, word);
+  }
+  fclose (ifs);
+  return 0;
+}
+
+/* The reader of src/fasta.c:87-300 for plain text: forward words only.  Returns what fasta_reader_read_nwords
+ * returns (0, or -1 after its message). */
+static int search_fasta (Searcher *s, const char *fname)
+{
+  enum { ST_NONE, ST_NAME, ST_SEQUENCE, ST_QUALITY } state = ST_NONE;
+  FILE *ifs = fopen (fname, "r");
+  if (!ifs) {
+    fprintf (stderr, "search_fasta: Cannot open %s\n", fname);
+    return 1;
+  }
+  const int c0 = fgetc (ifs), c1 = fgetc (ifs);
+  if (c0 == 0x1f && c1 == 0x8b) {
+    fprintf (stderr, "Error: %s is gzip-compressed: decompress it first (compressed sequence files are not read)\n", fname);
+    fclose (ifs);
+    return 1;
+  }
+  rewind (ifs);
+  const unsigned int k = s->k;
+  const uint64_t mask = k >= 32 ? ~0ull : (1ull << (2 * k)) - 1;
+  int fastq = 0;
+  uint64_t wordfw = 0, cpos = 0;
+  unsigned int currentlength = 0;
+  int result = 0;
+#define READ() ((cval = fgetc (ifs)) < 0 ? (cval = 0) : cval) /* a sequence source returns 0 at the end */
+  for (;;) {
+    int cval;
+    READ ();
+    if (cval == 0) break;
+    switch (state) {
+    case ST_NONE:
+      if (cval == '>') fastq = 0;
+      else if (cval == '@') fastq = 1;
+      else {
+        fprintf (stderr, "fasta_reader_read_nwords: Reader %s invalid start tag '%c'\n", fname, cval);
+        result = -1;
+        goto done;
+      }
+      state = ST_NAME;
+      cpos += 1;
+      break;
+    case ST_NAME:
+      if (cval == '\n') {
+        state = ST_SEQUENCE;
+        wordfw = 0;
+        currentlength = 0;
+      }
+      cpos += 1;
+      break;
+    case ST_SEQUENCE:
+      if (!fastq && cval == '>') {
+        state = ST_NAME;
+      } else if (fastq && cval == '\n') {
+        READ ();
+        if (cval != '+') {
+          fprintf (stderr, "fasta_reader_read_nwords: Reader %s tag '+' missing, found '%c' instead at %llu\n", fname, cval, (unsigned long long) cpos);
+          result = -1;
+          goto done;
+        }
+        cpos += 1;
+        READ ();
+        cpos += 1;
+        while (cval != '\n') {
+          if (cval <= 0) {
+            fprintf (stderr, "fasta_reader_read_nwords: Reader %s invalid character '%c' after '+' %llu\n", fname, cval, (unsigned long long) cpos);
+            result = -1;
+            goto done;
+          }
+          READ ();
+          cpos += 1;
+        }
+        state = ST_QUALITY;
+      } else {
+        unsigned int nuclval = 4;
+        switch (cval) {
+        case 'A': case 'a': nuclval = 0; break;
+        case 'C': case 'c': nuclval = 1; break;
+        case 'G': case 'g': nuclval = 2; break;
+        case 'T': case 't': case 'U': case 'u': nuclval = 3; break;
+        }
+        if (nuclval <= 3) {
+          wordfw = (wordfw << 2) | nuclval;
+          currentlength += 1;
+          if (currentlength > k) {
+            wordfw &= mask;
+            currentlength = k;
+          }
+          if (currentlength == k) search_one_word (s, wordfw);
+        } else if (cval >= ' ') {
+          wordfw = 0;
+          currentlength = 0;
+        }
+      }
+      cpos += 1;
+      break;
+    case ST_QUALITY:
+      if (cval == '\n') {
+        READ ();
+        if (cval == 0) goto done;
+        if (cval != '@') {
+          fprintf (stderr, "fasta_reader_read_nwords: Reader %s tag '@' missing, found '%c' instead at %llu\n", fname, cval, (unsigned long long) cpos);
+          result = -1;
+          goto done;
+        }
+        cpos += 1;
+        state = ST_NAME;
+      }
+      cpos += 1;
+      break;
+    }
+  }
+#undef READ
+done:
+  fclose (ifs);
+  return result;
+}
+
+/* ------------------------------------------------------------------ main */
+
+int main (int argc, const char *argv[])
+{
+  int argidx, v = 0;
+  unsigned int n_lists = 0, invalid = 0;
+  const char *lists[MAX_LISTS];
+  const char *querystring = NULL, *queryfilename = NULL, *seqfilename = NULL, *querylistfilename = NULL;
+  unsigned int nmm = 0, pm3 = 0;
+  char *end;
+  int printall = 0, print_header = 0, locations = 0;
+  unsigned int minfreq = 0, maxfreq = UINT_MAX, distro = 0, command = CMD_QUERY, is_union = 0;
+
+  for (argidx = 1; argidx < argc; argidx++) {
+    const char *arg = argv[argidx];
+    const int opt = find_option (arg);
+    switch (opt) {
+    case OPT_VERSION:
+      fprintf (stdout, "glistquery version %u.%u.%u (%s)\n", GT4_VERSION_MAJOR, GT4_VERSION_MINOR, GT4_VERSION_MICRO, GT4_VERSION_QUALIFIER);
+      return 0;
+    case OPT_HELP: print_help (0); break;
+    case OPT_SEQFILE:
+    case OPT_LISTFILE:
+    case OPT_QUERYFILE:
+    case OPT_QUERY:
+      if (!argv[argidx + 1] || argv[argidx + 1][0] == '-') {
+        fprintf (stderr, "Warning: No %s specified!\n", opt == OPT_SEQFILE ? "sequence file name" : opt == OPT_LISTFILE ? "query list file name"
+                                                        : opt == OPT_QUERYFILE ? "query file name" : "query");
+        argidx += 1;
+        continue;
+      }
+      if (opt == OPT_SEQFILE) seqfilename = argv[argidx + 1];
+      else if (opt == OPT_LISTFILE) querylistfilename = argv[argidx + 1];
+      else if (opt == OPT_QUERYFILE) queryfilename = argv[argidx + 1];
+      else querystring = argv[argidx + 1];
+      argidx += 1;
+      break;
+    case OPT_PM:
+    case OPT_MM: {
+      argidx += 1;
+      if (argidx >= argc) print_help (1);
+      const unsigned int val = (unsigned int) strtol (argv[argidx], &end, 10);
+      if (*end || val > (opt == OPT_PM ? 32u : 16u)) print_help (1);
+      if (opt == OPT_PM) pm3 = val;
+      else nmm = val;
+      break;
+    }
+    case OPT_MIN:
+      if (!argv[argidx + 1]) {
+        fprintf (stderr, "Warning: No minimum frequency specified! Using the default value: %d.\n", minfreq);
+        argidx += 1;
+        continue;
+      }
+      minfreq = (unsigned int) strtol (argv[argidx + 1], &end, 10);
+      if (*end != 0) {
+        fprintf (stderr, "Error: Invalid minimum frequency: %s! Must be a positive integer.\n", argv[argidx + 1]);
+        print_help (1);
+      }
+      argidx += 1;
+      break;
+    case OPT_MAX:
+      if (!argv[argidx + 1]) {
+        fprintf (stderr, "Warning: No maximum frequency specified! Using the default value: %d.\n", maxfreq);
+        argidx += 1;
+        continue;
+      }
+      maxfreq = (unsigned int) strtol (argv[argidx + 1], &end, 10);
+      if (*end != 0) {
+        fprintf (stderr, "Error: Invalid maximum frequency: %s! Must be a positive integer.\n", argv[argidx + 1]);
+        print_help (1);
+      }
+      argidx += 1;
+      break;
+    case OPT_DEBUG: debug += 1; break;
+    case OPT_ALL: printall = 1; break;
+    case OPT_STATS: command = CMD_STATS; break;
+    case OPT_MEDIAN: command = CMD_MEDIAN; break;
+    case OPT_DISTRO:
+      if (argidx + 1 >= argc) print_help (1);
+      argidx += 1;
+      distro = (unsigned int) strtol (argv[argidx], &end, 10);
+      command = CMD_DISTRO;
+      break;
+    case OPT_GC: command = CMD_GC; break;
+    case OPT_FILES: command = CMD_FILES; break;
+    case OPT_SEQUENCES: command = CMD_SEQUENCES; break;
+    case OPT_LOCATIONS: locations = 1; break;
+    case OPT_3P: use_3p = 1; break;
+    case OPT_5P: use_5p = 1; break;
+    case OPT_HEADER: print_header = 1; break;
+    case OPT_BLOOM: break;    /* accepted and ignored */
+    case OPT_NOSCOUTS: break; /* accepted and ignored */
+    case OPT_IS_UNION: is_union = 1; break;
+    case OPT_WORDS_ONLY: words_only = 1; break;
+    default:
+      if (arg[0] != '-') {
+        if (n_lists == MAX_LISTS) {
+          fprintf (stderr, "Error: more than %d lists\n", MAX_LISTS);
+          exit (1);
+        }
+        lists[n_lists++] = arg;
+      } else {
+        fprintf (stderr, "Error: Unknown argument: %s!\n", arg);
+        print_help (1);
+      }
+    }
+  }
+
+  if (!n_lists) {
+    fprintf (stderr, "No list/index files specified!\n");
+    print_help (1);
+  }
+  if (locations || command == CMD_FILES || command == CMD_SEQUENCES) {
+    fprintf (stderr, "Error: %s is not supported: the location tables of an index are not loaded\n",
+             command == CMD_FILES ? "--files" : command == CMD_SEQUENCES ? "--sequences" : "--locations");
+    exit (1);
+  }
+
+  /* Map every list / index (headers only so far) and test some errors */
+  static Input maps[MAX_LISTS];
+  unsigned int wlen = 0;
+  for (unsigned int i = 0; i < n_lists; i++) {
+    uint32_t code = 0;
+    int ok = 0;
+    FILE *ifs = fopen (lists[i], "r");
+    if (!ifs) {
+      fprintf (stderr, "Cannot open list %s\n", lists[i]);
+      exit (1);
+    }
+    if (fread (&code, 4, 1, ifs) != 1) code = 0;
+    fclose (ifs);
+    if (code == GT4_LIST_CODE_VALUE || code == GT4_INDEX_CODE_VALUE) {
+      ok = !input_open (&maps[i], lists[i], code);
+      if (ok && debug && code == GT4_LIST_CODE_VALUE) fprintf (stderr, "List %s loaded\n", lists[i]);
+    } else {
+      fprintf (stderr, "Error: %s is not a valid GenomeTester4 list/index file\n", lists[i]);
+      invalid = 1;
+    }
+    if (!ok) {
+      fprintf (stderr, "Error: %s is invalid or corrupted\n", lists[i]);
+      invalid = 1;
+    } else if (!wlen) {
+      wlen = maps[i].file.header.word_length;
+    } else if (maps[i].file.header.word_length != wlen) {
+      fprintf (stderr, "Error: %s has different word length %u (first list had %u)\n", lists[i], maps[i].file.header.word_length, wlen);
+      invalid = 1;
+    }
+  }
+  static Input query_input;
+  if (querylistfilename) {
+    uint32_t code = 0;
+    if (gt4_listfile_sniff (querylistfilename, &code) || (code != GT4_LIST_CODE_VALUE && code != GT4_INDEX_CODE_VALUE) ||
+        input_open (&query_input, querylistfilename, code)) {
+      fprintf (stderr, "Error: %s is invalid or corrupted\n", querylistfilename);
+      invalid = 1;
+    } else if (query_input.file.header.word_length != wlen) {
+      fprintf (stderr, "Error: %s has different word length %u (first list had %u)\n", querylistfilename, query_input.file.header.word_length, wlen);
+      invalid = 1;
+    }
+  }
+  if (invalid) exit (1);
+
+  /* Generic methods */
+  if (command == CMD_STATS) {
+    for (unsigned int i = 0; i < n_lists; i++) print_list_header (&maps[i]);
+    exit (0);
+  } else if (command == CMD_MEDIAN) {
+    for (unsigned int i = 0; i < n_lists; i++) print_median (&maps[i]);
+    exit (0);
+  } else if (command == CMD_DISTRO) {
+    for (unsigned int i = 0; i < n_lists; i++) print_distro (&maps[i], distro + 1);
+    exit (0);
+  } else if (command == CMD_GC) {
+    for (unsigned int i = 0; i < n_lists; i++) print_gc (&maps[i]);
+    exit (0);
+  }
+
+  g_wlen = wlen;
+  g_n_lists = n_lists;
+
+  /* If no options is given print all lists/indices */
+  if (!seqfilename && !querylistfilename && !queryfilename && !querystring) {
+    if (n_lists > 1) {
+      if (print_header) {
+        fprintf (stdout, "KMER");
+        for (unsigned int i = 0; i < n_lists; i++) fprintf (stdout, "\t%s", lists[i]);
+        fprintf (stdout, "\n");
+      }
+      static GT4HipWordList *objs[MAX_LISTS];
+      for (unsigned int i = 0; i < n_lists; i++) objs[i] = word_list_or_die (lists[i]);
+      const unsigned int r = is_union ? gt4_is_union (objs, n_lists, dump_cb, NULL) : gt4_union (objs, n_lists, dump_cb, NULL);
+      if (r) {
+        fprintf (stderr, "Error: the union of the lists failed (%u)\n", r);
+        exit (1);
+      }
+    } else {
+      print_full_map (&maps[0]);
+    }
+    exit (0);
+  }
+
+  /* Search one list against multiple */
+  if (querylistfilename && n_lists > 1) {
+    if (nmm || pm3) {
+      fprintf (stderr, "Error: Searching multiple lists is incompatible with mismatches\n");
+      exit (1);
+    }
+    static GT4HipWordList *objs[MAX_LISTS];
+    GT4HipWordList *q = word_list_or_die (querylistfilename);
+    for (unsigned int i = 0; i < n_lists; i++) objs[i] = word_list_or_die (lists[i]);
+    const unsigned int result = gt4_search_lists_multi (q, objs, n_lists, multi_cb, NULL);
+    if (multi_open) fputc ('\n', stdout);
+    exit ((int) result);
+  }
+
+  if (n_lists > 1) {
+    fprintf (stderr, "Error: Query is incompatible with multiple lists/indices\n");
+    exit (1);
+  }
+  if (nmm + pm3 > wlen) {
+    fprintf (stderr, "Error: Number of mismatches (%u) and 3' perfect match (%u) are longer than word length %u\n", nmm, pm3, wlen);
+    return 1;
+  }
+
+  /* one list against a query list without mismatches: the zipper (min / max / --all do not apply, as in the reference) */
+  if (!querystring && !queryfilename && !seqfilename && querylistfilename && !nmm && !words_only) {
+    GT4HipWordList *l = word_list_or_die (lists[0]);
+    GT4HipWordList *q = word_list_or_die (querylistfilename);
+    const unsigned int r = gt4_search_list_zipper (l, q, zipper_cb, NULL);
+    if (r) {
+      fprintf (stderr, "Error: the search of %s in %s failed (%u)\n", querylistfilename, lists[0], r);
+      exit (1);
+    }
+    exit (0);
+  }
+
+  Searcher s;
+  memset (&s, 0, sizeof s);
+  s.k = wlen;
+  s.prm.n_mm = nmm;
+  s.prm.pm_3 = pm3;
+  s.prm.canonize = 1;
+  s.min_freq = minfreq;
+  s.max_freq = maxfreq;
+  s.print_all = printall;
+  s.words = (uint64_t *) malloc ((size_t) QUERY_BATCH * 8);
+  s.values = (uint32_t *) malloc ((size_t) QUERY_BATCH * 4);
+  s.found = (uint8_t *) malloc (QUERY_BATCH);
+  s.hit_capacity = printall ? QUERY_BATCH : 0;
+  s.hits = printall ? (gt4hip_query_hit *) malloc ((size_t) s.hit_capacity * sizeof (gt4hip_query_hit)) : NULL;
+  if (!s.words || !s.values || !s.found || (printall && !s.hits)) {
+    fprintf (stderr, "Error: out of memory (query batch)\n");
+    exit (1);
+  }
+  GT4HipWordList *l = NULL;
+  if (!words_only) {
+    const gt4hip_list *dev = NULL;
+    l = to_device (lists[0], &s.ctx, &dev);
+    CHK (s.ctx, gt4hip_query_index_create (s.ctx, dev, &s.qindex));
+  }
+
+  if (querystring) {
+    uint64_t word;
+    v = query_string_word ("search_one_query_string", querystring, wlen, &word);
+    if (!v) search_one_word (&s, word);
+  } else if (queryfilename) {
+    v = search_n_query_strings (&s, queryfilename);
+  } else if (seqfilename) {
+    v = search_fasta (&s, seqfilename);
+  } else if (querylistfilename) {
+    for (uint64_t i = 0; i < query_input.file.header.n_words; i++) search_one_word (&s, input_word (&query_input, i));
+  }
+  flush_batch (&s);
+  fflush (stdout);
+  if (s.qindex) gt4hip_query_index_free (s.qindex);
+  if (l) gt4_hip_word_list_delete (l);
+  if (v) return v;
+  exit (0);
+}

@@ -21,81 +21,13 @@
 #define GT4_RESOLVE_LOOKBACK 0 /* (no chained scan of tile totals here) */
 #include "gt4hip_device.h"
 #include "gt4hip_host.h"
+#include "gt4hip_index.h"
 
 #include <string.h>
 
 namespace gt4 {
 namespace {
 
-constexpr int MM_THREADS = 256;
-constexpr int MM_ROUNDS = 8;                        /* compaction: items per thread and tile */
-constexpr u64 MM_TILE = (u64) MM_THREADS * MM_ROUNDS; /* items per compaction tile */
-constexpr u32 MM_MAX_INDEX_BITS = 22;               /* 32 MiB of offsets at most: well inside the Infinity Cache */
-
-/* C(n, r) for n, r <= 32 */
-struct Binomials {
-  u64 v[33][33];
-  constexpr Binomials () : v ()
-  {
-    for (int n = 0; n <= 32; n++) {
-      v[n][0] = 1;
-      for (int r = 1; r <= n; r++) v[n][r] = v[n - 1][r - 1] + (r <= n - 1 ? v[n - 1][r] : 0);
-    }
-  }
-};
-constexpr Binomials BINOM_HOST;
-__constant__ Binomials c_binom = Binomials ();
-
-/* A list and its bucket index.  n == 0 (an empty list, or no list at all) holds nothing. */
-struct Index {
-  const u32 *rec;
-  u64 n;
-  const u64 *off; /* nb + 1 entries */
-  u64 nb;         /* buckets, 2^b */
-  u32 shift;      /* prefix = key >> shift, clamped to nb - 1 */
-};
-
-__device__ __forceinline__ u64 bucket_of (u64 key, u32 shift, u64 nb)
-{
-  const u64 p = key >> shift;
-  return p < nb ? p : nb - 1;
-}
-
-/* record index of `key` in the list, or ~0 */
-__device__ __forceinline__ u64 find (const Index &ix, u64 key)
-{
-  if (ix.n == 0) return ~0ull;
-  const u64 p = bucket_of (key, ix.shift, ix.nb);
-  u64 lo = ix.off[p], hi = ix.off[p + 1];
-  if (hi > ix.n) hi = ix.n; /* keys out of order leave the index meaningless, never out of bounds */
-  while (lo < hi) {
-    const u64 mid = (lo + hi) >> 1;
-    const u64 k = load_key (ix.rec, mid);
-    if (k < key) lo = mid + 1;
-    else if (k > key) hi = mid;
-    else return mid;
-  }
-  return ~0ull;
-}
-
-/* get_reverse_complement (reference src/sequence.c:65-79) by bit reversal: complement, swap the two bits of
- * every base so that the reversal keeps them in order, reverse, drop the 64 - 2k bits that came from above the word */
-__device__ __forceinline__ u64 revcomp (u64 w, u32 k)
-{
-  u64 x = ~w;
-  x = ((x >> 1) & 0x5555555555555555ull) | ((x & 0x5555555555555555ull) << 1);
-  return __builtin_bitreverse64 (x) >> (64u - 2u * k);
-}
-
-/* offsets[s] for s in (prefix (i - 1), prefix (i)] is i; the slots after the last record's prefix are n */
-__global__ __launch_bounds__ (MM_THREADS) void k_index_build (const u32 *rec, u64 n, u32 shift, u64 nb, u64 *off)
-{
-  for (u64 i = (u64) blockIdx.x * MM_THREADS + threadIdx.x; i <= n; i += (u64) gridDim.x * MM_THREADS) {
-    const u64 first = i ? bucket_of (load_key (rec, i - 1), shift, nb) + 1 : 0;
-    const u64 last = i < n ? bucket_of (load_key (rec, i), shift, nb) : nb;
-    for (u64 s = first; s <= last; s++) off[s] = i;
-  }
-}
 
 /* The merge of compare_wordmaps_mm (:1005-1052) per record of x (side 0: x = list 1, the other = list 2, table
  * diff1; side 1: x = list 2, the other = list 1, table diff2): keep[i] and the table count val[i]. */
@@ -129,53 +61,7 @@ __global__ __launch_bounds__ (MM_THREADS) void k_prepass (const u32 *x, u64 nx, 
   }
 }
 
-/* ------------------------------------------------------------------ stable compaction */
-
-/* Tile t covers items [t * MM_TILE, (t + 1) * MM_TILE); round r of it items t * MM_TILE + r * MM_THREADS + thread. */
-__global__ __launch_bounds__ (MM_THREADS) void k_tile_count (const u32 *keep, u64 n, u64 n_tiles, u32 *tile_cnt)
-{
-  __shared__ u32 part[MM_THREADS / WAVE];
-  for (u64 t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-    u32 c = 0;
-    for (int r = 0; r < MM_ROUNDS; r++) {
-      const u64 i = t * MM_TILE + (u64) r * MM_THREADS + threadIdx.x;
-      c += i < n && keep[i];
-    }
-    c = dpp_wave_sum_u32 (c);
-    if ((threadIdx.x & (WAVE - 1)) == 0) part[threadIdx.x / WAVE] = c;
-    __syncthreads ();
-    if (threadIdx.x == 0) {
-      u32 s = 0;
-      for (int w = 0; w < MM_THREADS / WAVE; w++) s += part[w];
-      tile_cnt[t] = s;
-    }
-    __syncthreads ();
-  }
-}
-
-/* exclusive scan of the tile counts (one workgroup), total in *total */
-__global__ __launch_bounds__ (1024) void k_tile_scan (const u32 *tile_cnt, u64 n_tiles, u64 *tile_off, unsigned long long *total)
-{
-  __shared__ u64 wsum[1024 / WAVE];
-  __shared__ u64 carry;
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads ();
-  for (u64 base = 0; base < n_tiles; base += 1024) {
-    const u64 i = base + threadIdx.x;
-    const u64 v = i < n_tiles ? tile_cnt[i] : 0;
-    const u64 incl = wave_inclusive_scan (v, lane);
-    if (lane == WAVE - 1) wsum[wv] = incl;
-    __syncthreads ();
-    u64 before = carry;
-    for (int w = 0; w < wv; w++) before += wsum[w];
-    if (i < n_tiles) tile_off[i] = before + incl - v;
-    __syncthreads ();
-    if (threadIdx.x == 1023) carry = before + incl;
-    __syncthreads ();
-  }
-  if (threadIdx.x == 0) *total = carry;
-}
+/* (k_tile_count and k_tile_scan: gt4hip_index.h) */
 
 /* Kept items to their place: source keys from packed records (SRC_REC) or a key array, counts from `cnt`;
  * destination packed records (DST_REC; null: count only) or key + count arrays.  *sum += counts kept. */
@@ -246,33 +132,6 @@ struct Level {
   u32 *drop;     /* per word, subtract: a variant is in m and not in q */
 };
 
-/* Variant `r` of the c-substitution variants of a k-base word: r = combination * 3^c + substitutions, the
- * combination (positions p_c > .. > p_1) unranked in the combinatorial number system, the substitutions as base-3
- * digits (XOR masks 1, 2, 3 at bits 2p, gt4_word_table_generate_mismatches, src/word-table.c:361). */
-template <bool WIDE>
-__device__ __forceinline__ u64 variant_mask (u64 r, u64 pow3, u32 k, u32 c)
-{
-  u64 comb, sub;
-  if (WIDE) {
-    comb = r / pow3;
-    sub = r - comb * pow3;
-  } else {
-    const u32 q = (u32) r / (u32) pow3;
-    comb = q;
-    sub = (u32) r - q * (u32) pow3;
-  }
-  u64 mask = 0;
-  u32 x = k;
-  for (u32 j = c; j >= 1; j--) {
-    x--;
-    while (c_binom.v[x][j] > comb) x--;
-    comb -= c_binom.v[x][j];
-    const u32 d = (u32) (sub % 3u) + 1u;
-    sub /= 3u;
-    mask |= (u64) d << (2u * x);
-  }
-  return mask;
-}
 
 template <bool WIDE>
 __global__ __launch_bounds__ (MM_THREADS) void k_level (Level L, unsigned long long *probes)
@@ -345,50 +204,6 @@ using namespace gt4;
 
 namespace {
 
-struct Blocks {
-  std::vector<void *> owners;
-  ~Blocks ()
-  {
-    for (void *o : owners) gt4hip_block_free (o);
-  }
-  int get (gt4hip_context *ctx, size_t bytes, void **p)
-  {
-    void *owner = NULL;
-    const int rc = gt4hip_block_alloc (ctx, bytes ? bytes : 16, p, &owner);
-    if (rc) return rc;
-    owners.push_back (owner);
-    return GT4HIP_OK;
-  }
-};
-
-int grid_for (gt4hip_context *ctx, u64 items, u64 per_block)
-{
-  const u64 want = (items + per_block - 1) / per_block;
-  const u64 cap = (u64) (ctx->n_cus > 0 ? ctx->n_cus : 256) * 8;
-  return (int) (want < 1 ? 1 : want < cap ? want : cap);
-}
-
-int build_index (gt4hip_context *ctx, Blocks &blk, const gt4hip_list *l, Index *ix)
-{
-  const u32 k = l->word_length;
-  u32 b = 0;
-  for (u64 n = l->n_words; n > 1; n >>= 1) b++; /* floor (log2 n) */
-  b = b > 3 ? b - 3 : 1;
-  if (b > MM_MAX_INDEX_BITS) b = MM_MAX_INDEX_BITS;
-  if (b > 2 * k) b = 2 * k;
-  ix->rec = (const u32 *) l->dev;
-  ix->n = l->n_words;
-  ix->nb = 1ull << b;
-  ix->shift = 2 * k - b;
-  void *off = NULL;
-  int rc = blk.get (ctx, (ix->nb + 1) * 8, &off);
-  if (rc) return rc;
-  ix->off = (const u64 *) off;
-  hipLaunchKernelGGL (k_index_build, dim3 (grid_for (ctx, ix->n + 1, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, ix->rec, ix->n, ix->shift, ix->nb,
-                      (u64 *) off);
-  HIPCHK (ctx, hipGetLastError ());
-  return GT4HIP_OK;
-}
 
 /* Stable compaction of the n items with keep[i] != 0; returns the count in *kept (synchronises).  Scratch:
  * tile_cnt (u32) and tile_off (u64) with room for n / MM_TILE + 1 tiles. */

@@ -218,6 +218,64 @@ int gt4hip_compare_mismatch (gt4hip_context *ctx, const gt4hip_list *a, const gt
 /* The measurements of the context's last successful gt4hip_compare_mismatch. */
 int gt4hip_mismatch_stats_get (gt4hip_context *ctx, gt4hip_mismatch_stats *stats);
 
+/* ---------------------------------------------------------------- (ii c) glistquery: lookups and list statistics */
+
+/* The bucket index of a resident list (windows of ~8 records, at most 32 MiB), built once and used by every batch.
+ * The index reads the list's records: keep the list alive and unchanged until gt4hip_query_index_free. */
+typedef struct gt4hip_query_index gt4hip_query_index;
+int gt4hip_query_index_create (gt4hip_context *ctx, const gt4hip_list *list, gt4hip_query_index **qindex);
+void gt4hip_query_index_free (gt4hip_query_index *qindex);
+/* Device time (HIP events) of the kernels of the last lookup call on this index, copies excluded. */
+double gt4hip_query_index_last_ms (const gt4hip_query_index *qindex);
+
+/* Arguments of gt4_word_dict_lookup_mm (src/word-dict.c:74-106) as search_one_word passes them. */
+typedef struct {
+  uint32_t n_mm;      /* -mm: substitutions allowed, 0..32; n_mm + pm_3 <= word length when n_mm > 0     */
+  uint32_t pm_3;      /* -p: base positions 0..pm_3 - 1 (bits 2i, 2i + 1: the LAST bases) never change;
+                         ignored when n_mm == 0                                                        */
+  int32_t canonize;   /* non-zero (the reference's only mode): the query and every variant are replaced
+                         by min (w, reverse complement); 0: words are looked up as they are            */
+} gt4hip_query_params;
+
+/* Variants per query, V = sum over c = 0..n_mm of C(k - pm_3, c) 3^c; GT4HIP_EINVAL when it does not fit 64 bits. */
+int gt4hip_query_variants (uint32_t word_length, const gt4hip_query_params *params, uint64_t *n_variants);
+/* The XOR mask of variant `rank` (0 <= rank < V): rank 0 is the word itself, then every variant with one
+ * substitution, with two, ...  A substitution at base position i with m in 1..3 is m << 2i. */
+int gt4hip_query_variant_mask (uint32_t word_length, const gt4hip_query_params *params, uint64_t rank, uint64_t *mask);
+
+/* `words`: n_queries packed k-mers in HOST memory; `values` (u32) and `found` (one byte) per query, HOST memory too:
+ * the call copies in, runs on the context's stream, copies out and returns when the results are there.
+ * n_mm == 0: found = the (canonical) word is in the list, value = its count (a stored count of 0 is still found).
+ * n_mm > 0: value = sum of the counts of all V variants found, each canonicalised before it is looked up, in uint32_t
+ * arithmetic that wraps; two variants with the same canonical word count twice; found = value != 0.
+ * n_queries x V must fit 64 bits (GT4HIP_EINVAL with a message otherwise). */
+int gt4hip_query_lookup (gt4hip_context *ctx, gt4hip_query_index *qindex, const uint64_t *words, uint64_t n_queries,
+                         const gt4hip_query_params *params, uint32_t *values, uint8_t *found);
+
+typedef struct {
+  uint64_t query;     /* number of the query in the batch                  */
+  uint64_t rank;      /* the variant (gt4hip_query_variant_mask)           */
+  uint64_t word;      /* the word that was found: the canonical variant    */
+  uint32_t count;     /* its stored count (may be 0)                       */
+  uint32_t reserved;
+} gt4hip_query_hit;
+
+/* The --all form: every variant that is in the list, in (query, rank) order.  Two passes on the device (count, then
+ * fill): *n_hits is always the number of hits; `hits` (HOST memory, room for `capacity`) is filled only when
+ * *n_hits <= capacity -- call with capacity 0 to size a buffer, or with a guess and again when *n_hits exceeds it. */
+int gt4hip_query_lookup_all (gt4hip_context *ctx, gt4hip_query_index *qindex, const uint64_t *words, uint64_t n_queries,
+                             const gt4hip_query_params *params, gt4hip_query_hit *hits, uint64_t capacity, uint64_t *n_hits);
+
+/* One streaming pass over the records each (glistquery --median, --distribution, --gc; src/glistquery.c:831-932).
+ * Smallest and largest count (0xffffffff and 0 for an empty list). */
+int gt4hip_list_count_stats (gt4hip_context *ctx, const gt4hip_list *list, uint32_t *min, uint32_t *max);
+/* Records with count < med and with count > med: one step of print_median's bisection. */
+int gt4hip_list_count_split (gt4hip_context *ctx, const gt4hip_list *list, uint32_t med, uint64_t *below, uint64_t *above);
+/* hist[c - 1] = records with count c, for 1 <= c <= max (`max` entries of host memory; counts of 0 are skipped). */
+int gt4hip_list_count_histogram (gt4hip_context *ctx, const gt4hip_list *list, uint32_t max, uint64_t *hist);
+/* Sum over the records of count x (G and C bases of the word). */
+int gt4hip_list_gc (gt4hip_context *ctx, const gt4hip_list *list, uint64_t *weighted_gc_bases);
+
 /* ---------------------------------------------------------------- (iii) N-way operations */
 
 typedef struct {
