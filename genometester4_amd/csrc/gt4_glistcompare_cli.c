@@ -17,15 +17,20 @@
  *     per-probe traces of -D -D and more;
  *   - --stream and --disable_scouts are accepted and ignored (the whole list is uploaded to HBM;
  *     results are identical for well-formed files);
- *   - GT4HIP_VERBOSE=1 prints the device, kernel times and the chunk plan on stderr (-D prints exactly
- *     what the reference prints);
- *   - GT4HIP_CHECK_SORTED=1 rejects an input that is not strictly ascending (the reference trusts it);
- *   - --gpus N / GT4HIP_GPUS=N shards the job by key range over N GPUs (one worker process each, forked
- *     before any HIP call; every worker writes its own extents of the output files, or with
- *     GT4HIP_GATHER=rccl the shards are gathered on worker 0 over RCCL); GT4HIP_HBM_LIMIT=<bytes>, or
- *     inputs that do not fit the device memory, stream the job through the GPU in key-range chunks
- *     (gt4_shard.c).  Outputs are byte-identical to the single-pass run;
+ *   - --gpus N shards the job by key range over N GPUs (one worker process each, forked before any HIP
+ *     call; every worker writes its own extents of the output files).  Inputs of 4 GiB and more, or that
+ *     do not fit the device memory, stream through the GPU in key-range chunks.  Outputs are
+ *     byte-identical to the single-pass run;
  *   - without a usable GPU the program fails: there is no CPU fallback.
+ * Environment, all of it read in read_environment():
+ *   GT4HIP_GPUS=N            as --gpus N (which overrides it);
+ *   GT4HIP_HBM_LIMIT=<bytes> ([K|M|G]) device bytes a worker holds in flight: key-range chunks (gt4_shard.c);
+ *   GT4HIP_PIPELINE=0        inputs of 4 GiB and more stay in one piece as long as they fit the device;
+ *   GT4HIP_GATHER=rccl       the shards of several GPUs are gathered on worker 0 over RCCL;
+ *   GT4HIP_CHECK_SORTED=1    rejects an input that is not strictly ascending (the reference trusts it);
+ *   GT4HIP_DEVICE=N          the device of a one-GPU run (default 0);
+ *   GT4HIP_VERBOSE=1         prints the device, kernel times and the chunk plan on stderr (-D prints exactly
+ *                            what the reference prints).
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -172,177 +177,59 @@ static uint64_t parse_bytes (const char *s)
   return v > 0 ? (uint64_t) v : 0;
 }
 
-/* compare_wordmaps_mm (reference :958-1093): two lists, diff1 and / or diff2 up to nmm mismatches */
-static int mismatch_main (GT4ListFile *files, unsigned int wlen, int find_diff, int find_ddiff, int subtraction, int countonly,
-                          const char *outputname, unsigned int cutoff, unsigned int nmm, int debug, int verbose, int n_gpus, uint64_t hbm_limit,
-                          const char *const *fnames)
+/* What argv and the environment decide.  read_environment and parse_argv fill it, validate settles
+ * find_diff; the run_* stages only read it. */
+typedef struct {
+  const char *fnames[MAX_FILES];
+  unsigned int nfiles;
+  int rule;
+  unsigned int cutoff, nmm, count_override;
+  int find_union, find_intrsec, find_diff, find_ddiff, find_subset, subtraction, countonly, print_operation, debug;
+  const char *outputname;
+  /* environment */
+  int n_gpus;         /* GT4HIP_GPUS, or --gpus N */
+  int verbose;        /* lines of this implementation's own (device, kernel times, chunk plan): -D stays the reference's transcript */
+  uint64_t hbm_limit; /* bytes; 0: none given */
+  int pipeline_off, gather_rccl, check_sorted;
+  int device;
+} Options;
+
+/* every environment variable of the program, once */
+static void read_environment (Options *o)
 {
-  if (debug) {
-    fprintf (stderr, "compare_wordmaps: List 1: %llu entries\n", (unsigned long long) files[0].header.n_words);
-    fprintf (stderr, "compare_wordmaps; List 2: %llu entries\n", (unsigned long long) files[1].header.n_words);
-    fprintf (stderr, "Table 1: %llu entries\n", (unsigned long long) files[0].header.n_words);
-    fprintf (stderr, "Table 2: %llu entries\n", (unsigned long long) files[1].header.n_words);
-  }
-  /* without -d / -dd / -du the reference takes this path all the same and writes nothing */
-  if (!find_diff) {
-    for (unsigned int f = 0; f < 2; f++) gt4_listfile_close (&files[f]);
-    return 0;
-  }
-  if (n_gpus > 1 || hbm_limit) {
-    fprintf (stderr, "Error: -mm needs both lists resident on one GPU: it cannot be combined with %s\n",
-             n_gpus > 1 ? "--gpus N > 1 (GT4HIP_GPUS)" : "GT4HIP_HBM_LIMIT");
-    return 1;
-  }
-  if (!gt4hip_compare_mismatch || !gt4hip_mismatch_stats_get) {
-    fprintf (stderr, "Error: this build has no -mm (mismatch difference) path\n");
-    return 1;
-  }
-  gt4hip_context *ctx = NULL;
-  const char *dev = getenv ("GT4HIP_DEVICE");
-  if (gt4hip_create (dev ? atoi (dev) : 0, &ctx)) {
-    fprintf (stderr, "Error: %s\n", gt4hip_last_error (NULL));
-    return 1;
-  }
-  if (verbose) fprintf (stderr, "Device: %s\n", gt4hip_device_info (ctx));
-  /* inputs, outputs and the lookup tables (~48 bytes per record of each side) must fit: there is no chunked -mm */
-  uint64_t free_b = 0, total_b = 0;
-  gt4hip_device_memory (ctx, &free_b, &total_b);
-  const uint64_t na = files[0].header.n_words, nb = files[1].header.n_words;
-  const uint64_t need = 12 * (na + nb) + 60 * na + (find_ddiff ? 60 * nb : 0);
-  if (free_b && need > free_b / 100 * 90) {
-    fprintf (stderr, "Error: %s: -mm needs about %llu bytes of device memory, %llu are free (both lists stay resident on one GPU)\n",
-             gt4hip_strerror (GT4HIP_ENOMEM), (unsigned long long) need, (unsigned long long) free_b);
-    gt4hip_destroy (ctx);
-    return 1;
-  }
-  gt4hip_list *lists[2];
-  for (unsigned int f = 0; f < 2; f++) {
-    if (files[f].index_kmers ? gt4hip_list_upload_index (ctx, files[f].index_kmers, files[f].header.n_words, files[f].index_locations, wlen, &lists[f])
-                             : gt4hip_list_upload (ctx, files[f].records, files[f].header.n_words, wlen, &lists[f])) {
-      fprintf (stderr, "Error: uploading %s to the GPU failed: %s\n", fnames[f], gt4hip_last_error (ctx));
-      return 1;
-    }
-    if (getenv ("GT4HIP_CHECK_SORTED") && atoi (getenv ("GT4HIP_CHECK_SORTED"))) {
-      int sorted = 0;
-      if (gt4hip_list_is_sorted (ctx, lists[f], &sorted) || !sorted) {
-        fprintf (stderr, "Error: File %s is not sorted by k-mer (strictly ascending, unique)\n", fnames[f]);
-        return 1;
-      }
-    }
-  }
-  gt4hip_mismatch_params prm;
-  memset (&prm, 0, sizeof prm);
-  prm.ops = GT4HIP_OP_DIFF1 | (find_ddiff ? GT4HIP_OP_DIFF2 : 0);
-  prm.cutoff = cutoff;
-  prm.subtract = subtraction;
-  prm.n_mismatch = nmm;
-  prm.count_only = countonly;
-  gt4hip_compare_result res;
-  memset (&res, 0, sizeof res);
-  if (gt4hip_compare_mismatch (ctx, lists[0], lists[1], &prm, &res)) {
-    fprintf (stderr, "Error: %s\n", gt4hip_last_error (ctx));
-    return 1;
-  }
-  gt4hip_mismatch_stats st;
-  gt4hip_mismatch_stats_get (ctx, &st);
-  if (debug) fprintf (stderr, "Finding diff with mismatches (%llu entries)\n", (unsigned long long) st.prepass_words[0]);
-  if (verbose) {
-    fprintf (stderr, "GPU mismatch pre-pass: %.3f ms, device total %.3f ms, %llu probes\n", res.merge_kernel_ms, res.device_ms,
-             (unsigned long long) st.probes);
-    for (uint32_t l = 0; l < st.n_levels; l++)
-      fprintf (stderr, "  level %u: %llu words, %llu probes, %.3f ms\n", l + 1, (unsigned long long) st.level_words[l],
-               (unsigned long long) st.level_probes[l], st.level_ms[l]);
-  }
-  int bad = 0;
-  if (countonly) {
-    for (int s = 2; s < 4; s++)
-      if ((prm.ops >> s) & 1u) fprintf (stdout, "NUnique\t%llu\nNTotal\t%llu\n", (unsigned long long) res.n_words[s], (unsigned long long) res.total_count[s]);
-  } else {
-    /* "<out>_<k>_<N>_diff1.list" / "_diff2.list", written as ".tmp" and renamed (reference :1072-1091) */
-    char name[4][2048], tmp_name[4][2100];
-    GT4ListWriter w[4];
-    const gt4hip_list *wl[2];
-    uint64_t wfirst[2], wcount[2], woff[2];
-    int wfd[2], ws[2];
-    uint32_t nw = 0;
-    for (int s = 2; s < 4 && !bad; s++) {
-      if (!((prm.ops >> s) & 1u)) continue;
-      snprintf (name[s], sizeof name[s], "%s_%u_%u_%s.list", outputname, wlen, nmm, s == 2 ? "diff1" : "diff2");
-      snprintf (tmp_name[s], sizeof tmp_name[s], "%s.tmp", name[s]);
-      if (gt4_listwriter_begin (&w[s], tmp_name[s], wlen, 0666)) {
-        fprintf (stderr, "Error: Cannot create output file %s\n", tmp_name[s]);
-        bad = 1;
-        break;
-      }
-      wl[nw] = res.out[s];
-      wfirst[nw] = 0;
-      wcount[nw] = res.n_words[s];
-      wfd[nw] = w[s].fd;
-      woff[nw] = 48;
-      ws[nw] = s;
-      nw++;
-    }
-    if (!bad && nw && gt4hip_lists_write_fd (ctx, nw, wl, wfirst, wcount, wfd, woff)) {
-      fprintf (stderr, "Error: writing the results failed: %s\n", gt4hip_last_error (ctx));
-      bad = 1;
-    }
-    for (uint32_t q = 0; q < nw; q++) {
-      const int s = ws[q];
-      if (bad) {
-        gt4_listwriter_abort (&w[s]);
-        unlink (tmp_name[s]);
-        continue;
-      }
-      if (gt4_listwriter_finish (&w[s], res.n_words[s], res.total_count[s])) {
-        fprintf (stderr, "Error: writing %s failed: %s\n", tmp_name[s], strerror (errno));
-        unlink (tmp_name[s]);
-        bad = 1;
-      } else if (rename (tmp_name[s], name[s])) {
-        fprintf (stderr, "Error: Cannot rename %s to %s\n", tmp_name[s], name[s]);
-        bad = 1;
-      }
-    }
-    for (int s = 2; s < 4; s++) gt4hip_list_free (res.out[s]);
-  }
-  for (unsigned int f = 0; f < 2; f++) {
-    gt4hip_list_free (lists[f]);
-    gt4_listfile_close (&files[f]);
-  }
-  gt4hip_destroy (ctx);
-  return bad;
+  const char *e;
+  o->n_gpus = (e = getenv ("GT4HIP_GPUS")) ? atoi (e) : 0;
+  o->verbose = (e = getenv ("GT4HIP_VERBOSE")) && atoi (e);
+  o->hbm_limit = parse_bytes (getenv ("GT4HIP_HBM_LIMIT"));
+  o->pipeline_off = (e = getenv ("GT4HIP_PIPELINE")) && !atoi (e);
+  o->gather_rccl = (e = getenv ("GT4HIP_GATHER")) && !strcmp (e, "rccl");
+  o->check_sorted = (e = getenv ("GT4HIP_CHECK_SORTED")) && atoi (e);
+  o->device = (e = getenv ("GT4HIP_DEVICE")) ? atoi (e) : 0;
 }
 
-int main (int argc, const char *argv[])
+/* argv (reference :107-230; every quirk of its hand-rolled loop is kept) */
+static void parse_argv (int argc, const char *argv[], Options *o)
 {
-  const char *fnames[MAX_FILES];
-  unsigned int nfiles = 0;
-  int rule = GT4HIP_RULE_DEFAULT;
-  unsigned int cutoff = 1, nmm = 0, count_override = 1;
-  int find_union = 0, find_intrsec = 0, find_diff = 0, find_ddiff = 0, subtraction = 0, countonly = 0, print_operation = 0;
-  int find_subset = 0, stream = 0, debug = 0;
-  int n_gpus = getenv ("GT4HIP_GPUS") ? atoi (getenv ("GT4HIP_GPUS")) : 0;
-  /* lines of this implementation's own (device, kernel times, chunk plan): -D stays the reference's transcript */
-  const int verbose = getenv ("GT4HIP_VERBOSE") && atoi (getenv ("GT4HIP_VERBOSE"));
-  const char *outputname = "out";
+  int stream = 0;
   char *end;
-
-  if (argc <= 1) print_help (1);
-
-  /* ---- argv (reference :107-230; every quirk of its hand-rolled loop is kept) */
+  o->rule = GT4HIP_RULE_DEFAULT;
+  o->cutoff = 1;
+  o->count_override = 1;
+  o->outputname = "out";
   for (int i = 1; i < argc; i++) {
     const char *arg = argv[i];
     if (arg[0] != '-') {
-      if (nfiles >= MAX_FILES) {
+      if (o->nfiles >= MAX_FILES) {
         fprintf (stderr, "Too many file arguments (max %d)\n", MAX_FILES);
         print_help (1);
       }
-      fnames[nfiles++] = arg;
+      o->fnames[o->nfiles++] = arg;
       continue;
     }
     switch (lookup_option (arg)) {
       case OPT_VERSION:
         print_version ();
-        return 0;
+        exit (0);
       case OPT_HELP:
         print_help (0);
         break;
@@ -352,14 +239,14 @@ int main (int argc, const char *argv[])
           i += 1; /* the reference skips the next argument here as well */
           break;
         }
-        outputname = argv[++i];
+        o->outputname = argv[++i];
         break;
       case OPT_CUTOFF:
         if (!argv[i + 1]) {
-          fprintf (stderr, "Warning: No frequency cut-off specified! Using the default value: %d.\n", cutoff);
+          fprintf (stderr, "Warning: No frequency cut-off specified! Using the default value: %d.\n", o->cutoff);
           break;
         }
-        cutoff = (unsigned int) strtol (argv[i + 1], &end, 10);
+        o->cutoff = (unsigned int) strtol (argv[i + 1], &end, 10);
         if (*end != 0) {
           fprintf (stderr, "Error: Invalid frequency cut-off: %s! Must be an integer.\n", argv[i + 1]);
           print_help (1);
@@ -371,22 +258,22 @@ int main (int argc, const char *argv[])
           fprintf (stderr, "Warning: No number of mismatches specified!");
           break;
         }
-        nmm = (unsigned int) strtol (argv[i + 1], &end, 10);
+        o->nmm = (unsigned int) strtol (argv[i + 1], &end, 10);
         if (*end != 0) {
           fprintf (stderr, "Error: Invalid number of mismatches: %s! Must be an integer.\n", argv[i + 1]);
           print_help (1);
         }
         i += 1;
         break;
-      case OPT_UNION: find_union = 1; break;
-      case OPT_INTRSEC: find_intrsec = 1; break;
-      case OPT_DIFF: find_diff = 1; break;
-      case OPT_DDIFF: find_ddiff = 1; break;
+      case OPT_UNION: o->find_union = 1; break;
+      case OPT_INTRSEC: o->find_intrsec = 1; break;
+      case OPT_DIFF: o->find_diff = 1; break;
+      case OPT_DDIFF: o->find_ddiff = 1; break;
       case OPT_DU:
-        find_diff = 1;
-        subtraction = 1;
+        o->find_diff = 1;
+        o->subtraction = 1;
         break;
-      case OPT_COUNT_ONLY: countonly = 1; break;
+      case OPT_COUNT_ONLY: o->countonly = 1; break;
       case OPT_RULE: {
         static const struct { const char *name; int rule; } RULES[] = {
           { "default", GT4HIP_RULE_DEFAULT }, { "add", GT4HIP_RULE_ADD }, { "sum", GT4HIP_RULE_ADD }, { "subtract", GT4HIP_RULE_SUBTRACT },
@@ -395,17 +282,17 @@ int main (int argc, const char *argv[])
         i += 1;
         if (i >= argc) print_help (1);
         if (argv[i][0] >= '1' && argv[i][0] <= '9') {
-          rule = GT4HIP_RULE_NUMBER;
-          count_override = (unsigned int) strtol (argv[i], &end, 10);
+          o->rule = GT4HIP_RULE_NUMBER;
+          o->count_override = (unsigned int) strtol (argv[i], &end, 10);
         } else {
           for (size_t r = 0; r < sizeof RULES / sizeof RULES[0]; r++)
-            if (!strcmp (argv[i], RULES[r].name)) rule = RULES[r].rule;
+            if (!strcmp (argv[i], RULES[r].name)) o->rule = RULES[r].rule;
           /* an unknown rule name is silently ignored, as in the reference */
         }
         break;
       }
       case OPT_SUBSET:
-        find_subset = 1;
+        o->find_subset = 1;
         i += 1;
         if (i >= argc) print_help (1);
         if (strcmp (argv[i], "rand") && strcmp (argv[i], "rand_unique") && strcmp (argv[i], "rand_weighted_unique")) print_help (1);
@@ -421,15 +308,15 @@ int main (int argc, const char *argv[])
         i += 1;
         if (i >= argc) print_help (1);
         break; /* only --subset draws random numbers */
-      case OPT_PRINT_OP: print_operation = 1; break;
+      case OPT_PRINT_OP: o->print_operation = 1; break;
       case OPT_NOSCOUTS: break;
       case OPT_STREAM: stream = 1; break;
-      case OPT_DEBUG: debug += 1; break;
+      case OPT_DEBUG: o->debug += 1; break;
       case OPT_GPUS:
         i += 1;
         if (i >= argc) print_help (1);
-        n_gpus = atoi (argv[i]);
-        if (n_gpus < 1) {
+        o->n_gpus = atoi (argv[i]);
+        if (o->n_gpus < 1) {
           fprintf (stderr, "Error: Invalid number of GPUs: %s!\n", argv[i]);
           print_help (1);
         }
@@ -439,42 +326,41 @@ int main (int argc, const char *argv[])
         print_help (1);
     }
   }
-  if (debug) fprintf (stderr, "Rule: %d\n", rule);
-  if (debug) fprintf (stderr, "Num files: %d\n", nfiles);
-  if (nmm || find_subset) {
-    if (stream) fprintf (stderr, "Warning: Subset and mismatches are incompatible with streaming, using mapping\n");
-    stream = 0;
-  }
+  if (o->debug) fprintf (stderr, "Rule: %d\n", o->rule);
+  if (o->debug) fprintf (stderr, "Num files: %d\n", o->nfiles);
+  if ((o->nmm || o->find_subset) && stream) fprintf (stderr, "Warning: Subset and mismatches are incompatible with streaming, using mapping\n");
+}
 
-  /* ---- open the inputs (reference :250-290) */
-  static GT4ListFile files[MAX_FILES];
+/* Maps the inputs (reference :250-290) and returns their word length; any bad file ends the program */
+static unsigned int open_inputs (const Options *o, GT4ListFile *files)
+{
   unsigned int wlen = 0, err = 0;
-  for (unsigned int f = 0; f < nfiles; f++) {
+  for (unsigned int f = 0; f < o->nfiles; f++) {
     uint32_t code;
     files[f].file_map = NULL;
-    if (gt4_listfile_sniff (fnames[f], &code)) {
-      fprintf (stderr, "Error: Cannot open %s\n", fnames[f]);
+    if (gt4_listfile_sniff (o->fnames[f], &code)) {
+      fprintf (stderr, "Error: Cannot open %s\n", o->fnames[f]);
       err = 1;
       continue;
     }
     if (code != GT4_LIST_CODE_VALUE && code != GT4_INDEX_CODE_VALUE) {
       /* the reference reports both: no object was made, so the interface lookup fails as well (:272-279) */
-      fprintf (stderr, "Error: File %s has unknown format\n", fnames[f]);
-      fprintf (stderr, "Error: File %s is invalid or corrupted\n", fnames[f]);
+      fprintf (stderr, "Error: File %s has unknown format\n", o->fnames[f]);
+      fprintf (stderr, "Error: File %s is invalid or corrupted\n", o->fnames[f]);
       err = 1;
       continue;
     }
     /* a GT4I index is read as the sorted (k-mer, number of locations) list it contains (:269-270) */
-    if (code == GT4_INDEX_CODE_VALUE ? gt4_indexfile_open (fnames[f], GT4_VERSION_MAJOR, &files[f])
-                                     : gt4_listfile_open (fnames[f], GT4_VERSION_MAJOR, &files[f])) {
-      fprintf (stderr, "Error: File %s is invalid or corrupted\n", fnames[f]);
+    if (code == GT4_INDEX_CODE_VALUE ? gt4_indexfile_open (o->fnames[f], GT4_VERSION_MAJOR, &files[f])
+                                     : gt4_listfile_open (o->fnames[f], GT4_VERSION_MAJOR, &files[f])) {
+      fprintf (stderr, "Error: File %s is invalid or corrupted\n", o->fnames[f]);
       err = 1;
       continue;
     }
     if (!wlen) {
       wlen = files[f].header.word_length;
     } else if (files[f].header.word_length != wlen) {
-      fprintf (stderr, "Error: File %s has different word length (%u != %u)\n", fnames[f], files[f].header.word_length, wlen);
+      fprintf (stderr, "Error: File %s has different word length (%u != %u)\n", o->fnames[f], files[f].header.word_length, wlen);
       err = 1;
     }
   }
@@ -482,203 +368,389 @@ int main (int argc, const char *argv[])
     fprintf (stderr, "Stopping...\n");
     exit (1);
   }
-  if (find_subset) {
+  return wlen;
+}
+
+/* validity checks, in the reference's order (:317-352) */
+static void validate (Options *o)
+{
+  if (o->find_subset) {
     fprintf (stderr, "Error: --subset is not part of the GPU set-operation path\n");
     exit (1);
   }
-
-  /* ---- validity checks, in the reference's order (:317-352) */
-  if (nfiles < 2) {
+  if (o->nfiles < 2) {
     fprintf (stderr, "Error: At least 2 list/index files are needed\n");
     exit (1);
   }
-  if (nfiles > 2) {
-    if (!(find_union || find_intrsec) || find_diff || find_ddiff) {
+  if (o->nfiles > 2) {
+    if (!(o->find_union || o->find_intrsec) || o->find_diff || o->find_ddiff) {
       fprintf (stderr, "Error: Algorithm incompatible with multiple files!\n");
       print_help (1);
     }
-    if (nmm) {
+    if (o->nmm) {
       fprintf (stderr, "Error: Multiple files are not compatible with mismatches!\n");
       print_help (1);
     }
   }
-  if (find_ddiff) find_diff = 1;
-  if (!find_diff && nmm) fprintf (stderr, "Warning: Number of mismatches are not used!\n");
-  if (!find_diff && subtraction) fprintf (stderr, "Warning: Subtraction is not used!\n");
-  if (strlen (outputname) > 200) {
+  if (o->find_ddiff) o->find_diff = 1;
+  if (!o->find_diff && o->nmm) fprintf (stderr, "Warning: Number of mismatches are not used!\n");
+  if (!o->find_diff && o->subtraction) fprintf (stderr, "Warning: Subtraction is not used!\n");
+  if (strlen (o->outputname) > 200) {
     fprintf (stderr, "Error: Output name exceeds the 200 character limit.\n");
     exit (1);
   }
-  if (!find_intrsec && (rule == GT4HIP_RULE_MIN || rule == GT4HIP_RULE_FIRST || rule == GT4HIP_RULE_SECOND)) {
+  if (!o->find_intrsec && (o->rule == GT4HIP_RULE_MIN || o->rule == GT4HIP_RULE_FIRST || o->rule == GT4HIP_RULE_SECOND)) {
     fprintf (stderr, "Error: Rules min, fist and second can only be used with finding the intersection.\n");
     exit (1);
   }
-  if ((!find_intrsec && !find_diff) && (rule == GT4HIP_RULE_SUBTRACT)) {
+  if ((!o->find_intrsec && !o->find_diff) && (o->rule == GT4HIP_RULE_SUBTRACT)) {
     fprintf (stderr, "Error: Rule subtract can only be used with intersection and difference.\n");
     exit (1);
   }
-  if (print_operation) {
-    fprintf (stdout, "Operation\t%s%s%s%s\trule\t%u\nFiles\t%u\n", find_union ? "U" : "", find_intrsec ? "I" : "", find_diff ? "D" : "",
-             find_ddiff ? "X" : "", rule, nfiles);
-    for (unsigned int f = 0; f < nfiles; f++) fprintf (stdout, "%u\t%s\n", f, fnames[f]);
+  if (o->print_operation) {
+    fprintf (stdout, "Operation\t%s%s%s%s\trule\t%u\nFiles\t%u\n", o->find_union ? "U" : "", o->find_intrsec ? "I" : "", o->find_diff ? "D" : "",
+             o->find_ddiff ? "X" : "", o->rule, o->nfiles);
+    for (unsigned int f = 0; f < o->nfiles; f++) fprintf (stdout, "%u\t%s\n", f, o->fnames[f]);
   }
-  if (nmm) return mismatch_main (files, wlen, find_diff, find_ddiff, subtraction, countonly, outputname, cutoff, nmm, debug, verbose, n_gpus,
-                                 parse_bytes (getenv ("GT4HIP_HBM_LIMIT")), fnames);
+}
 
+/* ---- what the three execution paths share */
 
-  /* ---- key-range shards: several GPUs and / or chunks streamed through the device memory */
-  static const char *const SUFFIX[4] = { "union", "intrsec", "0_diff1", "0_diff2" };
-  uint64_t hbm_limit = parse_bytes (getenv ("GT4HIP_HBM_LIMIT"));
-  int use_shards = n_gpus >= 1 || hbm_limit != 0;
-  int auto_budget = 0;
+static gt4hip_context *create_context (const Options *o)
+{
   gt4hip_context *ctx = NULL;
-  if (!use_shards) {
-    uint64_t in_records = 0;
-    for (unsigned int f = 0; f < nfiles; f++) in_records += files[f].header.n_words;
-    const int pipeline_off = getenv ("GT4HIP_PIPELINE") && !atoi (getenv ("GT4HIP_PIPELINE"));
-    if (12 * in_records >= (4ull << 30) && !pipeline_off) {
-      /* big inputs: key-range chunks through the loader / merger / writer pipeline, so that reading the next
-       * chunk and writing the previous one overlap the merge (GT4HIP_PIPELINE=0 keeps everything in one
-       * piece).  No context is created here: the worker that runs the job (in this process) creates the
-       * only one, measures the device's free memory and chooses the chunk budget itself -- the HIP runtime
-       * starts once per process. */
-      use_shards = 1;
-      auto_budget = 1;
-    }
+  if (gt4hip_create (o->device, &ctx)) {
+    fprintf (stderr, "Error: %s\n", gt4hip_last_error (NULL));
+    exit (1);
   }
-  if (!use_shards) {
-    const char *dev = getenv ("GT4HIP_DEVICE");
-    if (gt4hip_create (dev ? atoi (dev) : 0, &ctx)) {
-      fprintf (stderr, "Error: %s\n", gt4hip_last_error (NULL));
-      exit (1);
-    }
-    if (verbose) fprintf (stderr, "Device: %s\n", gt4hip_device_info (ctx));
-    /* inputs + worst-case outputs (+ the N-way tree's intermediates) must fit, else stream in chunks */
-    uint64_t free_b = 0, total_b = 0, need = 0, in_records = 0;
-    gt4hip_device_memory (ctx, &free_b, &total_b);
-    for (unsigned int f = 0; f < nfiles; f++) in_records += files[f].header.n_words;
-    if (nfiles == 2) need = 12 * in_records * (1 + (uint64_t) (find_union + find_intrsec + find_diff + find_ddiff));
-    else need = 12 * in_records * 4;
-    if (free_b && need > free_b / 100 * 85) {
-      if (verbose) fprintf (stderr, "Inputs and outputs need %llu bytes, %llu are free: streaming in key-range chunks\n", (unsigned long long) need, (unsigned long long) free_b);
-      gt4hip_destroy (ctx);
-      ctx = NULL;
-      use_shards = 1;
-    }
-  }
-  if (use_shards) {
-    GT4ShardJob job;
-    memset (&job, 0, sizeof job);
-    job.n_files = nfiles;
-    job.files = files;
-    job.word_length = wlen;
-    job.n_ranks = n_gpus >= 1 ? n_gpus : 1;
-    job.hbm_limit = hbm_limit;
-    job.auto_budget = auto_budget;
-    job.gather_rccl = getenv ("GT4HIP_GATHER") && !strcmp (getenv ("GT4HIP_GATHER"), "rccl");
-    job.debug = verbose;
-    job.prm.rule = rule;
-    job.prm.cutoff = cutoff;
-    job.prm.subtract = subtraction;
-    job.prm.count_override = count_override;
-    job.prm.count_only = countonly;
-    char names[4][2048];
-    int v = 0;
-    if (nfiles == 2) {
-      if (debug) {
-        fprintf (stderr, "compare_wordmaps: methods %u/%u/%u/%u\n", find_union, find_intrsec, find_diff, find_ddiff);
-        fprintf (stderr, "compare_wordmaps: List 1: %llu entries\n", (unsigned long long) files[0].header.n_words);
-        fprintf (stderr, "compare_wordmaps; List 2: %llu entries\n", (unsigned long long) files[1].header.n_words);
-      }
-      job.mode = GT4_SHARD_PAIR;
-      job.prm.ops = (find_union ? GT4HIP_OP_UNION : 0) | (find_intrsec ? GT4HIP_OP_INTRSEC : 0) | (find_diff ? GT4HIP_OP_DIFF1 : 0) |
-                    (find_ddiff ? GT4HIP_OP_DIFF2 : 0);
-      job.out_mode = 0666;
-      for (int s = 0; s < 4; s++) {
-        if (!((job.prm.ops >> s) & 1u) || countonly) continue;
-        snprintf (names[s], sizeof names[s], "%s_%d_%s.list", outputname, wlen, SUFFIX[s]);
-        job.out_name[s] = names[s];
-      }
-      GT4ShardResult res;
-      if (job.prm.ops) {
-        if (gt4_shard_run (&job, &res)) exit (1);
-        if (verbose) fprintf (stderr, "Sharded run: %u chunks over %d GPU(s)\n", res.n_chunks, job.n_ranks);
-        for (int s = 0; s < 4; s++) {
-          if (!((job.prm.ops >> s) & 1u)) continue;
-          if (countonly) fprintf (stdout, "NUnique\t%llu\nNTotal\t%llu\n", (unsigned long long) res.n_words[s], (unsigned long long) res.total_count[s]);
-          else if (debug && s >= 2) fprintf (stderr, "Renaming %s.tmp to %s\n", names[s], names[s]);
-        }
-      }
-    } else {
-      for (int pass = 0; pass < 2; pass++) {
-        const int is_union = pass == 0;
-        if (is_union ? !find_union : !find_intrsec) continue;
-        job.mode = is_union ? GT4_SHARD_UNION_MULTI : GT4_SHARD_INTERSECT_MULTI;
-        job.out_mode = 0644;
-        job.out_name[0] = NULL;
-        if (!countonly) {
-          snprintf (names[0], sizeof names[0], "%s_%d_%s.list", outputname, wlen, is_union ? "union" : "intrsec");
-          job.out_name[0] = names[0];
-        }
-        GT4ShardResult res;
-        const double t_s = now_seconds ();
-        const int rc = gt4_shard_run (&job, &res);
-        const double t_e = now_seconds ();
-        if (rc && res.rule_rejected) {
-          fprintf (stderr, "%s\n", res.message);
-          v = 1;
-          continue;
-        }
-        if (rc) exit (1);
-        v = 0;
-        if (debug) {
-          unsigned long long total = 0;
-          for (unsigned int f = 0; f < nfiles; f++) total += files[f].header.n_words;
-          fprintf (stderr, "Combined %u maps: input %llu (%.3f Mwords/s) output %llu (%.3f Mwords/s)\n", nfiles, is_union ? total : 0ull,
-                   (is_union ? total : 0ull) / (1000000 * (t_e - t_s)), (unsigned long long) res.n_words[0], res.n_words[0] / (1000000 * (t_e - t_s)));
-        }
-        if (countonly || debug) fprintf (stdout, "NUnique\t%llu\nNTotal\t%llu\n", (unsigned long long) res.n_words[0], (unsigned long long) res.total_count[0]);
-      }
-    }
-    for (unsigned int f = 0; f < nfiles; f++) gt4_listfile_close (&files[f]);
-    return v ? 1 : 0;
-  }
+  if (o->verbose) fprintf (stderr, "Device: %s\n", gt4hip_device_info (ctx));
+  return ctx;
+}
 
-  static gt4hip_list *lists[MAX_FILES];
-  for (unsigned int f = 0; f < nfiles; f++) {
+static void upload_inputs (const Options *o, gt4hip_context *ctx, const GT4ListFile *files, unsigned int wlen, gt4hip_list **lists)
+{
+  for (unsigned int f = 0; f < o->nfiles; f++) {
     if (files[f].index_kmers ? gt4hip_list_upload_index (ctx, files[f].index_kmers, files[f].header.n_words, files[f].index_locations, wlen, &lists[f])
                              : gt4hip_list_upload (ctx, files[f].records, files[f].header.n_words, wlen, &lists[f])) {
-      fprintf (stderr, "Error: uploading %s to the GPU failed: %s\n", fnames[f], gt4hip_last_error (ctx));
+      fprintf (stderr, "Error: uploading %s to the GPU failed: %s\n", o->fnames[f], gt4hip_last_error (ctx));
       exit (1);
     }
     /* the reference trusts its inputs to be strictly ascending (results are undefined otherwise);
      * GT4HIP_CHECK_SORTED=1 verifies that on the device before merging */
-    if (getenv ("GT4HIP_CHECK_SORTED") && atoi (getenv ("GT4HIP_CHECK_SORTED"))) {
+    if (o->check_sorted) {
       int sorted = 0;
       if (gt4hip_list_is_sorted (ctx, lists[f], &sorted) || !sorted) {
-        fprintf (stderr, "Error: File %s is not sorted by k-mer (strictly ascending, unique)\n", fnames[f]);
+        fprintf (stderr, "Error: File %s is not sorted by k-mer (strictly ascending, unique)\n", o->fnames[f]);
         exit (1);
       }
     }
   }
+}
 
-  int v = 0;
-  if (nfiles == 2) {
-    /* ---- compare_wordmaps (reference :789-955) */
-    if (debug) {
-      fprintf (stderr, "compare_wordmaps: methods %u/%u/%u/%u\n", find_union, find_intrsec, find_diff, find_ddiff);
-      fprintf (stderr, "compare_wordmaps: List 1: %llu entries\n", (unsigned long long) files[0].header.n_words);
-      fprintf (stderr, "compare_wordmaps; List 2: %llu entries\n", (unsigned long long) files[1].header.n_words);
+static uint32_t ops_mask (const Options *o)
+{
+  return (o->find_union ? GT4HIP_OP_UNION : 0) | (o->find_intrsec ? GT4HIP_OP_INTRSEC : 0) | (o->find_diff ? GT4HIP_OP_DIFF1 : 0) |
+         (o->find_ddiff ? GT4HIP_OP_DIFF2 : 0);
+}
+
+static gt4hip_compare_params compare_params (const Options *o)
+{
+  return (gt4hip_compare_params) { .ops = ops_mask (o), .rule = o->rule, .cutoff = o->cutoff, .subtract = o->subtraction,
+                                   .count_override = o->count_override, .count_only = o->countonly };
+}
+
+/* the -D lines at the head of compare_wordmaps (reference :789-955) and of compare_wordmaps_mm (:958-1093) */
+static void print_lists_debug (const Options *o, const GT4ListFile *files)
+{
+  if (!o->debug) return;
+  if (!o->nmm) fprintf (stderr, "compare_wordmaps: methods %u/%u/%u/%u\n", o->find_union, o->find_intrsec, o->find_diff, o->find_ddiff);
+  fprintf (stderr, "compare_wordmaps: List 1: %llu entries\n", (unsigned long long) files[0].header.n_words);
+  fprintf (stderr, "compare_wordmaps; List 2: %llu entries\n", (unsigned long long) files[1].header.n_words);
+  if (!o->nmm) return;
+  fprintf (stderr, "Table 1: %llu entries\n", (unsigned long long) files[0].header.n_words);
+  fprintf (stderr, "Table 2: %llu entries\n", (unsigned long long) files[1].header.n_words);
+}
+
+/* the end of every path: the device lists and the mappings, file by file, then the context (NULL: none was made) */
+static void release (const Options *o, GT4ListFile *files, gt4hip_list *const *lists, gt4hip_context *ctx)
+{
+  for (unsigned int f = 0; f < o->nfiles; f++) {
+    if (lists) gt4hip_list_free (lists[f]);
+    gt4_listfile_close (&files[f]);
+  }
+  gt4hip_destroy (ctx);
+}
+
+static void print_totals (uint64_t n_words, uint64_t total_count)
+{
+  fprintf (stdout, "NUnique\t%llu\nNTotal\t%llu\n", (unsigned long long) n_words, (unsigned long long) total_count);
+}
+
+/* "<out>_<k>_union.list", "_intrsec.list", "<out>_<k>_<mismatches>_diff1.list", "_diff2.list" (reference :814-834, -mm :1072-1091) */
+static void output_name (const Options *o, unsigned int wlen, int s, char name[2048])
+{
+  if (s < 2) snprintf (name, 2048, "%s_%u_%s.list", o->outputname, wlen, s ? "intrsec" : "union");
+  else snprintf (name, 2048, "%s_%u_%u_%s.list", o->outputname, wlen, o->nmm, s == 2 ? "diff1" : "diff2");
+}
+
+/* The streams `ops` of a pair result: under --count_only their totals; else each to its own "<name>.tmp" at once (the copy
+ * threads are dealt to the files), then header back-patch and rename in the reference's order (:907-953, -mm :1072-1091).
+ * Frees the result lists.  Returns 1 after a message, with no temporary left behind. */
+static int write_outputs (const Options *o, gt4hip_context *ctx, unsigned int wlen, uint32_t ops, gt4hip_compare_result *res)
+{
+  if (o->countonly) {
+    for (int s = 0; s < 4; s++)
+      if ((ops >> s) & 1u) print_totals (res->n_words[s], res->total_count[s]);
+    return 0;
+  }
+  char name[4][2048], tmp_name[4][2100];
+  GT4ListWriter w[4];
+  const gt4hip_list *wl[4];
+  uint64_t wfirst[4], wcount[4], woff[4];
+  int wfd[4], ws[4];
+  uint32_t nw = 0;
+  int bad = 0;
+  for (int s = 0; s < 4; s++) {
+    if (!((ops >> s) & 1u)) continue;
+    output_name (o, wlen, s, name[s]);
+    snprintf (tmp_name[s], sizeof tmp_name[s], "%s.tmp", name[s]);
+    /* fopen (.., "w") in the reference: mode 0666 minus umask */
+    if (gt4_listwriter_begin (&w[s], tmp_name[s], wlen, 0666)) {
+      fprintf (stderr, "Error: Cannot create output file %s\n", tmp_name[s]);
+      bad = 1;
+      break;
     }
-    gt4hip_compare_params prm;
-    memset (&prm, 0, sizeof prm);
-    prm.ops = (find_union ? GT4HIP_OP_UNION : 0) | (find_intrsec ? GT4HIP_OP_INTRSEC : 0) | (find_diff ? GT4HIP_OP_DIFF1 : 0) |
-              (find_ddiff ? GT4HIP_OP_DIFF2 : 0);
-    prm.rule = rule;
-    prm.cutoff = cutoff;
-    prm.subtract = subtraction;
-    prm.count_override = count_override;
-    prm.count_only = countonly;
+    wl[nw] = res->out[s];
+    wfirst[nw] = 0;
+    wcount[nw] = res->n_words[s];
+    wfd[nw] = w[s].fd;
+    woff[nw] = 48;
+    ws[nw] = s;
+    nw++;
+  }
+  if (!bad && nw && gt4hip_lists_write_fd (ctx, nw, wl, wfirst, wcount, wfd, woff)) {
+    fprintf (stderr, "Error: writing the results failed: %s\n", gt4hip_last_error (ctx));
+    bad = 1;
+  }
+  for (uint32_t q = 0; q < nw; q++) {
+    const int s = ws[q];
+    if (bad) {
+      gt4_listwriter_abort (&w[s]);
+      unlink (tmp_name[s]);
+      continue;
+    }
+    /* compare_wordmaps announces the renames of the differences under -D, compare_wordmaps_mm does not */
+    if (o->debug && s >= 2 && !o->nmm) fprintf (stderr, "Renaming %s to %s\n", tmp_name[s], name[s]);
+    if (gt4_listwriter_finish (&w[s], res->n_words[s], res->total_count[s])) {
+      fprintf (stderr, "Error: writing %s failed: %s\n", tmp_name[s], strerror (errno));
+      unlink (tmp_name[s]);
+      bad = 1;
+    } else if (rename (tmp_name[s], name[s])) {
+      fprintf (stderr, "Error: Cannot rename %s to %s\n", tmp_name[s], name[s]);
+      bad = 1;
+    }
+  }
+  for (int s = 0; s < 4; s++) gt4hip_list_free (res->out[s]);
+  return bad;
+}
+
+/* union_multi / intersect_multi (reference :366-422): the union pass, then the intersection pass.  With `job` every pass
+ * is a gt4_shard_run, which writes the output itself; without it the lists are resident in `ctx`.  Returns the exit code. */
+static int run_multi (const Options *o, const GT4ListFile *files, unsigned int wlen, GT4ShardJob *job, gt4hip_context *ctx, gt4hip_list *const *lists)
+{
+  int v = 0;
+  for (int pass = 0; pass < 2; pass++) {
+    const int is_union = pass == 0;
+    if (is_union ? !o->find_union : !o->find_intrsec) continue;
+    char name[2048];
+    output_name (o, wlen, pass, name);
+    int rc;
+    GT4ShardResult sres;
+    gt4hip_multi_result mres;
+    memset (&mres, 0, sizeof mres);
+    if (job) {
+      job->mode = is_union ? GT4_SHARD_UNION_MULTI : GT4_SHARD_INTERSECT_MULTI;
+      job->out_mode = 0644;
+      job->out_name[0] = o->countonly ? NULL : name;
+    }
+    const double t_s = now_seconds ();
+    if (job) rc = gt4_shard_run (job, &sres);
+    else rc = (is_union ? gt4hip_union_multi : gt4hip_intersect_multi) (ctx, (const gt4hip_list *const *) lists, o->nfiles, o->cutoff, o->rule,
+                                                                        o->count_override, o->countonly, &mres);
+    const double t_e = now_seconds ();
+    const int rule_rejected = job ? sres.rule_rejected : rc == GT4HIP_ERULE;
+    const char *message = job ? sres.message : rc ? gt4hip_last_error (ctx) : "";
+    const uint64_t n_words = job ? sres.n_words[0] : mres.n_words, total_count = job ? sres.total_count[0] : mres.total_count;
+    if (rc && rule_rejected) {
+      fprintf (stderr, "%s\n", message);
+      v = 1; /* the reference returns 1 from the merge and exits 1 without an output file */
+      continue;
+    }
+    if (rc) {
+      if (!job) fprintf (stderr, "Error: %s\n", message); /* gt4_shard_run has said why */
+      exit (1);
+    }
+    v = 0;
+    if (o->debug) {
+      unsigned long long total = 0;
+      for (unsigned int f = 0; f < o->nfiles; f++) total += files[f].header.n_words;
+      fprintf (stderr, "Combined %u maps: input %llu (%.3f Mwords/s) output %llu (%.3f Mwords/s)\n", o->nfiles, is_union ? total : 0ull,
+               (is_union ? total : 0ull) / (1000000 * (t_e - t_s)), (unsigned long long) n_words, n_words / (1000000 * (t_e - t_s)));
+    }
+    if (!job && !o->countonly) {
+      /* creat (.., 0644) in the reference */
+      if (write_list_file (ctx, mres.out, wlen, n_words, total_count, name, 0644)) exit (1);
+      gt4hip_list_free (mres.out);
+    }
+    if (o->countonly || o->debug) print_totals (n_words, total_count);
+  }
+  return v;
+}
+
+/* ---- the three execution paths */
+
+/* compare_wordmaps_mm (reference :958-1093): two lists, diff1 and / or diff2 up to nmm mismatches */
+static int run_mismatch (const Options *o, GT4ListFile *files, unsigned int wlen)
+{
+  print_lists_debug (o, files);
+  /* without -d / -dd / -du the reference takes this path all the same and writes nothing */
+  if (!o->find_diff) {
+    release (o, files, NULL, NULL);
+    return 0;
+  }
+  if (o->n_gpus > 1 || o->hbm_limit) {
+    fprintf (stderr, "Error: -mm needs both lists resident on one GPU: it cannot be combined with %s\n",
+             o->n_gpus > 1 ? "--gpus N > 1 (GT4HIP_GPUS)" : "GT4HIP_HBM_LIMIT");
+    return 1;
+  }
+  if (!gt4hip_compare_mismatch || !gt4hip_mismatch_stats_get) {
+    fprintf (stderr, "Error: this build has no -mm (mismatch difference) path\n");
+    return 1;
+  }
+  gt4hip_context *ctx = create_context (o);
+  /* inputs, outputs and the lookup tables (~48 bytes per record of each side) must fit: there is no chunked -mm */
+  uint64_t free_b = 0, total_b = 0;
+  gt4hip_device_memory (ctx, &free_b, &total_b);
+  const uint64_t na = files[0].header.n_words, nb = files[1].header.n_words;
+  const uint64_t need = 12 * (na + nb) + 60 * na + (o->find_ddiff ? 60 * nb : 0);
+  if (free_b && need > free_b / 100 * 90) {
+    fprintf (stderr, "Error: %s: -mm needs about %llu bytes of device memory, %llu are free (both lists stay resident on one GPU)\n",
+             gt4hip_strerror (GT4HIP_ENOMEM), (unsigned long long) need, (unsigned long long) free_b);
+    gt4hip_destroy (ctx);
+    return 1;
+  }
+  gt4hip_list *lists[2];
+  upload_inputs (o, ctx, files, wlen, lists);
+  gt4hip_mismatch_params prm;
+  memset (&prm, 0, sizeof prm);
+  prm.ops = ops_mask (o) & (GT4HIP_OP_DIFF1 | GT4HIP_OP_DIFF2);
+  prm.cutoff = o->cutoff;
+  prm.subtract = o->subtraction;
+  prm.n_mismatch = o->nmm;
+  prm.count_only = o->countonly;
+  gt4hip_compare_result res;
+  memset (&res, 0, sizeof res);
+  if (gt4hip_compare_mismatch (ctx, lists[0], lists[1], &prm, &res)) {
+    fprintf (stderr, "Error: %s\n", gt4hip_last_error (ctx));
+    exit (1);
+  }
+  gt4hip_mismatch_stats st;
+  gt4hip_mismatch_stats_get (ctx, &st);
+  if (o->debug) fprintf (stderr, "Finding diff with mismatches (%llu entries)\n", (unsigned long long) st.prepass_words[0]);
+  if (o->verbose) {
+    fprintf (stderr, "GPU mismatch pre-pass: %.3f ms, device total %.3f ms, %llu probes\n", res.merge_kernel_ms, res.device_ms,
+             (unsigned long long) st.probes);
+    for (uint32_t l = 0; l < st.n_levels; l++)
+      fprintf (stderr, "  level %u: %llu words, %llu probes, %.3f ms\n", l + 1, (unsigned long long) st.level_words[l],
+               (unsigned long long) st.level_probes[l], st.level_ms[l]);
+  }
+  if (write_outputs (o, ctx, wlen, prm.ops, &res)) exit (1);
+  release (o, files, lists, ctx);
+  return 0;
+}
+
+static uint64_t input_records (const Options *o, const GT4ListFile *files)
+{
+  uint64_t n = 0;
+  for (unsigned int f = 0; f < o->nfiles; f++) n += files[f].header.n_words;
+  return n;
+}
+
+/* Big inputs with no plan given: key-range chunks through the loader / merger / writer pipeline, so that reading the next
+ * chunk and writing the previous one overlap the merge (GT4HIP_PIPELINE=0 keeps everything in one piece).  The worker that
+ * runs the job (in this process) measures the device's free memory and chooses the chunk budget itself. */
+static int wants_pipeline (const Options *o, const GT4ListFile *files)
+{
+  return o->n_gpus < 1 && !o->hbm_limit && !o->pipeline_off && 12 * input_records (o, files) >= (4ull << 30);
+}
+
+/* The context of a resident run, or NULL: the job goes through the key-range shards, and no context may exist in this
+ * process -- the workers are forked before any HIP call, and the HIP runtime starts once per process. */
+static gt4hip_context *resident_context (const Options *o, const GT4ListFile *files)
+{
+  if (o->n_gpus >= 1 || o->hbm_limit || wants_pipeline (o, files)) return NULL;
+  gt4hip_context *ctx = create_context (o);
+  /* inputs + worst-case outputs (+ the N-way tree's intermediates) must fit, else stream in chunks */
+  uint64_t free_b = 0, total_b = 0;
+  gt4hip_device_memory (ctx, &free_b, &total_b);
+  const uint64_t need = 12 * input_records (o, files) * (o->nfiles == 2 ? 1 + (uint64_t) (o->find_union + o->find_intrsec + o->find_diff + o->find_ddiff) : 4);
+  if (free_b && need > free_b / 100 * 85) {
+    if (o->verbose) fprintf (stderr, "Inputs and outputs need %llu bytes, %llu are free: streaming in key-range chunks\n", (unsigned long long) need, (unsigned long long) free_b);
+    gt4hip_destroy (ctx);
+    return NULL;
+  }
+  return ctx;
+}
+
+/* key-range shards: several GPUs and / or chunks streamed through the device memory (gt4_shard.c) */
+static int run_sharded (const Options *o, GT4ListFile *files, unsigned int wlen)
+{
+  GT4ShardJob job;
+  memset (&job, 0, sizeof job);
+  job.n_files = o->nfiles;
+  job.files = files;
+  job.word_length = wlen;
+  job.n_ranks = o->n_gpus >= 1 ? o->n_gpus : 1;
+  job.hbm_limit = o->hbm_limit;
+  job.auto_budget = wants_pipeline (o, files);
+  job.gather_rccl = o->gather_rccl;
+  job.debug = o->verbose;
+  job.prm = compare_params (o); /* gt4_shard.c reads prm.ops in pair mode only */
+  const int v = o->nfiles > 2 ? run_multi (o, files, wlen, &job, NULL, NULL) : 0;
+  if (o->nfiles == 2) print_lists_debug (o, files);
+  if (o->nfiles == 2 && job.prm.ops) {
+    job.mode = GT4_SHARD_PAIR;
+    job.out_mode = 0666;
+    char names[4][2048];
+    for (int s = 0; s < 4; s++) {
+      if (!((job.prm.ops >> s) & 1u) || o->countonly) continue;
+      output_name (o, wlen, s, names[s]);
+      job.out_name[s] = names[s];
+    }
+    GT4ShardResult res;
+    if (gt4_shard_run (&job, &res)) exit (1);
+    if (o->verbose) fprintf (stderr, "Sharded run: %u chunks over %d GPU(s)\n", res.n_chunks, job.n_ranks);
+    for (int s = 0; s < 4; s++) {
+      if (!((job.prm.ops >> s) & 1u)) continue;
+      if (o->countonly) print_totals (res.n_words[s], res.total_count[s]);
+      else if (o->debug && s >= 2) fprintf (stderr, "Renaming %s.tmp to %s\n", names[s], names[s]);
+    }
+  }
+  release (o, files, NULL, NULL);
+  return v;
+}
+
+/* everything in device memory at once: compare_wordmaps (reference :789-955) or the N-way passes */
+static int run_resident (const Options *o, GT4ListFile *files, unsigned int wlen, gt4hip_context *ctx)
+{
+  static gt4hip_list *lists[MAX_FILES];
+  int v = 0;
+  upload_inputs (o, ctx, files, wlen, lists);
+  if (o->nfiles > 2) {
+    v = run_multi (o, files, wlen, NULL, ctx, lists);
+  } else {
+    print_lists_debug (o, files);
+    const gt4hip_compare_params prm = compare_params (o);
     gt4hip_compare_result res;
     memset (&res, 0, sizeof res);
     if (prm.ops) {
@@ -686,106 +758,25 @@ int main (int argc, const char *argv[])
         fprintf (stderr, "Error: %s\n", gt4hip_last_error (ctx));
         exit (1);
       }
-      if (verbose) fprintf (stderr, "GPU merge kernel: %.3f ms (%llu tiles), device total %.3f ms\n", res.merge_kernel_ms,
-                          (unsigned long long) res.merge_tiles, res.device_ms);
+      if (o->verbose) fprintf (stderr, "GPU merge kernel: %.3f ms (%llu tiles), device total %.3f ms\n", res.merge_kernel_ms,
+                               (unsigned long long) res.merge_tiles, res.device_ms);
     }
-    if (countonly) {
-      for (int s = 0; s < 4; s++)
-        if ((prm.ops >> s) & 1u) fprintf (stdout, "NUnique\t%llu\nNTotal\t%llu\n", (unsigned long long) res.n_words[s], (unsigned long long) res.total_count[s]);
-    } else {
-      /* every requested output to its own "<name>.tmp" at once (the copy threads are dealt to the
-       * files), then header back-patch and rename in the reference's order (:907-953) */
-      char name[4][2048], tmp_name[4][2100];
-      GT4ListWriter w[4];
-      const gt4hip_list *wl[4];
-      uint64_t wfirst[4], wcount[4], woff[4];
-      int wfd[4], ws[4];
-      uint32_t nw = 0;
-      int bad = 0;
-      for (int s = 0; s < 4 && !bad; s++) {
-        if (!((prm.ops >> s) & 1u)) continue;
-        snprintf (name[s], sizeof name[s], "%s_%d_%s.list", outputname, wlen, SUFFIX[s]);
-        snprintf (tmp_name[s], sizeof tmp_name[s], "%s.tmp", name[s]);
-        /* fopen (.., "w") in the reference: mode 0666 minus umask */
-        if (gt4_listwriter_begin (&w[s], tmp_name[s], wlen, 0666)) {
-          fprintf (stderr, "Error: Cannot create output file %s\n", tmp_name[s]);
-          bad = 1;
-          break;
-        }
-        wl[nw] = res.out[s];
-        wfirst[nw] = 0;
-        wcount[nw] = res.n_words[s];
-        wfd[nw] = w[s].fd;
-        woff[nw] = 48;
-        ws[nw] = s;
-        nw++;
-      }
-      if (!bad && nw && gt4hip_lists_write_fd (ctx, nw, wl, wfirst, wcount, wfd, woff)) {
-        fprintf (stderr, "Error: writing the results failed: %s\n", gt4hip_last_error (ctx));
-        bad = 1;
-      }
-      for (uint32_t q = 0; q < nw; q++) {
-        const int s = ws[q];
-        if (bad) {
-          gt4_listwriter_abort (&w[s]);
-          unlink (tmp_name[s]);
-          continue;
-        }
-        if (debug && s >= 2) fprintf (stderr, "Renaming %s to %s\n", tmp_name[s], name[s]);
-        if (gt4_listwriter_finish (&w[s], res.n_words[s], res.total_count[s])) {
-          fprintf (stderr, "Error: writing %s failed: %s\n", tmp_name[s], strerror (errno));
-          unlink (tmp_name[s]);
-          bad = 1;
-        } else if (rename (tmp_name[s], name[s])) {
-          fprintf (stderr, "Error: Cannot rename %s to %s\n", tmp_name[s], name[s]);
-          bad = 1;
-        }
-        gt4hip_list_free (res.out[s]);
-      }
-      if (bad) exit (1);
-    }
-  } else {
-    /* ---- union_multi / intersect_multi (reference :366-422) */
-    for (int pass = 0; pass < 2; pass++) {
-      const int is_union = pass == 0;
-      if (is_union ? !find_union : !find_intrsec) continue;
-      gt4hip_multi_result res;
-      memset (&res, 0, sizeof res);
-      const double t_s = now_seconds ();
-      int rc = is_union ? gt4hip_union_multi (ctx, (const gt4hip_list *const *) lists, nfiles, cutoff, rule, count_override, countonly, &res)
-                        : gt4hip_intersect_multi (ctx, (const gt4hip_list *const *) lists, nfiles, cutoff, rule, count_override, countonly, &res);
-      const double t_e = now_seconds ();
-      if (rc == GT4HIP_ERULE) {
-        fprintf (stderr, "%s\n", gt4hip_last_error (ctx));
-        v = 1; /* the reference returns 1 from the merge and exits 1 without an output file */
-        continue;
-      }
-      if (rc) {
-        fprintf (stderr, "Error: %s\n", gt4hip_last_error (ctx));
-        exit (1);
-      }
-      v = 0;
-      if (debug) {
-        unsigned long long total = 0;
-        for (unsigned int f = 0; f < nfiles; f++) total += files[f].header.n_words;
-        fprintf (stderr, "Combined %u maps: input %llu (%.3f Mwords/s) output %llu (%.3f Mwords/s)\n", nfiles, is_union ? total : 0ull,
-                 (is_union ? total : 0ull) / (1000000 * (t_e - t_s)), (unsigned long long) res.n_words, res.n_words / (1000000 * (t_e - t_s)));
-      }
-      if (!countonly) {
-        char name[2048];
-        snprintf (name, sizeof name, "%s_%d_%s.list", outputname, wlen, is_union ? "union" : "intrsec");
-        /* creat (.., 0644) in the reference */
-        if (write_list_file (ctx, res.out, wlen, res.n_words, res.total_count, name, 0644)) exit (1);
-        gt4hip_list_free (res.out);
-      }
-      if (countonly || debug) fprintf (stdout, "NUnique\t%llu\nNTotal\t%llu\n", (unsigned long long) res.n_words, (unsigned long long) res.total_count);
-    }
+    if (write_outputs (o, ctx, wlen, prm.ops, &res)) exit (1);
   }
+  release (o, files, lists, ctx);
+  return v;
+}
 
-  for (unsigned int f = 0; f < nfiles; f++) {
-    gt4hip_list_free (lists[f]);
-    gt4_listfile_close (&files[f]);
-  }
-  gt4hip_destroy (ctx);
-  return v ? 1 : 0;
+int main (int argc, const char *argv[])
+{
+  static Options o;
+  static GT4ListFile files[MAX_FILES];
+  if (argc <= 1) print_help (1);
+  read_environment (&o);
+  parse_argv (argc, argv, &o); /* --gpus N overrides GT4HIP_GPUS */
+  const unsigned int wlen = open_inputs (&o, files);
+  validate (&o);
+  if (o.nmm) return run_mismatch (&o, files, wlen);
+  gt4hip_context *ctx = resident_context (&o, files); /* run_resident owns it from here and destroys it */
+  return ctx ? run_resident (&o, files, wlen, ctx) : run_sharded (&o, files, wlen);
 }

@@ -28,6 +28,7 @@
 #define _GNU_SOURCE
 #include <errno.h>
 #include <limits.h>
+#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -198,11 +199,24 @@ static void print_list_header (const Input *in)
   fprintf (stdout, "NTotal\t%llu\n", (unsigned long long) in->file.header.total_count);
 }
 
-/* the list in device memory, or exit 1 */
+/* p, or exit 1 after "Error: out of memory (<what>)"; the compiler checks `what` against its arguments */
+__attribute__ ((format (printf, 2, 3))) static void *or_oom (void *p, const char *what, ...)
+{
+  if (p) return p;
+  va_list ap;
+  va_start (ap, what);
+  fprintf (stderr, "Error: out of memory (");
+  vfprintf (stderr, what, ap);
+  fprintf (stderr, ")\n");
+  exit (1);
+}
+
+/* the list in device memory, or exit 1; `ctx` and `dev` may be NULL where the caller needs the object alone */
 static GT4HipWordList *to_device (const char *name, gt4hip_context **ctx, const gt4hip_list **dev)
 {
-  *ctx = gt4_hip_default_context ();
-  if (!*ctx) exit (1);
+  gt4hip_context *c = gt4_hip_default_context ();
+  if (!c) exit (1);
+  if (ctx) *ctx = c;
   GT4HipWordList *l = gt4_hip_word_list_new (name, GT4_VERSION_MAJOR);
   if (!l) {
     fprintf (stderr, "Error: %s could not be loaded into device memory\n", name);
@@ -228,11 +242,8 @@ static GT4HipWordList *to_device (const char *name, gt4hip_context **ctx, const 
 
 /* ------------------------------------------------------------------ statistics */
 
-static void print_median (const Input *in)
+static void print_median (const Input *in, gt4hip_context *ctx, const gt4hip_list *dev)
 {
-  gt4hip_context *ctx;
-  const gt4hip_list *dev;
-  GT4HipWordList *l = to_device (in->name, &ctx, &dev);
   const uint64_t num_words = in->file.header.n_words;
   uint32_t min, max, med, gmin, gmax;
   if (debug > 0) fprintf (stderr, "Finding min/max...");
@@ -265,34 +276,21 @@ static void print_median (const Input *in)
   }
   print_list_header (in);
   fprintf (stdout, "Min %u Max %u Median %u Average %.2f\n", gmin, gmax, med, (double) in->file.header.total_count / num_words);
-  gt4_hip_word_list_delete (l);
 }
 
-static void print_distro (const Input *in, unsigned int max)
+static void print_distro (gt4hip_context *ctx, const gt4hip_list *dev, unsigned int max)
 {
-  gt4hip_context *ctx;
-  const gt4hip_list *dev;
-  GT4HipWordList *l = to_device (in->name, &ctx, &dev);
-  uint64_t *d = (uint64_t *) calloc (max ? max : 1, 8);
-  if (!d) {
-    fprintf (stderr, "Error: out of memory (distribution of %u)\n", max);
-    exit (1);
-  }
+  uint64_t *d = (uint64_t *) or_oom (calloc (max ? max : 1, 8), "distribution of %u", max);
   CHK (ctx, gt4hip_list_count_histogram (ctx, dev, max, d));
   for (unsigned int i = 0; i < max; i++) fprintf (stdout, "%u\t%llu\n", i + 1, (unsigned long long) d[i]);
   free (d);
-  gt4_hip_word_list_delete (l);
 }
 
-static void print_gc (const Input *in)
+static void print_gc (const Input *in, gt4hip_context *ctx, const gt4hip_list *dev)
 {
-  gt4hip_context *ctx;
-  const gt4hip_list *dev;
-  GT4HipWordList *l = to_device (in->name, &ctx, &dev);
   uint64_t count = 0;
   CHK (ctx, gt4hip_list_gc (ctx, dev, &count));
   printf ("GC\t%g\n", (double) count / (in->file.header.total_count * in->file.header.word_length));
-  gt4_hip_word_list_delete (l);
 }
 
 static void print_full_map (const Input *in)
@@ -345,17 +343,6 @@ static unsigned int zipper_cb (uint64_t word, uint32_t count, void *data)
   gt4_word2string (b, word, g_wlen);
   fprintf (stdout, "%s\t%u\n", b, count);
   return 0;
-}
-
-static GT4HipWordList *word_list_or_die (const char *name)
-{
-  if (!gt4_hip_default_context ()) exit (1);
-  GT4HipWordList *l = gt4_hip_word_list_new (name, GT4_VERSION_MAJOR);
-  if (!l) {
-    fprintf (stderr, "Error: %s could not be loaded into device memory\n", name);
-    exit (1);
-  }
-  return l;
 }
 
 /* ------------------------------------------------------------------ batched lookups */
@@ -413,11 +400,7 @@ static void flush_batch (Searcher *s)
   if (n_hits > s->hit_capacity) {
     free (s->hits);
     s->hit_capacity = n_hits;
-    s->hits = (gt4hip_query_hit *) malloc ((size_t) n_hits * sizeof (gt4hip_query_hit));
-    if (!s->hits) {
-      fprintf (stderr, "Error: out of memory (%llu hits)\n", (unsigned long long) n_hits);
-      exit (1);
-    }
+    s->hits = (gt4hip_query_hit *) or_oom (malloc ((size_t) n_hits * sizeof (gt4hip_query_hit)), "%llu hits", (unsigned long long) n_hits);
     CHK (s->ctx, gt4hip_query_lookup_all (s->ctx, s->qindex, s->words, s->n, &s->prm, s->hits, s->hit_capacity, &n_hits));
   }
   OrderedHit *ord = NULL;
@@ -429,11 +412,7 @@ static void flush_batch (Searcher *s)
     const size_t m = (size_t) (e - h);
     if (m > ord_cap) {
       ord_cap = m * 2;
-      ord = (OrderedHit *) realloc (ord, ord_cap * sizeof *ord);
-      if (!ord) {
-        fprintf (stderr, "Error: out of memory (%llu hits of one query)\n", (unsigned long long) m);
-        exit (1);
-      }
+      ord = (OrderedHit *) or_oom (realloc (ord, ord_cap * sizeof *ord), "%llu hits of one query", (unsigned long long) m);
     }
     uint32_t sum = 0;
     for (size_t j = 0; j < m; j++) {
@@ -641,6 +620,31 @@ done:
 
 /* ------------------------------------------------------------------ main */
 
+/* the value of -min / -max; NULL at the end of argv: a warning, and the default stays */
+static void parse_frequency (const char *value, const char *which, unsigned int *freq)
+{
+  char *end;
+  if (!value) {
+    fprintf (stderr, "Warning: No %s frequency specified! Using the default value: %d.\n", which, *freq);
+    return;
+  }
+  *freq = (unsigned int) strtol (value, &end, 10);
+  if (*end != 0) {
+    fprintf (stderr, "Error: Invalid %s frequency: %s! Must be a positive integer.\n", which, value);
+    print_help (1);
+  }
+}
+
+/* The magic number of a list.  1: the file cannot be opened; a file shorter than the number has code 0 */
+static int list_code (const char *name, uint32_t *code)
+{
+  FILE *ifs = fopen (name, "r");
+  if (!ifs) return 1;
+  if (fread (code, 4, 1, ifs) != 1) *code = 0;
+  fclose (ifs);
+  return 0;
+}
+
 int main (int argc, const char *argv[])
 {
   int argidx, v = 0;
@@ -686,32 +690,8 @@ int main (int argc, const char *argv[])
       else nmm = val;
       break;
     }
-    case OPT_MIN:
-      if (!argv[argidx + 1]) {
-        fprintf (stderr, "Warning: No minimum frequency specified! Using the default value: %d.\n", minfreq);
-        argidx += 1;
-        continue;
-      }
-      minfreq = (unsigned int) strtol (argv[argidx + 1], &end, 10);
-      if (*end != 0) {
-        fprintf (stderr, "Error: Invalid minimum frequency: %s! Must be a positive integer.\n", argv[argidx + 1]);
-        print_help (1);
-      }
-      argidx += 1;
-      break;
-    case OPT_MAX:
-      if (!argv[argidx + 1]) {
-        fprintf (stderr, "Warning: No maximum frequency specified! Using the default value: %d.\n", maxfreq);
-        argidx += 1;
-        continue;
-      }
-      maxfreq = (unsigned int) strtol (argv[argidx + 1], &end, 10);
-      if (*end != 0) {
-        fprintf (stderr, "Error: Invalid maximum frequency: %s! Must be a positive integer.\n", argv[argidx + 1]);
-        print_help (1);
-      }
-      argidx += 1;
-      break;
+    case OPT_MIN: parse_frequency (argv[++argidx], "minimum", &minfreq); break;
+    case OPT_MAX: parse_frequency (argv[++argidx], "maximum", &maxfreq); break;
     case OPT_DEBUG: debug += 1; break;
     case OPT_ALL: printall = 1; break;
     case OPT_STATS: command = CMD_STATS; break;
@@ -763,13 +743,10 @@ int main (int argc, const char *argv[])
   for (unsigned int i = 0; i < n_lists; i++) {
     uint32_t code = 0;
     int ok = 0;
-    FILE *ifs = fopen (lists[i], "r");
-    if (!ifs) {
+    if (list_code (lists[i], &code)) {
       fprintf (stderr, "Cannot open list %s\n", lists[i]);
       exit (1);
     }
-    if (fread (&code, 4, 1, ifs) != 1) code = 0;
-    fclose (ifs);
     if (code == GT4_LIST_CODE_VALUE || code == GT4_INDEX_CODE_VALUE) {
       ok = !input_open (&maps[i], lists[i], code);
       if (ok && debug && code == GT4_LIST_CODE_VALUE) fprintf (stderr, "List %s loaded\n", lists[i]);
@@ -790,7 +767,7 @@ int main (int argc, const char *argv[])
   static Input query_input;
   if (querylistfilename) {
     uint32_t code = 0;
-    if (gt4_listfile_sniff (querylistfilename, &code) || (code != GT4_LIST_CODE_VALUE && code != GT4_INDEX_CODE_VALUE) ||
+    if (list_code (querylistfilename, &code) || (code != GT4_LIST_CODE_VALUE && code != GT4_INDEX_CODE_VALUE) ||
         input_open (&query_input, querylistfilename, code)) {
       fprintf (stderr, "Error: %s is invalid or corrupted\n", querylistfilename);
       invalid = 1;
@@ -805,14 +782,16 @@ int main (int argc, const char *argv[])
   if (command == CMD_STATS) {
     for (unsigned int i = 0; i < n_lists; i++) print_list_header (&maps[i]);
     exit (0);
-  } else if (command == CMD_MEDIAN) {
-    for (unsigned int i = 0; i < n_lists; i++) print_median (&maps[i]);
-    exit (0);
-  } else if (command == CMD_DISTRO) {
-    for (unsigned int i = 0; i < n_lists; i++) print_distro (&maps[i], distro + 1);
-    exit (0);
-  } else if (command == CMD_GC) {
-    for (unsigned int i = 0; i < n_lists; i++) print_gc (&maps[i]);
+  } else if (command == CMD_MEDIAN || command == CMD_DISTRO || command == CMD_GC) {
+    for (unsigned int i = 0; i < n_lists; i++) {
+      gt4hip_context *ctx;
+      const gt4hip_list *dev;
+      GT4HipWordList *l = to_device (lists[i], &ctx, &dev);
+      if (command == CMD_MEDIAN) print_median (&maps[i], ctx, dev);
+      else if (command == CMD_DISTRO) print_distro (ctx, dev, distro + 1);
+      else print_gc (&maps[i], ctx, dev);
+      gt4_hip_word_list_delete (l);
+    }
     exit (0);
   }
 
@@ -828,7 +807,7 @@ int main (int argc, const char *argv[])
         fprintf (stdout, "\n");
       }
       static GT4HipWordList *objs[MAX_LISTS];
-      for (unsigned int i = 0; i < n_lists; i++) objs[i] = word_list_or_die (lists[i]);
+      for (unsigned int i = 0; i < n_lists; i++) objs[i] = to_device (lists[i], NULL, NULL);
       const unsigned int r = is_union ? gt4_is_union (objs, n_lists, dump_cb, NULL) : gt4_union (objs, n_lists, dump_cb, NULL);
       if (r) {
         fprintf (stderr, "Error: the union of the lists failed (%u)\n", r);
@@ -847,8 +826,8 @@ int main (int argc, const char *argv[])
       exit (1);
     }
     static GT4HipWordList *objs[MAX_LISTS];
-    GT4HipWordList *q = word_list_or_die (querylistfilename);
-    for (unsigned int i = 0; i < n_lists; i++) objs[i] = word_list_or_die (lists[i]);
+    GT4HipWordList *q = to_device (querylistfilename, NULL, NULL);
+    for (unsigned int i = 0; i < n_lists; i++) objs[i] = to_device (lists[i], NULL, NULL);
     const unsigned int result = gt4_search_lists_multi (q, objs, n_lists, multi_cb, NULL);
     if (multi_open) fputc ('\n', stdout);
     exit ((int) result);
@@ -865,8 +844,8 @@ int main (int argc, const char *argv[])
 
   /* one list against a query list without mismatches: the zipper (min / max / --all do not apply, as in the reference) */
   if (!querystring && !queryfilename && !seqfilename && querylistfilename && !nmm && !words_only) {
-    GT4HipWordList *l = word_list_or_die (lists[0]);
-    GT4HipWordList *q = word_list_or_die (querylistfilename);
+    GT4HipWordList *l = to_device (lists[0], NULL, NULL);
+    GT4HipWordList *q = to_device (querylistfilename, NULL, NULL);
     const unsigned int r = gt4_search_list_zipper (l, q, zipper_cb, NULL);
     if (r) {
       fprintf (stderr, "Error: the search of %s in %s failed (%u)\n", querylistfilename, lists[0], r);
@@ -884,15 +863,11 @@ int main (int argc, const char *argv[])
   s.min_freq = minfreq;
   s.max_freq = maxfreq;
   s.print_all = printall;
-  s.words = (uint64_t *) malloc ((size_t) QUERY_BATCH * 8);
-  s.values = (uint32_t *) malloc ((size_t) QUERY_BATCH * 4);
-  s.found = (uint8_t *) malloc (QUERY_BATCH);
+  s.words = (uint64_t *) or_oom (malloc ((size_t) QUERY_BATCH * 8), "query batch");
+  s.values = (uint32_t *) or_oom (malloc ((size_t) QUERY_BATCH * 4), "query batch");
+  s.found = (uint8_t *) or_oom (malloc (QUERY_BATCH), "query batch");
   s.hit_capacity = printall ? QUERY_BATCH : 0;
-  s.hits = printall ? (gt4hip_query_hit *) malloc ((size_t) s.hit_capacity * sizeof (gt4hip_query_hit)) : NULL;
-  if (!s.words || !s.values || !s.found || (printall && !s.hits)) {
-    fprintf (stderr, "Error: out of memory (query batch)\n");
-    exit (1);
-  }
+  s.hits = printall ? (gt4hip_query_hit *) or_oom (malloc ((size_t) s.hit_capacity * sizeof (gt4hip_query_hit)), "query batch") : NULL;
   GT4HipWordList *l = NULL;
   if (!words_only) {
     const gt4hip_list *dev = NULL;

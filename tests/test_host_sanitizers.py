@@ -2,8 +2,9 @@
 ThreadSanitizer, WITHOUT a GPU: csrc/gt4_glistcompare_cli.c, gt4_shard.c (key-range plan, fork, barriers,
 semaphore pipeline, shared totals, pwrite extents, header back-patching, failure paths) and
 gt4_listfile.c linked against tests/harness/gt4hip_stub.c -- a CPU stand-in for the device layer that
-runs the set operations through the CPU oracle.  The golden reference invocations are replayed with
-one, two and three worker processes and through 1-KiB chunks: exit code, stdout, stderr and every output
+runs the set operations through the CPU oracle.  The golden reference invocations are replayed resident (no worker: the
+tool's own upload loop and output writer), with one, two and three worker processes and through 1-KiB
+chunks: exit code, stdout, stderr and every output
 file must be the reference's bytes, and no sanitizer may report anything.  Failures injected into one
 worker (context creation, the merge, the gather buffer, the collective itself) must end the whole run
 with exit code 1, no temporaries and no hang.  (Next 8; ADVICE round 2 on
@@ -49,8 +50,9 @@ def workdir():
 
 
 def _run(binary, argv, cwd, env_extra, timeout=120):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=97", UBSAN_OPTIONS="print_stacktrace=1:exitcode=98",
-               TSAN_OPTIONS="exitcode=99:halt_on_error=0", **env_extra)
+    # a mode is env_extra and nothing else: a GT4HIP_* variable of the caller's must not turn "resident" into a shard run
+    env = dict({k: v for k, v in os.environ.items() if not k.startswith("GT4HIP_")}, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=97",
+               UBSAN_OPTIONS="print_stacktrace=1:exitcode=98", TSAN_OPTIONS="exitcode=99:halt_on_error=0", **env_extra)
     cmd = [binary] + argv
     if binary.endswith("_tsan"):
         # ThreadSanitizer (gcc 11) fits the program into a fixed memory layout: on kernels that randomise mappings with
@@ -74,7 +76,8 @@ def _clean(err):
     return err
 
 
-MODES = [("one worker", {"GT4HIP_GPUS": "1"}),
+MODES = [("resident", {}),  # no GT4HIP_GPUS: everything in the stand-in's "device memory" at once, the tool's own writer
+         ("one worker", {"GT4HIP_GPUS": "1"}),
          ("1 KiB chunks", {"GT4HIP_GPUS": "1", "GT4HIP_HBM_LIMIT": "1024"}),
          ("two workers", {"GT4HIP_GPUS": "2", "GT4HIP_STUB_DEVICES": "2", "GT4HIP_HBM_LIMIT": "4096"}),
          ("three workers, gathered", {"GT4HIP_GPUS": "3", "GT4HIP_STUB_DEVICES": "3", "GT4HIP_HBM_LIMIT": "2048", "GT4HIP_GATHER": "rccl"})]
