@@ -1,5 +1,6 @@
-/* gt4hip_host.h -- host-side internals shared by the C-ABI implementation files
- * (gt4hip_api.hip, gt4hip_io.hip, gt4hip_comm.hip, gt4hip_nway.hip). */
+/* gt4hip_host.h -- host-side internals shared by the C-ABI implementation files: the context and list objects, and
+ * what the units of the library host (gt4hip_api.hip, gt4hip_pair.hip, gt4hip_multi.hip, gt4hip_table.hip,
+ * gt4hip_nway.hip) and gt4hip_io / _comm / _sort / _mismatch / _query.hip call in one another. */
 #ifndef GT4HIP_HOST_H
 #define GT4HIP_HOST_H
 
@@ -7,6 +8,7 @@
 #include "gt4hip_internal.h"
 
 #include <stddef.h>
+#include <algorithm>
 #include <utility>
 #include <vector>
 
@@ -81,15 +83,78 @@ struct gt4hip_list {
   int owns;
 };
 
-
+/* what only the library's own translation units call is kept out of its exported symbols */
+#define GT4HIP_LOCAL __attribute__ ((visibility ("hidden")))
+/* ---- gt4hip_api.hip */
 int gt4hip_fail (gt4hip_context *ctx, int code, const char *fmt, ...);
 /* every device allocation of the library: gives the pooled blocks back and retries when the driver is out of memory */
 hipError_t gt4hip_dev_alloc (gt4hip_context *ctx, void **p, size_t bytes);
+/* a workspace buffer of the context grown to `need` bytes and an eighth: the stream is drained before the old one goes */
+GT4HIP_LOCAL int gt4hip_grow (gt4hip_context *ctx, void **p, size_t *have, size_t need);
 int gt4hip_list_new (gt4hip_context *ctx, uint64_t capacity, uint32_t word_length, gt4hip_list **out);
-void gt4hip_io_destroy (gt4hip_context *ctx);
+/* a list of no records that owns nothing (the second operand where a call has only one) */
+GT4HIP_LOCAL gt4hip_list gt4hip_empty_list (gt4hip_context *ctx, uint32_t word_length);
+/* device -> host copy of `bytes` on the context's stream, then the stream is drained; fails with "<what>: <HIP error>" */
+GT4HIP_LOCAL int gt4hip_read_back (gt4hip_context *ctx, void *host, const void *dev, size_t bytes, const char *what);
+/* the first n u64 of ctx->scratch -> ctx->scratch_host, as above */
+GT4HIP_LOCAL inline int gt4hip_read_scratch (gt4hip_context *ctx, unsigned n) { return gt4hip_read_back (ctx, ctx->scratch_host, ctx->scratch, n * 8, "reading the scratch words back failed"); }
+
+/* Device lists that exist for one call: what the owner still holds when it goes out of scope is freed, in the order adopted
+ * (the block pool hands out the best-fitting block and evicts the oldest: that order decides what the next call reuses). */
+struct GT4HIP_LOCAL TempLists {
+  std::vector<gt4hip_list *> lists;
+  TempLists () {}
+  TempLists (const TempLists &) = delete;
+  void operator= (const TempLists &) = delete;
+  ~TempLists () { clear (); }
+  gt4hip_list *adopt (gt4hip_list *l) { return lists.push_back (l), l; }
+  void release () { lists.clear (); } /* (they are the caller's now) */
+  void clear ()
+  {
+    for (gt4hip_list *l : lists) gt4hip_list_free (l);
+    lists.clear ();
+  }
+  /* A level of a merge tree is complete (`level`: its results, `next`: what the level above reads): the lists of the level
+   * below are freed, except those carried over as they are; this owner then holds `level`'s lists followed by the carried. */
+  void next_level (TempLists &level, const std::vector<const gt4hip_list *> &next)
+  {
+    for (gt4hip_list *l : lists) {
+      if (std::find (next.begin (), next.end (), l) != next.end ()) level.lists.push_back (l);
+      else gt4hip_list_free (l);
+    }
+    lists.clear ();
+    lists.swap (level.lists);
+  }
+};
+
+/* *out = the caller's list `given` if it holds `need` records (an error if not; `s`: the output stream named in the
+ * text, < 0 where the call has one output), else a new list of that capacity, which `made` then owns */
+GT4HIP_LOCAL int gt4hip_output_list (gt4hip_context *ctx, int s, gt4hip_list *given, uint64_t need, uint32_t word_length, TempLists &made, gt4hip_list **out);
+
+/* ---- gt4hip_pair.hip */
+struct PairRun {
+  uint64_t n_words[4];
+  uint64_t total_count[4];
+  double merge_ms, device_ms;
+  uint64_t tiles;
+};
+/* the merge of (A, B) with fully resolved kernel parameters, waited for; dst[s]: non-null for every requested stream unless count_only */
+GT4HIP_LOCAL int gt4hip_run_pair (gt4hip_context *ctx, const uint32_t *A, uint64_t nA, const uint32_t *B, uint64_t nB, const gt4::PairParams &p,
+                                  bool count_only, uint32_t *const dst[4], PairRun *run, bool force_two_pass = false);
+/* The same on lists: out[s] is the caller's list or NULL (then one of the worst-case size is made and returned there);
+ * sets the outputs' n_words.  Nothing is made, and out[] is as it was, when the call fails. */
+GT4HIP_LOCAL int gt4hip_pair_with_outputs (gt4hip_context *ctx, const gt4hip_list *a, const gt4hip_list *b, const gt4::PairParams &p, bool count_only,
+                                           gt4hip_list *out[4], PairRun *run);
+/* the parameters of a step of an N-way operation or a table column: one stream, one rule for it, no subtract */
+GT4HIP_LOCAL gt4::PairParams gt4hip_nway_params (uint32_t op_bit, uint32_t rule, uint32_t cutoff, uint32_t ovr, uint32_t filter);
+/* bytes of the chained scan's descriptors (gt4hip_device.h): agg u32[4][rows * 64], carry u64[4][rows + 1], rowsum u64[4][rows] */
+GT4HIP_LOCAL size_t gt4hip_lookback_desc_bytes (uint64_t tiles);
+
+/* ---- gt4hip_nway.hip, gt4hip_table.hip, gt4hip_io.hip */
 int gt4hip_nway_union (gt4hip_context *ctx, const gt4hip_list *const lists[], uint32_t k, uint32_t rule, uint32_t cutoff, uint32_t ovr,
-                       uint32_t filter, bool count_only, gt4hip_list *out, uint64_t *n_words, uint64_t *total_count, double *device_ms,
-                       int *used);
+                       uint32_t filter, bool count_only, gt4hip_list *out, uint64_t *n_words, uint64_t *total_count, double *device_ms, int *used);
+int gt4hip_nway_table (gt4hip_context *ctx, const gt4hip_list *const lists[], uint32_t k, const uint32_t cols[], gt4hip_count_table *table, int probe,
+                       int presence, int *used);
 int gt4hip_block_alloc (gt4hip_context *ctx, size_t bytes, void **dev, void **owner);
 void gt4hip_block_free (void *owner);
 int gt4hip_table_alloc (gt4hip_context *ctx, gt4hip_count_table *table, uint64_t n, uint32_t n_lists);
@@ -98,8 +163,7 @@ int gt4hip_table_alloc (gt4hip_context *ctx, gt4hip_count_table *table, uint64_t
 int gt4hip_table_set_ragged (gt4hip_context *ctx, gt4hip_count_table *table, uint64_t tiles);
 void *gt4hip_table_compact_bases (gt4hip_count_table *table);
 void *gt4hip_table_padded_bases (gt4hip_count_table *table);
-int gt4hip_nway_table (gt4hip_context *ctx, const gt4hip_list *const lists[], uint32_t k, const uint32_t cols[], gt4hip_count_table *table, int probe,
-                       int presence, int *used);
+void gt4hip_io_destroy (gt4hip_context *ctx);
 int gt4hip_io_download (gt4hip_context *ctx, const void *dev, void *host, size_t bytes);
 
 #define HIPCHK(ctx, call)                                                                               \

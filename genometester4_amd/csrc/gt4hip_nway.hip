@@ -67,6 +67,7 @@
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 #define GT4_KM 8
 #define GT4_KM_NS km8

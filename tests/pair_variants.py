@@ -1,52 +1,51 @@
 """Which k_pair_merge<NT, IPT, MODE, OPS, FAST, OPSET> instantiation a call launches: a Python restatement of the host's
 selection, and the matrix of calls tests/test_pair_variants.py runs so that every launchable instantiation is reached.
 
-The restated C++ (genometester4_amd/csrc):
-  gt4hip_api.hip      gt4hip_compare :774 (per-stream default rules :785-790), nway_params :814,
-                      run_pair :606 (ops 8 -> 4 on (B, A) :608-621, shorter list first for an intersection :623-631,
-                      geometry :638, "dynamic" :652, "scan_group" :653, two-pass :656 / :663 / :679-687),
-                      gt4hip_union_multi :1050 (pairwise tree :1087-1117), gt4hip_intersect_multi :1122 (chain :1143-1169),
-                      table_column_by_union :1183, gt4hip_probe_table_ex :1434
-  gt4hip_kernels.hip  merge_ipt :218, fast_variant :1284, launch_pair_merge_ops :1304 (OPSET :1312), ops_class :1365,
-                      launch_pair_merge :1398
+The restated C++ (genometester4_amd/csrc), by file: function:
+  gt4hip_pair.hip     gt4hip_compare (per-stream default rules), gt4hip_run_pair (ops 8 -> 4 on (B, A), shorter list
+                      first for an intersection, geometry, "dynamic", "scan_group", the two-pass path)
+  gt4hip_multi.hip    gt4hip_nway_params, gt4hip_union_multi (the pairwise tree), gt4hip_intersect_multi (the chain)
+  gt4hip_table.hip    table_column_by_union, gt4hip_probe_table_ex
+  gt4hip_kernels.hip  merge_ipt, fast_variant, launch_pair_merge_ops (OPSET), ops_class, merge_tile_records,
+                      launch_pair_merge
 tests/test_pair_variant_map.py ties this map to the instantiations the compiler emits.
 No GPU and no library are needed to import this module."""
 from __future__ import annotations
 
 from collections import namedtuple
 
-MODE_COUNT, MODE_LOOKBACK, MODE_OFFSETS = 0, 1, 2        # gt4hip_internal.h:60-62
-FILTER_REFERENCE, FILTER_RAW, FILTER_RESULT = 0, 1, 2    # gt4hip_internal.h:26-28
+MODE_COUNT, MODE_LOOKBACK, MODE_OFFSETS = 0, 1, 2        # gt4hip_internal.h: enum MergeMode
+FILTER_REFERENCE, FILTER_RAW, FILTER_RESULT = 0, 1, 2    # gt4hip_internal.h: enum Filter
 RULE_DEFAULT, RULE_ADD, RULE_SUBTRACT, RULE_MIN, RULE_MAX, RULE_FIRST, RULE_SECOND, RULE_NUMBER = range(8)
-RULE_MINZ = 8                                            # gt4hip_internal.h:22
+RULE_MINZ = 8                                            # gt4hip_internal.h: RULE_MINZ
 OP_UNION, OP_INTRSEC, OP_DIFF1, OP_DIFF2 = 1, 2, 4, 8
 
-GT4_IPT_UNION, GT4_IPT_INTERSECT, GT4_IPT_INTERSECT_SMALL, MERGE_VT = 4, 6, 4, 4   # gt4hip_kernels.hip:25-27, gt4hip_internal.h:71
-MERGE_TILE_SLACK = 64                                                             # gt4hip_internal.h:72
+GT4_IPT_UNION, GT4_IPT_INTERSECT, GT4_IPT_INTERSECT_SMALL, MERGE_VT = 4, 6, 4, 4   # gt4hip_kernels.hip: GT4_IPT_*, gt4hip_internal.h: MERGE_VT
+MERGE_TILE_SLACK = 64                                                             # gt4hip_internal.h: MERGE_TILE_SLACK
 
 # PairParams, reduced to what the selection reads
 Params = namedtuple("Params", "ops rule cutoff subtract filter")
 
 
 def compare_params(ops, rule=RULE_DEFAULT, cutoff=1, subtract=0):
-    """gt4hip_compare (gt4hip_api.hip:785-797): DEFAULT resolves per stream to ADD / MIN / SUBTRACT / SUBTRACT"""
+    """gt4hip_pair.hip: gt4hip_compare: DEFAULT resolves per stream to ADD / MIN / SUBTRACT / SUBTRACT"""
     r = rule
     return Params(ops, (r or RULE_ADD, r or RULE_MIN, r or RULE_SUBTRACT, r or RULE_SUBTRACT), cutoff, 1 if subtract else 0,
                   FILTER_REFERENCE)
 
 
 def nway_params(op_bit, rule, cutoff, filt):
-    """nway_params (gt4hip_api.hip:814): one rule for every stream, no -du"""
+    """gt4hip_multi.hip: gt4hip_nway_params: one rule for every stream, no -du"""
     return Params(op_bit, (rule,) * 4, cutoff, 0, filt)
 
 
 def ops_class(ops):
-    """gt4hip_kernels.hip:1365"""
+    """gt4hip_kernels.hip: ops_class"""
     return ops if ops in (1, 2, 4) else 0
 
 
 def merge_ipt(nt, cls):
-    """gt4hip_kernels.hip:218"""
+    """gt4hip_kernels.hip: merge_ipt"""
     if nt == 1024 and cls == 2:
         return GT4_IPT_INTERSECT
     if nt == 1024 and cls == 1:
@@ -57,13 +56,13 @@ def merge_ipt(nt, cls):
 
 
 def merge_tile_records(geom, ops):
-    """merge_tile_records (gt4hip_kernels.hip:1367)"""
+    """gt4hip_kernels.hip: merge_tile_records"""
     nt = 1024 if geom else 512
     return nt * merge_ipt(nt, ops_class(ops)) - MERGE_TILE_SLACK
 
 
 def fast_variant(cls, p):
-    """gt4hip_kernels.hip:1284-1301"""
+    """gt4hip_kernels.hip: fast_variant"""
     fast = 0
     if p.filter == FILTER_REFERENCE:
         if cls == 1 and p.rule[0] == RULE_ADD:
@@ -84,14 +83,14 @@ def fast_variant(cls, p):
 
 
 def kernel_name(nt, mode, p):
-    """launch_pair_merge (gt4hip_kernels.hip:1398: the class from p.ops) -> launch_pair_merge_ops (:1304-1347)"""
+    """gt4hip_kernels.hip: launch_pair_merge (the class from p.ops) -> launch_pair_merge_ops"""
     cls = ops_class(p.ops)
     fast = fast_variant(cls, p)
     ipt = merge_ipt(nt, cls)
-    # :1312 the fixed output sets: any-combination kernel, FAST 1, ops 3 / 5 / 15, and (512, COUNT) or (1024, not COUNT)
+    # launch_pair_merge_ops, the fixed output sets: any-combination kernel, FAST 1, ops 3 / 5 / 15, and (512, COUNT) or (1024, not COUNT)
     if cls == 0 and fast == 1 and p.ops in (3, 5, 15) and (nt == 512 if mode == MODE_COUNT else nt == 1024):
         return "k_pair_merge<%d, %d, %d, 0, 1, %d>" % (nt, ipt, mode, p.ops)
-    # :1326 F2 / F3 exist for the union and the intersection only; any other FAST falls back to 0
+    # (the same) F2 / F3 exist for the union and the intersection only; any other FAST falls back to 0
     if fast in (2, 3) and cls not in (1, 2):
         fast = 0
     return "k_pair_merge<%d, %d, %d, %d, %d, 0>" % (nt, ipt, mode, cls, fast)
@@ -101,28 +100,28 @@ Launch = namedtuple("Launch", "names swapped tiles")
 
 
 def run_pair(p, nA, nB, count_only=False, two_pass=False, geom=None):
-    """run_pair (gt4hip_api.hip:606-687): the names launched (one, or two on the two-pass path), whether (A, B) went in
+    """gt4hip_pair.hip: gt4hip_run_pair: the names launched (one, or two on the two-pass path), whether (A, B) went in
     swapped, and the number of merge tiles.  geom: None (automatic), 0 or 1 (options "geom0" / "geom1")."""
     swapped = False
-    if p.ops == 8:  # :608-621 the second complement alone is the first complement of (B, A)
+    if p.ops == 8:  # the second complement alone is the first complement of (B, A)
         rule = list(p.rule)
         rule[2] = p.rule[3]
         p = p._replace(ops=4, rule=tuple(rule), subtract=0)
         nA, nB, swapped = nB, nA, True
-    if p.ops == 2 and nA > nB and p.rule[1] not in (RULE_SUBTRACT, RULE_MINZ):  # :623-631
+    if p.ops == 2 and nA > nB and p.rule[1] not in (RULE_SUBTRACT, RULE_MINZ):  # shorter list first
         rule = list(p.rule)
         rule[1] = {RULE_FIRST: RULE_SECOND, RULE_SECOND: RULE_FIRST}.get(rule[1], rule[1])
         p = p._replace(rule=tuple(rule))
         nA, nB, swapped = nB, nA, not swapped
     if not nA + nB or not p.ops:
         return Launch([], swapped, 0)
-    g = (0 if count_only else 1) if geom is None else geom                        # :638
+    g = (0 if count_only else 1) if geom is None else geom                        # geometry
     tr = merge_tile_records(g, p.ops)
     tiles = (nA + nB + tr - 1) // tr
     nt = 1024 if g else 512
     if count_only:
         names = [kernel_name(nt, MODE_COUNT, p)]
-    elif two_pass:                                                                 # :656, :681-685
+    elif two_pass:                                                                 # count, scan, write
         names = [kernel_name(nt, MODE_COUNT, p), kernel_name(nt, MODE_OFFSETS, p)]
     else:
         names = [kernel_name(nt, MODE_LOOKBACK, p)]
@@ -135,14 +134,14 @@ def compare_launches(ops, rule=0, cutoff=1, subtract=0, nA=1, nB=1, **path):
 
 def union_multi_steps(sizes, rule=RULE_DEFAULT, cutoff=1):
     """gt4hip_union_multi by the pairwise tree (option "kway" = 0, or fewer than three non-empty lists):
-    [(Params, nA, nB, final)]; the inner levels run FILTER_RAW (:1087), the last merge FILTER_RESULT (:1115).
+    [(Params, nA, nB, final)]; the inner levels run FILTER_RAW, the last merge (nway_final) FILTER_RESULT.
     Sizes of intermediate results are upper bounds (the union's size is at most the sum)."""
-    rule = RULE_ADD if rule == RULE_DEFAULT else rule                              # :1055
-    work = [n for n in sizes if n]                                                 # :1068 empty lists dropped
+    rule = RULE_ADD if rule == RULE_DEFAULT else rule                              # DEFAULT resolves to ADD
+    work = [n for n in sizes if n]                                                 # empty lists dropped
     steps = []
     if not work:
         return steps
-    while len(work) > 2:                                                           # :1088-1112
+    while len(work) > 2:                                                           # the pairwise tree
         nxt = []
         for i in range(0, len(work) - 1, 2):
             steps.append((nway_params(OP_UNION, rule, cutoff, FILTER_RAW), work[i], work[i + 1], False))
@@ -155,10 +154,10 @@ def union_multi_steps(sizes, rule=RULE_DEFAULT, cutoff=1):
 
 
 def intersect_multi_steps(sizes, rule=RULE_DEFAULT, cutoff=1):
-    """gt4hip_intersect_multi: the left-to-right chain, MIN as RULE_MINZ (:1143), inner steps FILTER_RAW (:1159),
-    the last FILTER_RESULT (:1169); one list: a union with an empty list under FIRST / NUMBER (:1144-1151)."""
-    rule = RULE_MIN if rule == RULE_DEFAULT else rule                              # :1127
-    if not sizes or any(n == 0 for n in sizes):                                    # :1140
+    """gt4hip_intersect_multi: the left-to-right chain, MIN as RULE_MINZ, inner steps FILTER_RAW,
+    the last FILTER_RESULT; one list: a union with an empty list under FIRST / NUMBER."""
+    rule = RULE_MIN if rule == RULE_DEFAULT else rule                              # DEFAULT resolves to MIN
+    if not sizes or any(n == 0 for n in sizes):                                    # an empty list: empty_result
         return []
     krule = RULE_MINZ if rule == RULE_MIN else rule
     if len(sizes) == 1:
@@ -175,8 +174,8 @@ def intersect_multi_steps(sizes, rule=RULE_DEFAULT, cutoff=1):
 
 def union_table_steps(n_keys, sizes, presence=False):
     """The count tables by merges (option "kway" = 0): gt4hip_probe_table_ex intersects the base with every list under
-    SECOND (NUMBER for presence), FILTER_RAW (:1434), then table_column_by_union takes union (keys, L_j) under SECOND,
-    FILTER_RAW (:1183)."""
+    SECOND (NUMBER for presence), FILTER_RAW, then table_column_by_union takes union (keys, L_j) under SECOND,
+    FILTER_RAW."""
     steps = []
     for n in sizes:
         steps.append((nway_params(OP_INTRSEC, RULE_NUMBER if presence else RULE_SECOND, 0, FILTER_RAW), n_keys, n, False))

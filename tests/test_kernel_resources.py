@@ -4,6 +4,7 @@ gfx950 without a GPU; the table comes from -Rpass-analysis=kernel-resource-usage
 (tools/kernel_resources.py)."""
 import concurrent.futures
 import os
+import re
 import shutil
 import sys
 
@@ -12,7 +13,20 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-SOURCES = ["gt4hip_kernels.hip", "gt4hip_nway.hip", "gt4hip_sort.hip", "gt4hip_api.hip"]  # every file of csrc that holds a __global__ function
+CSRC = os.path.join(ROOT, "genometester4_amd", "csrc")
+
+
+def _holds_kernel(name, seen=None):
+    """does csrc/<name>, or a header of csrc it includes (by name or by a GT4_KM_ROWS-like macro), define a __global__ function?"""
+    seen = set() if seen is None else seen
+    if name in seen or not os.path.exists(os.path.join(CSRC, name)):
+        return False
+    seen.add(name)
+    text = open(os.path.join(CSRC, name)).read()
+    return "__global__" in text or any(_holds_kernel(h, seen) for h in re.findall(r'"(gt4hip_\w+\.h)"', text))
+
+
+SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip") and _holds_kernel(f))  # every file of csrc that holds a __global__ function
 
 
 @pytest.fixture(scope="module")
