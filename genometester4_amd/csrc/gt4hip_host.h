@@ -69,6 +69,9 @@ struct gt4hip_context {
   int last_multi_one_pass;   /* the last gt4hip_union_multi was done by the one-pass tile kernel (counter "nway_one_pass") */
   gt4hip_io *io;            /* file <-> HBM staging (gt4hip_io.hip), NULL until first used */
   gt4hip_mismatch_stats mm_stats; /* the last gt4hip_compare_mismatch (gt4hip_mismatch.hip) */
+  uint64_t mm_wide_levels;      /* counter "mm_wide_levels": its levels, both sides added, that ran the 64-bit unranking (k_level<true>) */
+  uint64_t mm_unskipped_levels; /* counter "mm_unskipped_levels": ... that ran without the early exit (early == 0) */
+  uint64_t query_wide;          /* counter "query_wide": the last gt4hip_query_lookup launched k_query<true> */
   char err[512];
   char info[256];
 };

@@ -298,7 +298,10 @@ int run_level (gt4hip_context *ctx, Side &s, u32 k, u32 c, u32 cutoff, u32 subtr
     L.stride_w = stride / L.n_var;
     L.stride_r = stride % L.n_var;
     HIPCHK (ctx, hipMemsetAsync (ctx->scratch + 2, 0, 8, ctx->stream));
-    if (L.n_var + stride < 0xffffffffull) hipLaunchKernelGGL (k_level<false>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, L, ctx->scratch + 2);
+    const bool wide = !(L.n_var + stride < 0xffffffffull);
+    ctx->mm_wide_levels += wide;
+    ctx->mm_unskipped_levels += !L.early;
+    if (!wide) hipLaunchKernelGGL (k_level<false>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, L, ctx->scratch + 2);
     else hipLaunchKernelGGL (k_level<true>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, L, ctx->scratch + 2);
     HIPCHK (ctx, hipGetLastError ());
     HIPCHK (ctx, hipMemcpyAsync (ctx->scratch_host + 2, ctx->scratch + 2, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -345,6 +348,7 @@ extern "C" int gt4hip_compare_mismatch (gt4hip_context *ctx, const gt4hip_list *
 
   gt4hip_mismatch_stats st;
   memset (&st, 0, sizeof st);
+  ctx->mm_wide_levels = ctx->mm_unskipped_levels = 0;
   Blocks blk;
   hipEvent_t e0 = NULL, e1 = NULL, e2 = NULL;
   gt4hip_list *made[4] = { NULL, NULL, NULL, NULL };

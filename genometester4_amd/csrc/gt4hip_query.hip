@@ -423,6 +423,7 @@ extern "C" int gt4hip_query_lookup (gt4hip_context *ctx, gt4hip_query_index *qi,
   int rc = check_params (ctx, "gt4hip_query_lookup", qi, prm);
   if (rc) return rc;
   qi->last_ms = 0;
+  ctx->query_wide = 0;
   if (!n) return GT4HIP_OK;
   HIPCHK (ctx, hipSetDevice (ctx->device));
   Blocks blk;
@@ -446,7 +447,8 @@ extern "C" int gt4hip_query_lookup (gt4hip_context *ctx, gt4hip_query_index *qi,
     const u64 stride = (u64) grid * MM_THREADS;
     Q.stride_w = stride / Q.n_var;
     Q.stride_r = stride % Q.n_var;
-    if (Q.n_var + stride < 0xffffffffull) hipLaunchKernelGGL (k_query<false>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, Q, d_values);
+    ctx->query_wide = !(Q.n_var + stride < 0xffffffffull);
+    if (!ctx->query_wide) hipLaunchKernelGGL (k_query<false>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, Q, d_values);
     else hipLaunchKernelGGL (k_query<true>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, Q, d_values);
     HIPCHK (ctx, hipGetLastError ());
     hipLaunchKernelGGL (k_query_found, dim3 (grid_for (ctx, n, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, d_values, n, d_found);

@@ -444,7 +444,10 @@ int gt4hip_set_option (gt4hip_context *ctx, const char *name, int64_t value);
  * partitions repeated with fewer samples per tile because a tile would not have fit LDS;
  * "nway_kernel_us", "nway_tiles": the last N-way call's tile kernel; "nway_one_pass": 1 when the last
  * gt4hip_union_multi took the one-pass tile kernel, 0 when it took the pairwise tree; "sort_us", "fold_us", "table_us":
- * the last gt4hip_device_words_to_list / gt4hip_union_table call. */
+ * the last gt4hip_device_words_to_list / gt4hip_union_table call;
+ * "query_wide": 1 when the context's last gt4hip_query_lookup ran the kernel with 64-bit variant ranks, else 0;
+ * "mm_wide_levels": levels of the last gt4hip_compare_mismatch, both tables added, run with 64-bit variant ranks;
+ * "mm_unskipped_levels": levels of it run without the early exit of decided words (more than 2^32 - 1 variants a word, no subtract). */
 int gt4hip_get_counter (gt4hip_context *ctx, const char *name, uint64_t *value);
 
 #ifdef __cplusplus
