@@ -17,6 +17,9 @@ LIB_PATH = os.environ.get("GT4HIP_LIB") or os.path.join(PKG_DIR, "libgt4hip.so")
 
 OK = 0
 EINVAL, ENODEVICE, ENOMEM, ERULE, EHIP, EWORDLEN, EINTERNAL = 1, 2, 3, 4, 5, 6, 7
+EFORMAT = 11
+MAKER_FORWARD_ONLY, MAKER_TEXT_ON_DEVICE = 1, 2
+MAKER_ERR_START, MAKER_ERR_PLUS, MAKER_ERR_AT, MAKER_ERR_PLUS_EOF = 1, 2, 3, 4
 OP_UNION, OP_INTRSEC, OP_DIFF1, OP_DIFF2 = 1, 2, 4, 8
 RULE_DEFAULT, RULE_ADD, RULE_SUBTRACT, RULE_MIN, RULE_MAX, RULE_FIRST, RULE_SECOND, RULE_NUMBER = range(8)
 
@@ -56,6 +59,11 @@ class QueryHit(C.Structure):
 QUERY_HIT_DTYPE = np.dtype([("query", "<u8"), ("rank", "<u8"), ("word", "<u8"), ("count", "<u4"), ("reserved", "<u4")])
 
 
+class MakerCarry(C.Structure):
+    _fields_ = [("file_type", C.c_uint32), ("in_name", C.c_uint32), ("line_phase", C.c_uint32), ("at_line_start", C.c_uint32),
+                ("ended", C.c_uint32), ("error", C.c_uint32), ("codes", C.c_uint8 * 32)]
+
+
 class MultiResult(C.Structure):
     _fields_ = [("n_words", C.c_uint64), ("total_count", C.c_uint64), ("out", C.c_void_p), ("device_ms", C.c_double),
                 ("records_read", C.c_uint64), ("records_written", C.c_uint64)]
@@ -82,6 +90,7 @@ SYMBOLS = [
     "gt4hip_query_index_create", "gt4hip_query_index_free", "gt4hip_query_index_last_ms", "gt4hip_query_variants",
     "gt4hip_query_variant_mask", "gt4hip_query_lookup", "gt4hip_query_lookup_all", "gt4hip_list_count_stats",
     "gt4hip_list_count_split", "gt4hip_list_count_histogram", "gt4hip_list_gc",
+    "gt4hip_text_to_words", "gt4hip_words_free", "gt4hip_words_download", "gt4hip_text_to_list",
 ]
 
 _lib = None
@@ -171,6 +180,11 @@ def lib():
             "gt4hip_list_count_split": (C.c_int, [vp, vp, u32, C.POINTER(u64), C.POINTER(u64)]),
             "gt4hip_list_count_histogram": (C.c_int, [vp, vp, u32, vp]),
             "gt4hip_list_gc": (C.c_int, [vp, vp, C.POINTER(u64)]),
+            "gt4hip_text_to_words": (C.c_int, [vp, vp, C.c_size_t, C.c_uint, C.c_uint, C.POINTER(MakerCarry), C.POINTER(MakerCarry),
+                                               C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]),
+            "gt4hip_words_free": (None, [vp, vp]),
+            "gt4hip_words_download": (C.c_int, [vp, vp, u64, vp]),
+            "gt4hip_text_to_list": (C.c_int, [vp, vp, C.c_size_t, C.c_uint, C.c_uint, C.POINTER(vp)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -401,6 +415,36 @@ class Context:
         w = np.ascontiguousarray(words, dtype=np.uint64)
         h = C.c_void_p()
         self._chk(lib().gt4hip_words_to_list(self.h, w.ctypes.data if len(w) else None, len(w), word_length, C.byref(h)))
+        return DeviceList(self, h)
+
+    def text_to_words(self, text, word_length, flags=0, carry=None, n_bytes=None):
+        """FastA / FastQ text -> (words in text order, carry for the next piece of the file) (gt4hip_text_to_words).
+        `text`: host bytes, or with MAKER_TEXT_ON_DEVICE in `flags` the address of `n_bytes` of device memory.
+        Malformed text raises Gt4HipError with code EFORMAT; the exception carries `error_offset` and `kind`
+        (MAKER_ERR_*)."""
+        out, d, n, at = MakerCarry(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        if flags & MAKER_TEXT_ON_DEVICE:
+            buf = C.c_void_p(text)
+        else:
+            buf, n_bytes = (C.c_char * max(len(text), 1)).from_buffer_copy(bytes(text) or b"\0"), len(text)
+        rc = lib().gt4hip_text_to_words(self.h, buf, n_bytes, word_length, flags, C.byref(carry) if carry is not None else None,
+                                        C.byref(out), C.byref(d), C.byref(n), C.byref(at))
+        if rc:
+            e = Gt4HipError(rc, lib().gt4hip_last_error(self.h).decode())
+            e.error_offset, e.kind = at.value, out.error
+            raise e
+        words = np.empty(n.value, dtype=np.uint64)
+        if n.value:
+            rc = lib().gt4hip_words_download(self.h, d, n.value, words.ctypes.data)
+            lib().gt4hip_words_free(self.h, d)
+            self._chk(rc)
+        return words, out
+
+    def text_to_list(self, text: bytes, word_length, flags=0) -> "DeviceList":
+        """One whole text -> the list glistmaker writes for it (gt4hip_text_to_list)."""
+        h = C.c_void_p()
+        buf = (C.c_char * max(len(text), 1)).from_buffer_copy(bytes(text) or b"\0")
+        self._chk(lib().gt4hip_text_to_list(self.h, buf, len(text), word_length, flags, C.byref(h)))
         return DeviceList(self, h)
 
     def sort_words(self, device_ptr, n_words, word_length):

@@ -1,0 +1,452 @@
+/*
+ * gt4_glistmaker_cli.c -- `glistmaker`, the drop-in command line that turns FastA / FastQ text into a k-mer list.
+ * Host C; the text is read into HBM and everything behind that -- classifying the bytes, putting the canonical words
+ * together, sorting and counting them, collating the pieces -- runs in the HIP kernels behind include/gt4hip.h
+ * (gt4hip_maker.hip, gt4hip_sort.hip, the N-way union).
+ *
+ * Same argv grammar, defaults, validation order, messages, help text on stderr, -v, output name (`<out>_<k>.list`,
+ * written as `.tmp`, then renamed) and exit codes as the reference's main() (reference src/glistmaker.c:138-353).
+ * --num_threads, --max_tables, --table_size (which swallows the argument behind its value, :210), --tmpdir, --stream
+ * and -D are parsed and validated as there and otherwise ignored: there is no task queue and there are no temporary
+ * files.  -c / --cutoff / --min and --max are validated as there and, as there, do nothing to a list: the reference
+ * hands cutoff 1 to gt4_write_union (:333, :814) and reads min / max for index output only (:486).
+ * A text larger than a chunk goes through the device in pieces, cut behind a '\n' where the second half of the chunk has
+ * one; each piece becomes a list and the lists are collated by ADD unions of at most 32 (gt4_write_union): as soon as 32
+ * lists of a level exist they become one list of the level above, so at most 31 lists per level are resident while the
+ * files are read.  The reference keeps such lists in temporary files; here they stay in device memory, so the collated
+ * lists of the levels (in the end: the result) have to fit there.  Several input files pool their words; a run of bases
+ * never crosses from one file into the next.
+ * Deliberate differences, all an error message + exit 1:
+ *   - --index (the location tables are not built);
+ *   - input that starts with the gzip magic (the reference goes by the name's .gz): decompress it first;
+ *   - without a usable GPU the program fails: there is no CPU path;
+ *   - malformed text (a first byte that is neither '>' nor '@'; FastQ without its '+' line or its '@'): the reference's
+ *     message for the first offending byte, then "Error: ..."; no output file is written.  (The reference carries on
+ *     behind a reader error and writes whatever it still finds.)
+ * Environment, all of it read in read_environment():
+ *   GT4HIP_MAKER_CHUNK=<bytes>[K|M|G]  bytes of text per piece (default: 1/64 of the free device memory, at most 1 GiB);
+ *   GT4HIP_DEVICE=N                    the device (default 0);
+ *   GT4HIP_VERBOSE=1                   prints the device, the pieces (where each ends) and the kernel times on stderr.
+ */
+#define _GNU_SOURCE
+#include <errno.h>
+#include <fcntl.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include "gt4_listfile.h"
+#include "gt4hip.h"
+
+#define MAX_FILES 1024
+#define MAX_TABLES 256
+#define UNION_WIDTH 32 /* FILE_MERGE_SIZE, src/glistmaker.c:68 */
+#define MAX_LEVELS 13  /* 32^13 pieces: more than a text of 2^64 bytes has */
+#define DOWNLOAD_CHUNK (4u << 20) /* records per device -> host -> file step */
+
+static const char *const HELP_LINES[] = {
+  "Usage: glistmaker <INPUTFILES> [OPTIONS]",
+  "Options:",
+  "    -v, --version           - print version information and exit",
+  "    -h, --help              - print this usage screen and exit",
+  "    -w, --wordlength NUMBER - specify index wordsize (1-32)",
+  "    -o, --outputname STRING - specify output name (default \"out\")",
+  "    --index                 - create index instead of list",
+  "    --num_threads           - number of threads (default 8)",
+  "    --max_tables            - maximum number of temporary tables (default 4096)",
+  "    --table_size            - maximum size of the temporary table (default 1048576)",
+  "    --tmpdir                - directory for temporary files (may need an order of magnitude more space than the size of the final list)",
+  "    --stream                - read files as streams instead of memory-mapping (slower but uses less virtual memory)",
+  "    --index                 - creates indexed list (larger and slower)",
+  "    -D                      - increase debug level",
+};
+
+typedef struct {
+  const char *fnames[MAX_FILES];
+  unsigned int nfiles;
+  unsigned int wordlength, min, max, nthreads, ntables, stream, create_index, debug;
+  long long tablesize;
+  const char *outputname, *tmpdir;
+  /* environment */
+  uint64_t chunk;
+  int device, verbose;
+} Options;
+
+static void print_help (int exit_value)
+{
+  fprintf (stderr, "glistmaker version %u.%u.%u (%s)\n", GT4_VERSION_MAJOR, GT4_VERSION_MINOR, GT4_VERSION_MICRO, GT4_VERSION_QUALIFIER);
+  for (size_t i = 0; i < sizeof HELP_LINES / sizeof HELP_LINES[0]; i++) fprintf (stderr, "%s\n", HELP_LINES[i]);
+  exit (exit_value);
+}
+
+/* "<n>[K|M|G]" -> bytes */
+static uint64_t parse_bytes (const char *s)
+{
+  if (!s || !*s) return 0;
+  char *end;
+  double v = strtod (s, &end);
+  if (*end == 'K' || *end == 'k') v *= 1024.0;
+  else if (*end == 'M' || *end == 'm') v *= 1024.0 * 1024.0;
+  else if (*end == 'G' || *end == 'g') v *= 1024.0 * 1024.0 * 1024.0;
+  return v > 0 ? (uint64_t) v : 0;
+}
+
+/* every environment variable of the program, once */
+static void read_environment (Options *o)
+{
+  const char *e;
+  o->chunk = parse_bytes (getenv ("GT4HIP_MAKER_CHUNK"));
+  o->device = (e = getenv ("GT4HIP_DEVICE")) ? atoi (e) : 0;
+  o->verbose = (e = getenv ("GT4HIP_VERBOSE")) && atoi (e);
+}
+
+/* the value of a numeric option, or the reference's message + help */
+static long long number_arg (int argc, const char *argv[], int *i, const char *what)
+{
+  char *end;
+  if (++*i >= argc) print_help (1);
+  const long long v = strtoll (argv[*i], &end, 10);
+  if (*end != 0) {
+    fprintf (stderr, "Error: Invalid %s: %s! Must be an integer.\n", what, argv[*i]);
+    print_help (1);
+  }
+  return v;
+}
+
+/* argv (reference :158-228) */
+static void parse_argv (int argc, const char *argv[], Options *o)
+{
+  o->min = 1;
+  o->max = 0xffffffffu;
+  o->nthreads = 8;
+  o->ntables = 32 * 128;
+  o->tablesize = 1024 * 1024;
+  o->outputname = "out";
+  o->tmpdir = ".";
+  for (int i = 1; i < argc; i++) {
+    const char *a = argv[i];
+    if (!strcmp (a, "-v") || !strcmp (a, "--version")) {
+      fprintf (stdout, "glistmaker version %u.%u.%u (%s)\n", GT4_VERSION_MAJOR, GT4_VERSION_MINOR, GT4_VERSION_MICRO, GT4_VERSION_QUALIFIER);
+      exit (0);
+    } else if (!strcmp (a, "-h") || !strcmp (a, "--help") || !strcmp (a, "-?")) {
+      print_help (0);
+    } else if (!strcmp (a, "-o") || !strcmp (a, "--outputname")) {
+      if (++i >= argc) print_help (1);
+      o->outputname = argv[i];
+    } else if (!strcmp (a, "-w") || !strcmp (a, "--wordlength")) {
+      o->wordlength = (unsigned int) (long) number_arg (argc, argv, &i, "word-length");
+    } else if (!strcmp (a, "-c") || !strcmp (a, "--cutoff") || !strcmp (a, "--min")) {
+      o->min = (unsigned int) (long) number_arg (argc, argv, &i, "frequency cut-off");
+    } else if (!strcmp (a, "--max")) {
+      o->max = (unsigned int) (long) number_arg (argc, argv, &i, "frequency cut-off");
+    } else if (!strcmp (a, "--num_threads")) {
+      o->nthreads = (unsigned int) (long) number_arg (argc, argv, &i, "num-threads");
+    } else if (!strcmp (a, "--max_tables")) {
+      o->ntables = (unsigned int) (long) number_arg (argc, argv, &i, "max_tables");
+    } else if (!strcmp (a, "--table_size")) {
+      o->tablesize = number_arg (argc, argv, &i, "table-size");
+      i += 1; /* the reference skips the argument behind the value as well */
+    } else if (!strcmp (a, "--tmpdir")) {
+      if (++i >= argc) print_help (1);
+      o->tmpdir = argv[i];
+    } else if (!strcmp (a, "--stream")) {
+      o->stream = 1;
+    } else if (!strcmp (a, "--index")) {
+      o->create_index = 1;
+    } else if (!strcmp (a, "-D")) {
+      o->debug += 1;
+    } else {
+      if (a[0] == '-' && a[1]) print_help (1);
+      if (o->nfiles >= MAX_FILES) continue;
+      o->fnames[o->nfiles++] = a;
+    }
+  }
+}
+
+/* reference :230-264 */
+static void validate (Options *o)
+{
+  if (o->ntables > MAX_TABLES) o->ntables = MAX_TABLES;
+  if (!o->nfiles) {
+    fprintf (stderr, "Error: No FastA/FastQ file specified!\n");
+    print_help (1);
+  }
+  if (o->wordlength < 1 || o->wordlength > 32) {
+    fprintf (stderr, "Error: Invalid word-length %d (must be 1 - 32)!\n", (int) o->wordlength);
+    print_help (1);
+  }
+  if (o->min < 1) {
+    fprintf (stderr, "Error: Invalid frequency cut-off: %d! Must be positive.\n", (int) o->min);
+    print_help (1);
+  }
+  if (o->max < o->min) {
+    fprintf (stderr, "Error: Invalid frequency range: %u-%u!\n", o->min, o->max);
+    print_help (1);
+  }
+  if (strlen (o->outputname) > 200) {
+    fprintf (stderr, "Error: Output name exceeds the 200 character limit.");
+    exit (1);
+  }
+  for (unsigned int i = 0; i < o->nfiles; i++) {
+    struct stat s;
+    if (!strcmp (o->fnames[i], "-")) continue;
+    if (stat (o->fnames[i], &s)) {
+      fprintf (stderr, "main: No such file (cannot stat): %s\n", o->fnames[i]);
+      exit (1);
+    }
+  }
+}
+
+/* ------------------------------------------------------------------ input text */
+
+typedef struct {
+  const unsigned char *data;
+  size_t size;
+  int mapped;
+  char id[1100]; /* the reader's name in the reference's messages */
+} Text;
+
+static void text_open (const Options *o, const char *name, Text *t)
+{
+  memset (t, 0, sizeof *t);
+  if (!strcmp (name, "-")) {
+    snprintf (t->id, sizeof t->id, "STDIN");
+    size_t cap = 1u << 20, n = 0;
+    unsigned char *b = (unsigned char *) malloc (cap);
+    while (b) {
+      const size_t got = fread (b + n, 1, cap - n, stdin);
+      n += got;
+      if (n < cap) break;
+      b = (unsigned char *) realloc (b, cap *= 2);
+    }
+    if (!b) {
+      fprintf (stderr, "Error: out of memory (standard input)\n");
+      exit (1);
+    }
+    t->data = b;
+    t->size = n;
+    return;
+  }
+  if (o->stream) snprintf (t->id, sizeof t->id, "%.1024s", name);
+  else snprintf (t->id, sizeof t->id, "%.1024s block 0", name);
+  const int fd = open (name, O_RDONLY);
+  struct stat s;
+  if (fd < 0 || fstat (fd, &s)) {
+    fprintf (stderr, "Error: cannot open %s: %s\n", name, strerror (errno));
+    exit (1);
+  }
+  t->size = (size_t) s.st_size;
+  if (t->size) {
+    void *p = mmap (NULL, t->size, PROT_READ, MAP_PRIVATE, fd, 0);
+    if (p == MAP_FAILED) {
+      fprintf (stderr, "Error: cannot map %s: %s\n", name, strerror (errno));
+      exit (1);
+    }
+    t->data = (const unsigned char *) p;
+    t->mapped = 1;
+  }
+  close (fd);
+  if (t->size >= 2 && t->data[0] == 0x1f && t->data[1] == 0x8b) {
+    fprintf (stderr, "Error: %s is gzip-compressed: decompress it first (compressed sequence files are not read)\n", name);
+    exit (1);
+  }
+}
+
+static void text_close (Text *t)
+{
+  if (t->mapped) munmap ((void *) t->data, t->size);
+  else free ((void *) t->data);
+}
+
+/* the reference's line for a reader error (src/fasta.c:136, :202, :211, :277), then ours; exit 1 */
+static void format_error_exit (const Text *t, uint32_t kind, uint64_t at)
+{
+  const int found = at < t->size ? t->data[at] : 0;
+  const unsigned long long cpos = at ? at - 1 : 0;
+  switch (kind) {
+    case GT4HIP_MAKER_ERR_START: fprintf (stderr, "fasta_reader_read_nwords: Reader %s invalid start tag '%c'\n", t->id, found); break;
+    case GT4HIP_MAKER_ERR_PLUS: fprintf (stderr, "fasta_reader_read_nwords: Reader %s tag '+' missing, found '%c' instead at %llu\n", t->id, found, cpos); break;
+    case GT4HIP_MAKER_ERR_AT: fprintf (stderr, "fasta_reader_read_nwords: Reader %s tag '@' missing, found '%c' instead at %llu\n", t->id, found, cpos); break;
+    default: fprintf (stderr, "fasta_reader_read_nwords: Reader %s invalid character '%c' after '+' %llu\n", t->id, found, (unsigned long long) at); break;
+  }
+  fprintf (stderr, "Error: %s is not well-formed FastA / FastQ text (byte %llu): no list written\n", t->id, (unsigned long long) at);
+  exit (1);
+}
+
+/* ------------------------------------------------------------------ text -> lists -> one list */
+
+#define CHK(ctx, call)                                                            \
+  do {                                                                            \
+    if ((call) != GT4HIP_OK) {                                                    \
+      fprintf (stderr, "Error: %s: %s\n", #call, gt4hip_last_error (ctx));        \
+      exit (1);                                                                   \
+    }                                                                             \
+  } while (0)
+
+/* the lists not yet collated: level 0 holds the pieces' own, level i + 1 unions of UNION_WIDTH lists of level i */
+typedef struct {
+  gt4hip_list *v[MAX_LEVELS][UNION_WIDTH];
+  unsigned int n[MAX_LEVELS];
+} Lists;
+
+/* gt4_write_union (reference :333, :814): cnt lists -> one, by ADD with cutoff 1; the inputs are freed */
+static gt4hip_list *union_lists (gt4hip_context *ctx, gt4hip_list *const *v, unsigned int cnt)
+{
+  if (cnt == 1) return v[0];
+  gt4hip_multi_result res;
+  memset (&res, 0, sizeof res);
+  CHK (ctx, gt4hip_union_multi (ctx, (const gt4hip_list *const *) v, cnt, 1, GT4HIP_RULE_ADD, 1, 0, &res));
+  for (unsigned int i = 0; i < cnt; i++) gt4hip_list_free (v[i]);
+  return res.out;
+}
+
+/* a full level becomes one list of the level above at once */
+static void lists_push (gt4hip_context *ctx, Lists *ls, gt4hip_list *l)
+{
+  for (unsigned int level = 0; level < MAX_LEVELS; level++) {
+    ls->v[level][ls->n[level]++] = l;
+    if (ls->n[level] < UNION_WIDTH || level + 1 == MAX_LEVELS) return;
+    l = union_lists (ctx, ls->v[level], UNION_WIDTH);
+    ls->n[level] = 0;
+  }
+}
+
+/* one file through the device, a piece at a time: a list per piece that holds a word */
+static void file_to_lists (const Options *o, gt4hip_context *ctx, const Text *t, uint64_t chunk, Lists *ls)
+{
+  gt4hip_maker_carry carry, next;
+  int have = 0;
+  size_t pos = 0;
+  unsigned int pieces = 0;
+  double extract_us = 0, sort_us = 0;
+  while (pos < t->size) {
+    size_t len = t->size - pos;
+    if (len > chunk) {
+      len = (size_t) chunk;
+      /* behind the last '\n' of the chunk's second half, where there is one */
+      const unsigned char *nl = (const unsigned char *) memrchr (t->data + pos + len / 2, '\n', len - len / 2);
+      if (nl) len = (size_t) (nl - (t->data + pos)) + 1;
+    }
+    uint64_t *words = NULL, n_words = 0, at = 0;
+    const int rc = gt4hip_text_to_words (ctx, t->data + pos, len, o->wordlength, 0, have ? &carry : NULL, &next, &words, &n_words, &at);
+    if (rc == GT4HIP_EFORMAT) format_error_exit (t, next.error, pos + at);
+    if (rc) {
+      fprintf (stderr, "Error: %s\n", gt4hip_last_error (ctx));
+      exit (1);
+    }
+    if (n_words) {
+      gt4hip_list *l = NULL;
+      uint64_t us = 0;
+      CHK (ctx, gt4hip_device_words_to_list (ctx, words, n_words, o->wordlength, &l));
+      gt4hip_words_free (ctx, words);
+      lists_push (ctx, ls, l);
+      if (!gt4hip_get_counter (ctx, "extract_us", &us)) extract_us += (double) us;
+      if (!gt4hip_get_counter (ctx, "sort_us", &us)) sort_us += (double) us;
+    }
+    carry = next;
+    have = 1;
+    pos += len;
+    pieces++;
+    if (o->verbose && pos < t->size) fprintf (stderr, "%s: piece %u ends at byte %zu\n", t->id, pieces, pos);
+    if (carry.ended) break;
+  }
+  /* the end of the file behind a FastQ sequence line or inside a '+' line (src/fasta.c:200-213) */
+  if (have && !carry.ended && carry.file_type == GT4HIP_MAKER_FASTQ && carry.line_phase == 2)
+    format_error_exit (t, carry.at_line_start ? GT4HIP_MAKER_ERR_PLUS : GT4HIP_MAKER_ERR_PLUS_EOF, t->size);
+  if (o->verbose) fprintf (stderr, "%s: %zu bytes in %u piece(s); extraction %.3f ms, radix sort %.3f ms\n", t->id, t->size, pieces, extract_us / 1000.0, sort_us / 1000.0);
+}
+
+/* what the levels still hold -> one list (NULL: there was no word), from the lowest level up */
+static gt4hip_list *collate (gt4hip_context *ctx, Lists *ls)
+{
+  gt4hip_list *up = NULL;
+  for (unsigned int level = 0; level < MAX_LEVELS; level++) {
+    if (up) ls->v[level][ls->n[level]++] = up; /* (a level in use holds at most UNION_WIDTH - 1) */
+    up = ls->n[level] ? union_lists (ctx, ls->v[level], ls->n[level]) : NULL;
+    ls->n[level] = 0;
+  }
+  return up;
+}
+
+/* device list (NULL: no words, a header alone as reference :341-348) -> "<final>.tmp" -> rename */
+static int write_list_file (gt4hip_context *ctx, const gt4hip_list *list, unsigned int word_length, const char *tmp_name, const char *final_name)
+{
+  GT4ListWriter w;
+  if (gt4_listwriter_begin (&w, tmp_name, word_length, 0666)) {
+    fprintf (stderr, "Cannot create output file %s\n", tmp_name);
+    return 1;
+  }
+  const uint64_t n_words = list ? gt4hip_list_n_words (list) : 0;
+  uint64_t total_count = 0;
+  int bad = 0;
+  if (n_words && gt4hip_list_sum_counts (ctx, list, &total_count)) bad = 1;
+  void *buf = n_words ? malloc ((size_t) (n_words < DOWNLOAD_CHUNK ? n_words : DOWNLOAD_CHUNK) * 12u) : NULL;
+  if (n_words && !buf) bad = 1;
+  for (uint64_t first = 0; first < n_words && !bad; first += DOWNLOAD_CHUNK) {
+    const uint64_t cnt = n_words - first < DOWNLOAD_CHUNK ? n_words - first : DOWNLOAD_CHUNK;
+    if (gt4hip_list_download_range (ctx, list, first, cnt, buf)) {
+      fprintf (stderr, "Error: reading results back from the GPU failed: %s\n", gt4hip_last_error (ctx));
+      bad = 1;
+    } else if (gt4_listwriter_append (&w, buf, cnt)) {
+      fprintf (stderr, "Error: writing %s failed: %s\n", tmp_name, strerror (errno));
+      bad = 1;
+    }
+  }
+  free (buf);
+  if (bad) {
+    gt4_listwriter_abort (&w);
+    unlink (tmp_name);
+    return 1;
+  }
+  if (gt4_listwriter_finish (&w, n_words, total_count)) {
+    fprintf (stderr, "Error: writing %s failed: %s\n", tmp_name, strerror (errno));
+    unlink (tmp_name);
+    return 1;
+  }
+  if (rename (tmp_name, final_name)) fprintf (stderr, "Cannot rename %s to %s\n", tmp_name, final_name);
+  return 0;
+}
+
+int main (int argc, const char *argv[])
+{
+  static Options o;
+  read_environment (&o);
+  parse_argv (argc, argv, &o);
+  validate (&o);
+  if (o.create_index) {
+    fprintf (stderr, "Error: --index is not supported: this glistmaker writes lists only\n");
+    return 1;
+  }
+  static Text texts[MAX_FILES];
+  for (unsigned int i = 0; i < o.nfiles; i++) text_open (&o, o.fnames[i], &texts[i]);
+  gt4hip_context *ctx = NULL;
+  if (gt4hip_create (o.device, &ctx)) {
+    fprintf (stderr, "Error: no usable GPU: %s\n", gt4hip_last_error (NULL));
+    return 1;
+  }
+  uint64_t chunk = o.chunk;
+  if (!chunk) {
+    uint64_t free_b = 0, total_b = 0;
+    gt4hip_device_memory (ctx, &free_b, &total_b);
+    chunk = free_b / 64;
+    if (chunk > (1ull << 30)) chunk = 1ull << 30;
+    if (chunk < (1ull << 20)) chunk = 1ull << 20;
+  }
+  if (o.verbose) fprintf (stderr, "Device: %s; pieces of %llu bytes\n", gt4hip_device_info (ctx), (unsigned long long) chunk);
+  static Lists ls;
+  for (unsigned int i = 0; i < o.nfiles; i++) {
+    file_to_lists (&o, ctx, &texts[i], chunk, &ls);
+    text_close (&texts[i]);
+  }
+  gt4hip_list *result = collate (ctx, &ls);
+  char tmp_name[1024], out_name[1024];
+  snprintf (tmp_name, sizeof tmp_name, "%s_%u.list.tmp", o.outputname, o.wordlength);
+  snprintf (out_name, sizeof out_name, "%s_%u.list", o.outputname, o.wordlength);
+  if (write_list_file (ctx, result, o.wordlength, tmp_name, out_name)) return 1;
+  if (result) gt4hip_list_free (result);
+  gt4hip_destroy (ctx);
+  return 0;
+}

@@ -41,6 +41,7 @@ extern "C" const char *gt4hip_strerror (int code)
     case GT4HIP_ECALLBACK: return "stopped by callback";
     case GT4HIP_EIO: return "file I/O failed";
     case GT4HIP_ECOMM: return "RCCL communication failed";
+    case GT4HIP_EFORMAT: return "malformed sequence text";
     default: return "unknown error";
   }
 }
@@ -112,6 +113,7 @@ extern "C" void gt4hip_destroy (gt4hip_context *ctx)
   hipSetDevice (ctx->device);
   if (ctx->stream) hipStreamSynchronize (ctx->stream);
   gt4hip_io_destroy (ctx);
+  gt4hip_words_free (ctx, NULL);
   if (ctx->pool) {
     pool_flush (ctx);
     delete ctx->pool;
@@ -195,6 +197,8 @@ extern "C" int gt4hip_get_counter (gt4hip_context *ctx, const char *name, uint64
   else if (!strcmp (name, "nway_one_pass")) *value = (uint64_t) ctx->last_multi_one_pass;
   else if (!strcmp (name, "sort_us")) *value = (uint64_t) (ctx->sort_ms * 1000.0);
   else if (!strcmp (name, "fold_us")) *value = (uint64_t) (ctx->fold_ms * 1000.0);
+  else if (!strcmp (name, "extract_us")) *value = (uint64_t) (ctx->extract_ms * 1000.0);
+  else if (!strcmp (name, "maker_text_tile") || !strcmp (name, "maker_code_tile")) *value = GT4HIP_MAKER_TILE;
   else if (!strcmp (name, "table_us")) *value = (uint64_t) (ctx->table_ms * 1000.0);
   else if (!strcmp (name, "query_wide")) *value = ctx->query_wide;
   else if (!strcmp (name, "mm_wide_levels")) *value = ctx->mm_wide_levels;

@@ -64,6 +64,8 @@ struct gt4hip_context {
   uint64_t kway_declined;    /* ... handed to the pairwise tree because the keys are clustered (option "kway" = 1) */
   double table_ms;           /* the last gt4hip_union_table, wall time of the call */
   double sort_ms, fold_ms;   /* the last gt4hip_device_words_to_list: radix sort and fold (HIP events) */
+  double extract_ms;         /* the last gt4hip_text_to_words that gave words: its kernels (HIP events around them alone) */
+  struct gt4hip_list *maker_words; /* the words of the last gt4hip_text_to_words, until gt4hip_words_free or the next call */
   double nway_kernel_ms;     /* the last one-pass launch's kernel time (HIP events on the library's stream) and tiles */
   uint64_t nway_tiles;
   int last_multi_one_pass;   /* the last gt4hip_union_multi was done by the one-pass tile kernel (counter "nway_one_pass") */
@@ -153,7 +155,7 @@ GT4HIP_LOCAL gt4::PairParams gt4hip_nway_params (uint32_t op_bit, uint32_t rule,
 /* bytes of the chained scan's descriptors (gt4hip_device.h): agg u32[4][rows * 64], carry u64[4][rows + 1], rowsum u64[4][rows] */
 GT4HIP_LOCAL size_t gt4hip_lookback_desc_bytes (uint64_t tiles);
 
-/* ---- gt4hip_nway.hip, gt4hip_table.hip, gt4hip_io.hip */
+/* ---- gt4hip_nway.hip, gt4hip_table.hip, gt4hip_io.hip, gt4hip_maker.hip */
 int gt4hip_nway_union (gt4hip_context *ctx, const gt4hip_list *const lists[], uint32_t k, uint32_t rule, uint32_t cutoff, uint32_t ovr,
                        uint32_t filter, bool count_only, gt4hip_list *out, uint64_t *n_words, uint64_t *total_count, double *device_ms, int *used);
 int gt4hip_nway_table (gt4hip_context *ctx, const gt4hip_list *const lists[], uint32_t k, const uint32_t cols[], gt4hip_count_table *table, int probe,
@@ -167,6 +169,8 @@ int gt4hip_table_set_ragged (gt4hip_context *ctx, gt4hip_count_table *table, uin
 void *gt4hip_table_compact_bases (gt4hip_count_table *table);
 void *gt4hip_table_padded_bases (gt4hip_count_table *table);
 void gt4hip_io_destroy (gt4hip_context *ctx);
+/* bytes of text, and codes, per tile of gt4hip_maker.hip's kernels (counters "maker_text_tile", "maker_code_tile") */
+#define GT4HIP_MAKER_TILE 4096u
 int gt4hip_io_download (gt4hip_context *ctx, const void *dev, void *host, size_t bytes);
 
 #define HIPCHK(ctx, call)                                                                               \

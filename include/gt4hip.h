@@ -43,7 +43,8 @@ enum {
   GT4HIP_EINTERNAL = 7,   /* in-kernel consistency check tripped             */
   GT4HIP_ECALLBACK = 8,   /* (internal) walk stopped by the caller's callback */
   GT4HIP_EIO = 9,         /* reading or writing a file descriptor failed       */
-  GT4HIP_ECOMM = 10       /* RCCL could not be loaded / a collective failed    */
+  GT4HIP_ECOMM = 10,      /* RCCL could not be loaded / a collective failed    */
+  GT4HIP_EFORMAT = 11     /* sequence text that is neither FastA nor FastQ, or malformed FastQ */
 };
 
 /* enum Rules of the reference, src/glistcompare.c:45-54 (same numeric values) */
@@ -397,6 +398,55 @@ int gt4hip_words_to_list (gt4hip_context *ctx, const uint64_t *host_words, uint6
 int gt4hip_device_words_to_list (gt4hip_context *ctx, void *device_words, uint64_t n_words, uint32_t word_length,
                                  gt4hip_list **out);
 
+/* ---------------------------------------------------------------- glistmaker's front: sequence text -> words */
+
+enum {
+  GT4HIP_MAKER_FORWARD_ONLY = 1,   /* the forward word as it stands, not min (word, reverse complement)              */
+  GT4HIP_MAKER_TEXT_ON_DEVICE = 2  /* `text` is device memory (16-byte aligned); else host memory, copied in by the call */
+};
+enum { GT4HIP_MAKER_FASTA = 1, GT4HIP_MAKER_FASTQ = 2 };
+/* what GT4HIP_EFORMAT stands for (gt4hip_maker_carry.error), with the reference's message in src/fasta.c */
+enum {
+  GT4HIP_MAKER_ERR_START = 1,    /* :136 the first byte of a file is neither '>' nor '@'                              */
+  GT4HIP_MAKER_ERR_PLUS = 2,     /* :202 the line behind a FastQ sequence line does not start with '+' (or is missing) */
+  GT4HIP_MAKER_ERR_AT = 3,       /* :277 the byte behind a FastQ quality line is neither '@' nor the end of the text  */
+  GT4HIP_MAKER_ERR_PLUS_EOF = 4  /* :211 the text ends inside a FastQ '+' line                                        */
+};
+
+/* The reader's state between two pieces of one file: hand the `out` of a piece to the next piece as `in`; NULL starts a
+ * file.  A piece may be cut anywhere. */
+typedef struct {
+  uint32_t file_type;      /* 0: nothing read yet; GT4HIP_MAKER_FASTA / _FASTQ, decided by the first byte of the file */
+  uint32_t in_name;        /* FastA: the piece ended inside a name                                                    */
+  uint32_t line_phase;     /* FastQ: '\n's so far mod 4 (0 name, 1 sequence, 2 '+' line, 3 quality)                   */
+  uint32_t at_line_start;  /* the last byte was a '\n' (or there was none yet)                                        */
+  uint32_t ended;          /* a NUL byte ended the text (the reference's end of file): later pieces give nothing      */
+  uint32_t error;          /* GT4HIP_MAKER_ERR_* when the call returned GT4HIP_EFORMAT                                */
+  uint8_t codes[32];       /* the last codes (0..3 a base, 4 none): the word_length - 1 bases a word of the next piece may begin with */
+} gt4hip_maker_carry;
+
+/* fasta_reader_read_nwords (src/fasta.c:87-291) as glistmaker runs it (canonising, src/listmaker-queue.c:196) on
+ * `n_bytes` of FastA / FastQ text: every word of `word_length` bases, in text order, into a new device buffer
+ * (*d_words, *n_words; NULL and 0 when there is none).  The buffer is the context's, one at a time: it is scratch for
+ * gt4hip_device_words_to_list and lasts until gt4hip_words_free (d_words NULL: whatever the context holds), the
+ * context's next gt4hip_text_to_words or gt4hip_destroy.  Bytes < ' ' are skipped, so words span line breaks; any other byte that is no base
+ * ends the run; a NUL byte ends the text.  Malformed text is GT4HIP_EFORMAT with the offending byte's offset in
+ * *error_offset (may be NULL) and the kind in out->error; what the end of the file makes of a FastQ text that stops
+ * behind a sequence line or inside a '+' line is the caller's to report, unless a NUL ended it (gt4hip_text_to_list does). */
+int gt4hip_text_to_words (gt4hip_context *ctx, const void *text, size_t n_bytes, unsigned word_length, unsigned flags,
+                          const gt4hip_maker_carry *in, gt4hip_maker_carry *out, uint64_t **d_words, uint64_t *n_words,
+                          uint64_t *error_offset);
+/* Gives the context's word buffer back.  The context holds exactly one: `d_words` is that buffer's address or NULL
+ * ("whatever the context holds"); any other pointer is ignored.  A d_words of an earlier gt4hip_text_to_words is
+ * invalid from the moment the context's next gt4hip_text_to_words is entered, also when that call fails or gives no
+ * words: finish with the words of a piece (gt4hip_device_words_to_list, gt4hip_words_download) before the next piece. */
+void gt4hip_words_free (gt4hip_context *ctx, uint64_t *d_words);
+/* n_words words of such a buffer -> host memory */
+int gt4hip_words_download (gt4hip_context *ctx, const uint64_t *d_words, uint64_t n_words, uint64_t *host_words);
+/* One whole text -> the list glistmaker writes for it: gt4hip_text_to_words, then gt4hip_device_words_to_list. */
+int gt4hip_text_to_list (gt4hip_context *ctx, const void *text, size_t n_bytes, unsigned word_length, unsigned flags,
+                         gt4hip_list **out);
+
 /* ---------------------------------------------------------------- synthetic lists (bench) */
 
 /* Fills `list` (capacity >= n) with n strictly ascending keys < 4^word_length and counts in
@@ -444,7 +494,10 @@ int gt4hip_set_option (gt4hip_context *ctx, const char *name, int64_t value);
  * partitions repeated with fewer samples per tile because a tile would not have fit LDS;
  * "nway_kernel_us", "nway_tiles": the last N-way call's tile kernel; "nway_one_pass": 1 when the last
  * gt4hip_union_multi took the one-pass tile kernel, 0 when it took the pairwise tree; "sort_us", "fold_us", "table_us":
- * the last gt4hip_device_words_to_list / gt4hip_union_table call;
+ * the last gt4hip_device_words_to_list / gt4hip_union_table call; "extract_us": the kernels of the last gt4hip_text_to_words
+ * that gave words (HIP events around the kernels alone: the call's read-back of its totals and the allocation of the
+ * words lie between two spans and are not in it; a kernel trace sums the same kernels); "maker_text_tile",
+ * "maker_code_tile": bytes of text, and codes (one per text byte >= ' '), per tile of that call's kernels;
  * "query_wide": 1 when the context's last gt4hip_query_lookup ran the kernel with 64-bit variant ranks, else 0;
  * "mm_wide_levels": levels of the last gt4hip_compare_mismatch, both tables added, run with 64-bit variant ranks;
  * "mm_unskipped_levels": levels of it run without the early exit of decided words (more than 2^32 - 1 variants a word, no subtract). */

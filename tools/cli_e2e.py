@@ -2,14 +2,69 @@
 (GPU box; not part of the product).
 
     python tools/cli_e2e.py [records_per_list] [--no-ref] [--modes=plain,chunks,gpus2,plain]
+    python tools/cli_e2e.py --maker [bases] [--no-ref] [--keep=DIR]
+
+--maker: glistmaker instead -- the seeded genome of tests/genome_util.py at `bases` (default 10^8) as FastA in /dev/shm,
+k = 25, the drop-in (twice: the first run pays the start of the HIP runtime) against oracle/_ref/glistmaker with its
+default threads, outputs compared with cmp.  --keep=DIR leaves genome.fa in DIR (for a profiler run) and stops there.
 
 Modes of the drop-in: plain (no environment variables: inputs of 4 GiB and more take the chunk pipeline with a
 budget the tool chooses, smaller ones stay in one piece), chunks (GT4HIP_HBM_LIMIT: key-range chunks through the
 loader / merger / writer pipeline with a quarter of the inputs in flight), gpus2 (two worker processes on the
 visible device(s)), and the reference binary.  Prints one line per run and whether the outputs are identical."""
 import os, subprocess, sys, time, shutil, tempfile, json
+import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def maker_main(argv):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import genome_util
+    nums = [a for a in argv if a.isdigit()]
+    bases = int(nums[0]) if nums else 100_000_000
+    keep = [a.split("=", 1)[1] for a in argv if a.startswith("--keep=")]
+    d = keep[0] if keep else tempfile.mkdtemp(prefix="gt4maker_", dir="/dev/shm")
+    os.makedirs(d, exist_ok=True)
+    try:
+        codes = genome_util.make_genome(length=bases)
+        lines = np.frombuffer(b"ACGT", dtype=np.uint8)[codes]
+        with open(os.path.join(d, "genome.fa"), "wb") as f:  # lines of 70 bases, as genome_util.fasta_text
+            f.write(b">genome seed %d\n" % genome_util.GENOME_SEED)
+            whole = len(lines) // 70 * 70
+            body = np.empty((whole // 70, 71), dtype=np.uint8)
+            body[:, :70] = lines[:whole].reshape(-1, 70)
+            body[:, 70] = 10
+            f.write(body.tobytes())
+            if whole < len(lines):
+                f.write(lines[whole:].tobytes() + b"\n")
+        print("input: %d bases, %d bytes in %s" % (bases, os.path.getsize(os.path.join(d, "genome.fa")), d), flush=True)
+        if keep:
+            return
+        results = []
+        runs = [("ours", os.path.join(ROOT, "genometester4_amd", "glistmaker")), ("ours2", os.path.join(ROOT, "genometester4_amd", "glistmaker"))]
+        if "--no-ref" not in argv:
+            runs.append(("ref", os.path.join(ROOT, "oracle", "_ref", "glistmaker")))
+        for tag, exe in runs:
+            t0 = time.perf_counter()
+            r = subprocess.run([exe, "genome.fa", "-w", "25", "-o", tag], cwd=d, capture_output=True, env=dict(os.environ, GT4HIP_VERBOSE="1"))
+            dt = time.perf_counter() - t0
+            print("%-6s rc %d  %.3f s  (%.1f M bases/s)  %s" % (tag, r.returncode, dt, bases / dt / 1e6, r.stderr.decode()[-300:].replace("\n", " | ") if tag != "ref" else ""), flush=True)
+            results.append(dict(mode=tag, rc=r.returncode, seconds=dt))
+        for tag, _ in runs[1:]:
+            same = subprocess.run(["cmp", "-s", os.path.join(d, "ours_25.list"), os.path.join(d, tag + "_25.list")]).returncode == 0
+            print("%-6s output identical to ours: %s" % (tag, same), flush=True)
+            results.append(dict(mode=tag, identical_to_ours=same))
+        print(json.dumps(dict(maker_bases=bases, results=results)))
+    finally:
+        if not keep:
+            shutil.rmtree(d, ignore_errors=True)
+
+
+if "--maker" in sys.argv:
+    maker_main(sys.argv[1:])
+    sys.exit(0)
+
 from genometester4_amd import capi
 from genometester4_amd.listio import write_list
 from bench import build_lists
