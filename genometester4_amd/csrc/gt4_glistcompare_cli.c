@@ -41,6 +41,7 @@
 #include <sys/time.h>
 #include <unistd.h>
 
+#include "gt4_cli.h"
 #include "gt4_listfile.h"
 #include "gt4_shard.h"
 #include "gt4hip.h"
@@ -55,10 +56,7 @@
 enum { OPT_PLAIN, OPT_VERSION, OPT_HELP, OPT_OUT, OPT_CUTOFF, OPT_MM, OPT_UNION, OPT_INTRSEC, OPT_DIFF, OPT_DDIFF, OPT_DU,
        OPT_COUNT_ONLY, OPT_RULE, OPT_SUBSET, OPT_SEED, OPT_PRINT_OP, OPT_NOSCOUTS, OPT_STREAM, OPT_DEBUG, OPT_GPUS };
 
-static const struct {
-  const char *name;
-  int opt;
-} OPTIONS[] = {
+static const GT4CliOption OPTIONS[] = {
   { "-v", OPT_VERSION }, { "--version", OPT_VERSION }, { "-h", OPT_HELP }, { "--help", OPT_HELP }, { "-?", OPT_HELP },
   { "-o", OPT_OUT }, { "--outputname", OPT_OUT }, { "-c", OPT_CUTOFF }, { "--cutoff", OPT_CUTOFF },
   { "--count_cutoff", OPT_CUTOFF }, /* alias used by the benchmark description; not in the reference */
@@ -94,23 +92,10 @@ static const char *const HELP_LINES[] = {
   "    -D                       - increase debug level",
 };
 
-static void print_version (void)
-{
-  fprintf (stdout, "glistcompare version %u.%u.%u (%s)\n", GT4_VERSION_MAJOR, GT4_VERSION_MINOR, GT4_VERSION_MICRO, GT4_VERSION_QUALIFIER);
-}
-
 static void print_help (int exit_value)
 {
-  print_version ();
-  for (size_t i = 0; i < sizeof HELP_LINES / sizeof HELP_LINES[0]; i++) fprintf (stdout, "%s\n", HELP_LINES[i]);
+  gt4_cli_print_help (stdout, "glistcompare", HELP_LINES, sizeof HELP_LINES / sizeof HELP_LINES[0]);
   exit (exit_value);
-}
-
-static int lookup_option (const char *arg)
-{
-  for (size_t i = 0; i < sizeof OPTIONS / sizeof OPTIONS[0]; i++)
-    if (!strcmp (arg, OPTIONS[i].name)) return OPTIONS[i].opt;
-  return -1;
 }
 
 static double now_seconds (void)
@@ -118,63 +103,6 @@ static double now_seconds (void)
   struct timeval tv;
   gettimeofday (&tv, NULL);
   return tv.tv_sec + tv.tv_usec * 1e-6;
-}
-
-#define DOWNLOAD_CHUNK (4u << 20) /* records per device -> host -> file step (48 MiB) */
-
-/* device list -> "<final>.tmp" -> rename, header back-patched with the kernel's totals */
-static int write_list_file (gt4hip_context *ctx, const gt4hip_list *list, unsigned int word_length, uint64_t n_words, uint64_t total_count,
-                            const char *final_name, unsigned int mode)
-{
-  char tmp_name[2100];
-  snprintf (tmp_name, sizeof tmp_name, "%.2048s.tmp", final_name);
-  GT4ListWriter w;
-  if (gt4_listwriter_begin (&w, tmp_name, word_length, mode)) {
-    fprintf (stderr, "Error: Cannot create output file %s\n", tmp_name);
-    return 1;
-  }
-  int bad = 0;
-  void *buf = n_words ? malloc ((size_t) (n_words < DOWNLOAD_CHUNK ? n_words : DOWNLOAD_CHUNK) * 12u) : NULL;
-  if (n_words && !buf) bad = 1;
-  for (uint64_t first = 0; first < n_words && !bad; first += DOWNLOAD_CHUNK) {
-    const uint64_t cnt = n_words - first < DOWNLOAD_CHUNK ? n_words - first : DOWNLOAD_CHUNK;
-    if (gt4hip_list_download_range (ctx, list, first, cnt, buf)) {
-      fprintf (stderr, "Error: reading results back from the GPU failed: %s\n", gt4hip_last_error (ctx));
-      bad = 1;
-    } else if (gt4_listwriter_append (&w, buf, cnt)) {
-      fprintf (stderr, "Error: writing %s failed: %s\n", tmp_name, strerror (errno));
-      bad = 1;
-    }
-  }
-  free (buf);
-  if (bad) {
-    gt4_listwriter_abort (&w);
-    unlink (tmp_name);
-    return 1;
-  }
-  if (gt4_listwriter_finish (&w, n_words, total_count)) {
-    fprintf (stderr, "Error: writing %s failed: %s\n", tmp_name, strerror (errno));
-    unlink (tmp_name);
-    return 1;
-  }
-  if (rename (tmp_name, final_name)) {
-    fprintf (stderr, "Error: Cannot rename %s to %s\n", tmp_name, final_name);
-    return 1;
-  }
-  return 0;
-}
-
-
-/* "<n>[K|M|G]" -> bytes */
-static uint64_t parse_bytes (const char *s)
-{
-  if (!s || !*s) return 0;
-  char *end;
-  double v = strtod (s, &end);
-  if (*end == 'K' || *end == 'k') v *= 1024.0;
-  else if (*end == 'M' || *end == 'm') v *= 1024.0 * 1024.0;
-  else if (*end == 'G' || *end == 'g') v *= 1024.0 * 1024.0 * 1024.0;
-  return v > 0 ? (uint64_t) v : 0;
 }
 
 /* What argv and the environment decide.  read_environment and parse_argv fill it, validate settles
@@ -198,13 +126,12 @@ typedef struct {
 static void read_environment (Options *o)
 {
   const char *e;
+  gt4_cli_read_environment (&o->device, &o->verbose);
   o->n_gpus = (e = getenv ("GT4HIP_GPUS")) ? atoi (e) : 0;
-  o->verbose = (e = getenv ("GT4HIP_VERBOSE")) && atoi (e);
-  o->hbm_limit = parse_bytes (getenv ("GT4HIP_HBM_LIMIT"));
+  o->hbm_limit = gt4_cli_parse_bytes (getenv ("GT4HIP_HBM_LIMIT"));
   o->pipeline_off = (e = getenv ("GT4HIP_PIPELINE")) && !atoi (e);
   o->gather_rccl = (e = getenv ("GT4HIP_GATHER")) && !strcmp (e, "rccl");
   o->check_sorted = (e = getenv ("GT4HIP_CHECK_SORTED")) && atoi (e);
-  o->device = (e = getenv ("GT4HIP_DEVICE")) ? atoi (e) : 0;
 }
 
 /* argv (reference :107-230; every quirk of its hand-rolled loop is kept) */
@@ -226,9 +153,9 @@ static void parse_argv (int argc, const char *argv[], Options *o)
       o->fnames[o->nfiles++] = arg;
       continue;
     }
-    switch (lookup_option (arg)) {
+    switch (gt4_cli_find_option (OPTIONS, sizeof OPTIONS / sizeof OPTIONS[0], arg)) {
       case OPT_VERSION:
-        print_version ();
+        gt4_cli_print_version (stdout, "glistcompare");
         exit (0);
       case OPT_HELP:
         print_help (0);
@@ -598,8 +525,8 @@ static int run_multi (const Options *o, const GT4ListFile *files, unsigned int w
                (is_union ? total : 0ull) / (1000000 * (t_e - t_s)), (unsigned long long) n_words, n_words / (1000000 * (t_e - t_s)));
     }
     if (!job && !o->countonly) {
-      /* creat (.., 0644) in the reference */
-      if (write_list_file (ctx, mres.out, wlen, n_words, total_count, name, 0644)) exit (1);
+      /* creat (.., 0644) in the reference; a failed rename is fatal here */
+      if (gt4_cli_write_list_file (ctx, mres.out, wlen, n_words, total_count, name, 0644, "Error: ")) exit (1);
       gt4hip_list_free (mres.out);
     }
     if (o->countonly || o->debug) print_totals (n_words, total_count);

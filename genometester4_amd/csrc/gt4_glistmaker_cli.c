@@ -38,6 +38,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include "gt4_cli.h"
 #include "gt4_listfile.h"
 #include "gt4hip.h"
 
@@ -45,7 +46,6 @@
 #define MAX_TABLES 256
 #define UNION_WIDTH 32 /* FILE_MERGE_SIZE, src/glistmaker.c:68 */
 #define MAX_LEVELS 13  /* 32^13 pieces: more than a text of 2^64 bytes has */
-#define DOWNLOAD_CHUNK (4u << 20) /* records per device -> host -> file step */
 
 static const char *const HELP_LINES[] = {
   "Usage: glistmaker <INPUTFILES> [OPTIONS]",
@@ -77,30 +77,15 @@ typedef struct {
 
 static void print_help (int exit_value)
 {
-  fprintf (stderr, "glistmaker version %u.%u.%u (%s)\n", GT4_VERSION_MAJOR, GT4_VERSION_MINOR, GT4_VERSION_MICRO, GT4_VERSION_QUALIFIER);
-  for (size_t i = 0; i < sizeof HELP_LINES / sizeof HELP_LINES[0]; i++) fprintf (stderr, "%s\n", HELP_LINES[i]);
+  gt4_cli_print_help (stderr, "glistmaker", HELP_LINES, sizeof HELP_LINES / sizeof HELP_LINES[0]);
   exit (exit_value);
-}
-
-/* "<n>[K|M|G]" -> bytes */
-static uint64_t parse_bytes (const char *s)
-{
-  if (!s || !*s) return 0;
-  char *end;
-  double v = strtod (s, &end);
-  if (*end == 'K' || *end == 'k') v *= 1024.0;
-  else if (*end == 'M' || *end == 'm') v *= 1024.0 * 1024.0;
-  else if (*end == 'G' || *end == 'g') v *= 1024.0 * 1024.0 * 1024.0;
-  return v > 0 ? (uint64_t) v : 0;
 }
 
 /* every environment variable of the program, once */
 static void read_environment (Options *o)
 {
-  const char *e;
-  o->chunk = parse_bytes (getenv ("GT4HIP_MAKER_CHUNK"));
-  o->device = (e = getenv ("GT4HIP_DEVICE")) ? atoi (e) : 0;
-  o->verbose = (e = getenv ("GT4HIP_VERBOSE")) && atoi (e);
+  o->chunk = gt4_cli_parse_bytes (getenv ("GT4HIP_MAKER_CHUNK"));
+  gt4_cli_read_environment (&o->device, &o->verbose);
 }
 
 /* the value of a numeric option, or the reference's message + help */
@@ -129,7 +114,7 @@ static void parse_argv (int argc, const char *argv[], Options *o)
   for (int i = 1; i < argc; i++) {
     const char *a = argv[i];
     if (!strcmp (a, "-v") || !strcmp (a, "--version")) {
-      fprintf (stdout, "glistmaker version %u.%u.%u (%s)\n", GT4_VERSION_MAJOR, GT4_VERSION_MINOR, GT4_VERSION_MICRO, GT4_VERSION_QUALIFIER);
+      gt4_cli_print_version (stdout, "glistmaker");
       exit (0);
     } else if (!strcmp (a, "-h") || !strcmp (a, "--help") || !strcmp (a, "-?")) {
       print_help (0);
@@ -249,10 +234,7 @@ static void text_open (const Options *o, const char *name, Text *t)
     t->mapped = 1;
   }
   close (fd);
-  if (t->size >= 2 && t->data[0] == 0x1f && t->data[1] == 0x8b) {
-    fprintf (stderr, "Error: %s is gzip-compressed: decompress it first (compressed sequence files are not read)\n", name);
-    exit (1);
-  }
+  if (t->size >= 2 && gt4_cli_refuse_gzip (name, t->data[0], t->data[1])) exit (1);
 }
 
 static void text_close (Text *t)
@@ -277,14 +259,6 @@ static void format_error_exit (const Text *t, uint32_t kind, uint64_t at)
 }
 
 /* ------------------------------------------------------------------ text -> lists -> one list */
-
-#define CHK(ctx, call)                                                            \
-  do {                                                                            \
-    if ((call) != GT4HIP_OK) {                                                    \
-      fprintf (stderr, "Error: %s: %s\n", #call, gt4hip_last_error (ctx));        \
-      exit (1);                                                                   \
-    }                                                                             \
-  } while (0)
 
 /* the lists not yet collated: level 0 holds the pieces' own, level i + 1 unions of UNION_WIDTH lists of level i */
 typedef struct {
@@ -371,45 +345,6 @@ static gt4hip_list *collate (gt4hip_context *ctx, Lists *ls)
   return up;
 }
 
-/* device list (NULL: no words, a header alone as reference :341-348) -> "<final>.tmp" -> rename */
-static int write_list_file (gt4hip_context *ctx, const gt4hip_list *list, unsigned int word_length, const char *tmp_name, const char *final_name)
-{
-  GT4ListWriter w;
-  if (gt4_listwriter_begin (&w, tmp_name, word_length, 0666)) {
-    fprintf (stderr, "Cannot create output file %s\n", tmp_name);
-    return 1;
-  }
-  const uint64_t n_words = list ? gt4hip_list_n_words (list) : 0;
-  uint64_t total_count = 0;
-  int bad = 0;
-  if (n_words && gt4hip_list_sum_counts (ctx, list, &total_count)) bad = 1;
-  void *buf = n_words ? malloc ((size_t) (n_words < DOWNLOAD_CHUNK ? n_words : DOWNLOAD_CHUNK) * 12u) : NULL;
-  if (n_words && !buf) bad = 1;
-  for (uint64_t first = 0; first < n_words && !bad; first += DOWNLOAD_CHUNK) {
-    const uint64_t cnt = n_words - first < DOWNLOAD_CHUNK ? n_words - first : DOWNLOAD_CHUNK;
-    if (gt4hip_list_download_range (ctx, list, first, cnt, buf)) {
-      fprintf (stderr, "Error: reading results back from the GPU failed: %s\n", gt4hip_last_error (ctx));
-      bad = 1;
-    } else if (gt4_listwriter_append (&w, buf, cnt)) {
-      fprintf (stderr, "Error: writing %s failed: %s\n", tmp_name, strerror (errno));
-      bad = 1;
-    }
-  }
-  free (buf);
-  if (bad) {
-    gt4_listwriter_abort (&w);
-    unlink (tmp_name);
-    return 1;
-  }
-  if (gt4_listwriter_finish (&w, n_words, total_count)) {
-    fprintf (stderr, "Error: writing %s failed: %s\n", tmp_name, strerror (errno));
-    unlink (tmp_name);
-    return 1;
-  }
-  if (rename (tmp_name, final_name)) fprintf (stderr, "Cannot rename %s to %s\n", tmp_name, final_name);
-  return 0;
-}
-
 int main (int argc, const char *argv[])
 {
   static Options o;
@@ -442,10 +377,13 @@ int main (int argc, const char *argv[])
     text_close (&texts[i]);
   }
   gt4hip_list *result = collate (ctx, &ls);
-  char tmp_name[1024], out_name[1024];
-  snprintf (tmp_name, sizeof tmp_name, "%s_%u.list.tmp", o.outputname, o.wordlength);
+  char out_name[1024];
   snprintf (out_name, sizeof out_name, "%s_%u.list", o.outputname, o.wordlength);
-  if (write_list_file (ctx, result, o.wordlength, tmp_name, out_name)) return 1;
+  /* no word at all: a header alone (reference :341-348); a rename that fails is reported and the run ends with 0, as there */
+  const uint64_t n_words = result ? gt4hip_list_n_words (result) : 0;
+  uint64_t total_count = 0;
+  if (n_words && gt4hip_list_sum_counts (ctx, result, &total_count)) return 1;
+  if (gt4_cli_write_list_file (ctx, result, o.wordlength, n_words, total_count, out_name, 0666, "") == 1) return 1;
   if (result) gt4hip_list_free (result);
   gt4hip_destroy (ctx);
   return 0;

@@ -24,6 +24,8 @@
  *   - the list must fit one device (as for glistcompare -mm); larger is an out-of-memory error;
  *   - --words-only (not in the reference) prints the packed query words -q / -f / -s / -l would look up,
  *     one decimal number per line, and opens no device: for tests of the parsers.
+ * Argv is read in parse_argv() alone.  No environment variable is read here: GT4HIP_DEVICE picks the device of the
+ * library's default context, GT4HIP_HBM_LIMIT and GT4HIP_VERBOSE act inside the multi-list calls (gt4_setops.c).
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -33,6 +35,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "gt4_cli.h"
 #include "gt4_listfile.h"
 #include "gt4_set_operations.h"
 #include "gt4hip.h"
@@ -46,10 +49,7 @@ enum { OPT_VERSION, OPT_HELP, OPT_SEQFILE, OPT_LISTFILE, OPT_QUERYFILE, OPT_QUER
        OPT_STATS, OPT_MEDIAN, OPT_DISTRO, OPT_GC, OPT_FILES, OPT_SEQUENCES, OPT_LOCATIONS, OPT_3P, OPT_5P, OPT_HEADER, OPT_BLOOM,
        OPT_IS_UNION, OPT_NOSCOUTS, OPT_WORDS_ONLY };
 
-static const struct {
-  const char *name;
-  int opt;
-} OPTIONS[] = {
+static const GT4CliOption OPTIONS[] = {
   { "-v", OPT_VERSION }, { "--version", OPT_VERSION }, { "-h", OPT_HELP }, { "--help", OPT_HELP }, { "-?", OPT_HELP },
   { "-s", OPT_SEQFILE }, { "--seqfile", OPT_SEQFILE }, { "-l", OPT_LISTFILE }, { "--listfile", OPT_LISTFILE },
   { "-f", OPT_QUERYFILE }, { "--queryfile", OPT_QUERYFILE }, { "-q", OPT_QUERY }, { "--query", OPT_QUERY },
@@ -90,22 +90,19 @@ static const char *const HELP_LINES[] = {
   "    -D                        - increase debug level",
 };
 
-static int debug = 0;
-static unsigned int use_3p = 0, use_5p = 0;
-static int words_only = 0;
+/* What argv decides.  parse_argv fills it, validate and open_inputs check it; the jobs only read it. */
+typedef struct {
+  const char *lists[MAX_LISTS];
+  unsigned int n_lists;
+  const char *querystring, *queryfilename, *seqfilename, *querylistfilename;
+  unsigned int nmm, pm3, minfreq, maxfreq, distro, command;
+  int printall, print_header, locations, is_union, use_3p, use_5p, words_only, debug;
+} Options;
 
 static void print_help (int exit_value)
 {
-  fprintf (stderr, "glistquery version %u.%u.%u (%s)\n", GT4_VERSION_MAJOR, GT4_VERSION_MINOR, GT4_VERSION_MICRO, GT4_VERSION_QUALIFIER);
-  for (size_t i = 0; i < sizeof HELP_LINES / sizeof HELP_LINES[0]; i++) fprintf (stderr, "%s\n", HELP_LINES[i]);
+  gt4_cli_print_help (stderr, "glistquery", HELP_LINES, sizeof HELP_LINES / sizeof HELP_LINES[0]);
   exit (exit_value);
-}
-
-static int find_option (const char *arg)
-{
-  for (size_t i = 0; i < sizeof OPTIONS / sizeof OPTIONS[0]; i++)
-    if (!strcmp (arg, OPTIONS[i].name)) return OPTIONS[i].opt;
-  return -1;
 }
 
 /* ------------------------------------------------------------------ words */
@@ -232,17 +229,9 @@ static GT4HipWordList *to_device (const char *name, gt4hip_context **ctx, const 
   return l;
 }
 
-#define CHK(ctx, call)                                                            \
-  do {                                                                            \
-    if ((call) != GT4HIP_OK) {                                                    \
-      fprintf (stderr, "Error: %s: %s\n", #call, gt4hip_last_error (ctx));        \
-      exit (1);                                                                   \
-    }                                                                             \
-  } while (0)
-
 /* ------------------------------------------------------------------ statistics */
 
-static void print_median (const Input *in, gt4hip_context *ctx, const gt4hip_list *dev)
+static void print_median (const Input *in, gt4hip_context *ctx, const gt4hip_list *dev, int debug)
 {
   const uint64_t num_words = in->file.header.n_words;
   uint32_t min, max, med, gmin, gmax;
@@ -293,44 +282,32 @@ static void print_gc (const Input *in, gt4hip_context *ctx, const gt4hip_list *d
   printf ("GC\t%g\n", (double) count / (in->file.header.total_count * in->file.header.word_length));
 }
 
-static void print_full_map (const Input *in)
-{
-  const unsigned int k = in->file.header.word_length;
-  char b[64];
-  for (uint64_t i = 0; i < in->file.header.n_words; i++) {
-    gt4_word2string (b, input_word (in, i), k);
-    fprintf (stdout, "%s\t%u\n", b, input_count (in, i));
-  }
-}
-
 /* ------------------------------------------------------------------ multi-list forms (include/gt4_set_operations.h) */
 
-static unsigned int g_wlen, g_n_lists;
+/* the callbacks' `data`: word length and number of lists; multi_cb's open line (one per word, "\t<list>:<count>" per list) and its word */
+typedef struct { unsigned int wlen, n_lists; int open; uint64_t last; } PrintState;
 
 static unsigned int dump_cb (uint64_t word, uint32_t *counts, void *data)
 {
+  const PrintState *st = (const PrintState *) data;
   char b[64];
-  (void) data;
-  gt4_word2string (b, word, g_wlen);
+  gt4_word2string (b, word, st->wlen);
   fputs (b, stdout);
-  for (unsigned int j = 0; j < g_n_lists; j++) fprintf (stdout, "\t%u", counts[j]);
+  for (unsigned int j = 0; j < st->n_lists; j++) fprintf (stdout, "\t%u", counts[j]);
   fputc ('\n', stdout);
   return 0;
 }
 
-static uint64_t multi_last;
-static int multi_open;
-
 static unsigned int multi_cb (uint64_t word, unsigned int list, uint32_t count, void *data)
 {
-  (void) data;
-  if (!multi_open || word != multi_last) {
+  PrintState *st = (PrintState *) data;
+  if (!st->open || word != st->last) {
     char b[64];
-    if (multi_open) fputc ('\n', stdout);
-    gt4_word2string (b, word, g_wlen);
+    if (st->open) fputc ('\n', stdout);
+    gt4_word2string (b, word, st->wlen);
     fputs (b, stdout);
-    multi_open = 1;
-    multi_last = word;
+    st->open = 1;
+    st->last = word;
   }
   fprintf (stdout, "\t%u:%u", list, count);
   return 0;
@@ -339,8 +316,7 @@ static unsigned int multi_cb (uint64_t word, unsigned int list, uint32_t count, 
 static unsigned int zipper_cb (uint64_t word, uint32_t count, void *data)
 {
   char b[64];
-  (void) data;
-  gt4_word2string (b, word, g_wlen);
+  gt4_word2string (b, word, ((const PrintState *) data)->wlen);
   fprintf (stdout, "%s\t%u\n", b, count);
   return 0;
 }
@@ -351,8 +327,8 @@ typedef struct {
   gt4hip_context *ctx;
   gt4hip_query_index *qindex;
   gt4hip_query_params prm;
-  unsigned int k, min_freq, max_freq;
-  int print_all;
+  const Options *o; /* min / max frequency, --all, --3p, --5p, --words-only */
+  unsigned int k;
   uint64_t *words; /* canonical query words of the batch */
   uint64_t n;
   uint32_t *values;
@@ -375,19 +351,19 @@ static void flush_batch (Searcher *s)
 {
   char b[64];
   if (!s->n) return;
-  if (words_only) {
+  if (s->o->words_only) {
     for (uint64_t i = 0; i < s->n; i++) fprintf (stdout, "%llu\n", (unsigned long long) s->words[i]);
     s->n = 0;
     return;
   }
-  if (!s->print_all) {
+  if (!s->o->printall) {
     CHK (s->ctx, gt4hip_query_lookup (s->ctx, s->qindex, s->words, s->n, &s->prm, s->values, s->found));
     for (uint64_t i = 0; i < s->n; i++) {
       if (s->found[i]) {
-        if (s->values[i] < s->min_freq || s->values[i] > s->max_freq) continue;
+        if (s->values[i] < s->o->minfreq || s->values[i] > s->o->maxfreq) continue;
         gt4_word2string (b, s->words[i], s->k);
         fprintf (stdout, "%s\t%u\n", b, s->values[i]);
-      } else if (!s->min_freq) {
+      } else if (!s->o->minfreq) {
         gt4_word2string (b, s->words[i], s->k);
         fprintf (stdout, "%s\t0\n", b);
       }
@@ -434,7 +410,7 @@ static void flush_batch (Searcher *s)
     }
     /* the reference's return value: with mismatches the summed count, without them "found" */
     const int none = s->prm.n_mm ? sum == 0 : m == 0;
-    if (none && !s->min_freq) {
+    if (none && !s->o->minfreq) {
       gt4_word2string (b, s->words[i], s->k);
       fprintf (stdout, "%s\t0\n", b);
     }
@@ -447,21 +423,21 @@ static void flush_batch (Searcher *s)
 /* search_one_word: the query is looked up as its canonical form */
 static void search_one_word (Searcher *s, uint64_t word)
 {
-  s->words[s->n++] = words_only ? word : canonical_word (word, s->k);
+  s->words[s->n++] = s->o->words_only ? word : canonical_word (word, s->k);
   if (s->n == QUERY_BATCH) flush_batch (s);
 }
 
 /* the length rules of search_one_query_string / search_n_query_strings; 0: *word set */
-static int query_string_word (const char *who, const char *c, unsigned int k, uint64_t *word)
+static int query_string_word (const char *who, const char *c, const Searcher *s, uint64_t *word)
 {
-  const unsigned int len = (unsigned int) strlen (c);
+  const unsigned int len = (unsigned int) strlen (c), k = s->k;
   if (len != k) {
     if (len < k) {
       fprintf (stderr, "%s: Word too short (%u < %u)\n", who, k, len);
       return 1;
-    } else if (use_3p) {
+    } else if (s->o->use_3p) {
       *word = string_to_word (c + (len - k), k);
-    } else if (use_5p) {
+    } else if (s->o->use_5p) {
       *word = string_to_word (c, k);
     } else {
       fprintf (stderr, "%s: Wrong query length (%u != %u) - use --3p or --5p\n", who, k, len);
@@ -492,7 +468,7 @@ static int search_n_query_strings (Searcher *s, const char *queryfile)
     c[i] = 0;
     while (val > 0 && val != '\n') val = fgetc (ifs);
     while (val > 0 && val < 'A') val = fgetc (ifs);
-    if (query_string_word ("search_n_query_strings", c, s->k, &word)) {
+    if (query_string_word ("search_n_query_strings", c, s, &word)) {
       flush_batch (s); /* what the reference had printed before it stopped */
       return 1;        /* (the reference leaves the file open too) */
     }
@@ -513,8 +489,7 @@ static int search_fasta (Searcher *s, const char *fname)
     return 1;
   }
   const int c0 = fgetc (ifs), c1 = fgetc (ifs);
-  if (c0 == 0x1f && c1 == 0x8b) {
-    fprintf (stderr, "Error: %s is gzip-compressed: decompress it first (compressed sequence files are not read)\n", fname);
+  if (gt4_cli_refuse_gzip (fname, c0, c1)) {
     fclose (ifs);
     return 1;
   }
@@ -618,7 +593,7 @@ done:
   return result;
 }
 
-/* ------------------------------------------------------------------ main */
+/* ------------------------------------------------------------------ argv, validation, inputs */
 
 /* the value of -min / -max; NULL at the end of argv: a warning, and the default stays */
 static void parse_frequency (const char *value, const char *which, unsigned int *freq)
@@ -635,34 +610,18 @@ static void parse_frequency (const char *value, const char *which, unsigned int 
   }
 }
 
-/* The magic number of a list.  1: the file cannot be opened; a file shorter than the number has code 0 */
-static int list_code (const char *name, uint32_t *code)
+/* argv (reference :124-252; every quirk of its hand-rolled loop is kept) */
+static void parse_argv (int argc, const char *argv[], Options *o)
 {
-  FILE *ifs = fopen (name, "r");
-  if (!ifs) return 1;
-  if (fread (code, 4, 1, ifs) != 1) *code = 0;
-  fclose (ifs);
-  return 0;
-}
-
-int main (int argc, const char *argv[])
-{
-  int argidx, v = 0;
-  unsigned int n_lists = 0, invalid = 0;
-  const char *lists[MAX_LISTS];
-  const char *querystring = NULL, *queryfilename = NULL, *seqfilename = NULL, *querylistfilename = NULL;
-  unsigned int nmm = 0, pm3 = 0;
   char *end;
-  int printall = 0, print_header = 0, locations = 0;
-  unsigned int minfreq = 0, maxfreq = UINT_MAX, distro = 0, command = CMD_QUERY, is_union = 0;
-
-  for (argidx = 1; argidx < argc; argidx++) {
+  o->maxfreq = UINT_MAX; /* every other default is 0, CMD_QUERY among them */
+  for (int argidx = 1; argidx < argc; argidx++) {
     const char *arg = argv[argidx];
-    const int opt = find_option (arg);
+    const int opt = gt4_cli_find_option (OPTIONS, sizeof OPTIONS / sizeof OPTIONS[0], arg);
     switch (opt) {
     case OPT_VERSION:
-      fprintf (stdout, "glistquery version %u.%u.%u (%s)\n", GT4_VERSION_MAJOR, GT4_VERSION_MINOR, GT4_VERSION_MICRO, GT4_VERSION_QUALIFIER);
-      return 0;
+      gt4_cli_print_version (stdout, "glistquery");
+      exit (0);
     case OPT_HELP: print_help (0); break;
     case OPT_SEQFILE:
     case OPT_LISTFILE:
@@ -674,10 +633,10 @@ int main (int argc, const char *argv[])
         argidx += 1;
         continue;
       }
-      if (opt == OPT_SEQFILE) seqfilename = argv[argidx + 1];
-      else if (opt == OPT_LISTFILE) querylistfilename = argv[argidx + 1];
-      else if (opt == OPT_QUERYFILE) queryfilename = argv[argidx + 1];
-      else querystring = argv[argidx + 1];
+      if (opt == OPT_SEQFILE) o->seqfilename = argv[argidx + 1];
+      else if (opt == OPT_LISTFILE) o->querylistfilename = argv[argidx + 1];
+      else if (opt == OPT_QUERYFILE) o->queryfilename = argv[argidx + 1];
+      else o->querystring = argv[argidx + 1];
       argidx += 1;
       break;
     case OPT_PM:
@@ -686,210 +645,250 @@ int main (int argc, const char *argv[])
       if (argidx >= argc) print_help (1);
       const unsigned int val = (unsigned int) strtol (argv[argidx], &end, 10);
       if (*end || val > (opt == OPT_PM ? 32u : 16u)) print_help (1);
-      if (opt == OPT_PM) pm3 = val;
-      else nmm = val;
+      if (opt == OPT_PM) o->pm3 = val;
+      else o->nmm = val;
       break;
     }
-    case OPT_MIN: parse_frequency (argv[++argidx], "minimum", &minfreq); break;
-    case OPT_MAX: parse_frequency (argv[++argidx], "maximum", &maxfreq); break;
-    case OPT_DEBUG: debug += 1; break;
-    case OPT_ALL: printall = 1; break;
-    case OPT_STATS: command = CMD_STATS; break;
-    case OPT_MEDIAN: command = CMD_MEDIAN; break;
+    case OPT_MIN: parse_frequency (argv[++argidx], "minimum", &o->minfreq); break;
+    case OPT_MAX: parse_frequency (argv[++argidx], "maximum", &o->maxfreq); break;
+    case OPT_DEBUG: o->debug += 1; break;
+    case OPT_ALL: o->printall = 1; break;
+    case OPT_STATS: o->command = CMD_STATS; break;
+    case OPT_MEDIAN: o->command = CMD_MEDIAN; break;
     case OPT_DISTRO:
       if (argidx + 1 >= argc) print_help (1);
       argidx += 1;
-      distro = (unsigned int) strtol (argv[argidx], &end, 10);
-      command = CMD_DISTRO;
+      o->distro = (unsigned int) strtol (argv[argidx], &end, 10);
+      o->command = CMD_DISTRO;
       break;
-    case OPT_GC: command = CMD_GC; break;
-    case OPT_FILES: command = CMD_FILES; break;
-    case OPT_SEQUENCES: command = CMD_SEQUENCES; break;
-    case OPT_LOCATIONS: locations = 1; break;
-    case OPT_3P: use_3p = 1; break;
-    case OPT_5P: use_5p = 1; break;
-    case OPT_HEADER: print_header = 1; break;
-    case OPT_BLOOM: break;    /* accepted and ignored */
+    case OPT_GC: o->command = CMD_GC; break;
+    case OPT_FILES: o->command = CMD_FILES; break;
+    case OPT_SEQUENCES: o->command = CMD_SEQUENCES; break;
+    case OPT_LOCATIONS: o->locations = 1; break;
+    case OPT_3P: o->use_3p = 1; break;
+    case OPT_5P: o->use_5p = 1; break;
+    case OPT_HEADER: o->print_header = 1; break;
+    case OPT_BLOOM:
     case OPT_NOSCOUTS: break; /* accepted and ignored */
-    case OPT_IS_UNION: is_union = 1; break;
-    case OPT_WORDS_ONLY: words_only = 1; break;
+    case OPT_IS_UNION: o->is_union = 1; break;
+    case OPT_WORDS_ONLY: o->words_only = 1; break;
     default:
       if (arg[0] != '-') {
-        if (n_lists == MAX_LISTS) {
+        if (o->n_lists == MAX_LISTS) {
           fprintf (stderr, "Error: more than %d lists\n", MAX_LISTS);
           exit (1);
         }
-        lists[n_lists++] = arg;
+        o->lists[o->n_lists++] = arg;
       } else {
         fprintf (stderr, "Error: Unknown argument: %s!\n", arg);
         print_help (1);
       }
     }
   }
+}
 
-  if (!n_lists) {
+static void validate (const Options *o)
+{
+  if (!o->n_lists) {
     fprintf (stderr, "No list/index files specified!\n");
     print_help (1);
   }
-  if (locations || command == CMD_FILES || command == CMD_SEQUENCES) {
+  if (o->locations || o->command == CMD_FILES || o->command == CMD_SEQUENCES) {
     fprintf (stderr, "Error: %s is not supported: the location tables of an index are not loaded\n",
-             command == CMD_FILES ? "--files" : command == CMD_SEQUENCES ? "--sequences" : "--locations");
+             o->command == CMD_FILES ? "--files" : o->command == CMD_SEQUENCES ? "--sequences" : "--locations");
     exit (1);
   }
+}
 
-  /* Map every list / index (headers only so far) and test some errors */
-  static Input maps[MAX_LISTS];
-  unsigned int wlen = 0;
-  for (unsigned int i = 0; i < n_lists; i++) {
+/* The magic number of a list.  1: the file cannot be opened; a file shorter than the number has code 0 */
+static int list_code (const char *name, uint32_t *code)
+{
+  FILE *ifs = fopen (name, "r");
+  if (!ifs) return 1;
+  if (fread (code, 4, 1, ifs) != 1) *code = 0;
+  fclose (ifs);
+  return 0;
+}
+
+/* Maps every list / index and the -l query list (headers only so far) and returns the word length.  A list that cannot
+ * be opened ends the program at once; every other fault is reported for every file, then exit 1. */
+static unsigned int open_inputs (const Options *o, Input *maps, Input *query_input)
+{
+  unsigned int wlen = 0, invalid = 0;
+  for (unsigned int i = 0; i < o->n_lists; i++) {
     uint32_t code = 0;
     int ok = 0;
-    if (list_code (lists[i], &code)) {
-      fprintf (stderr, "Cannot open list %s\n", lists[i]);
+    if (list_code (o->lists[i], &code)) {
+      fprintf (stderr, "Cannot open list %s\n", o->lists[i]);
       exit (1);
     }
     if (code == GT4_LIST_CODE_VALUE || code == GT4_INDEX_CODE_VALUE) {
-      ok = !input_open (&maps[i], lists[i], code);
-      if (ok && debug && code == GT4_LIST_CODE_VALUE) fprintf (stderr, "List %s loaded\n", lists[i]);
+      ok = !input_open (&maps[i], o->lists[i], code);
+      if (ok && o->debug && code == GT4_LIST_CODE_VALUE) fprintf (stderr, "List %s loaded\n", o->lists[i]);
     } else {
-      fprintf (stderr, "Error: %s is not a valid GenomeTester4 list/index file\n", lists[i]);
+      fprintf (stderr, "Error: %s is not a valid GenomeTester4 list/index file\n", o->lists[i]);
       invalid = 1;
     }
     if (!ok) {
-      fprintf (stderr, "Error: %s is invalid or corrupted\n", lists[i]);
+      fprintf (stderr, "Error: %s is invalid or corrupted\n", o->lists[i]);
       invalid = 1;
     } else if (!wlen) {
       wlen = maps[i].file.header.word_length;
     } else if (maps[i].file.header.word_length != wlen) {
-      fprintf (stderr, "Error: %s has different word length %u (first list had %u)\n", lists[i], maps[i].file.header.word_length, wlen);
+      fprintf (stderr, "Error: %s has different word length %u (first list had %u)\n", o->lists[i], maps[i].file.header.word_length, wlen);
       invalid = 1;
     }
   }
-  static Input query_input;
-  if (querylistfilename) {
+  if (o->querylistfilename) {
     uint32_t code = 0;
-    if (list_code (querylistfilename, &code) || (code != GT4_LIST_CODE_VALUE && code != GT4_INDEX_CODE_VALUE) ||
-        input_open (&query_input, querylistfilename, code)) {
-      fprintf (stderr, "Error: %s is invalid or corrupted\n", querylistfilename);
+    if (list_code (o->querylistfilename, &code) || (code != GT4_LIST_CODE_VALUE && code != GT4_INDEX_CODE_VALUE) ||
+        input_open (query_input, o->querylistfilename, code)) {
+      fprintf (stderr, "Error: %s is invalid or corrupted\n", o->querylistfilename);
       invalid = 1;
-    } else if (query_input.file.header.word_length != wlen) {
-      fprintf (stderr, "Error: %s has different word length %u (first list had %u)\n", querylistfilename, query_input.file.header.word_length, wlen);
+    } else if (query_input->file.header.word_length != wlen) {
+      fprintf (stderr, "Error: %s has different word length %u (first list had %u)\n", o->querylistfilename, query_input->file.header.word_length, wlen);
       invalid = 1;
     }
   }
   if (invalid) exit (1);
+  return wlen;
+}
 
-  /* Generic methods */
-  if (command == CMD_STATS) {
-    for (unsigned int i = 0; i < n_lists; i++) print_list_header (&maps[i]);
-    exit (0);
-  } else if (command == CMD_MEDIAN || command == CMD_DISTRO || command == CMD_GC) {
-    for (unsigned int i = 0; i < n_lists; i++) {
-      gt4hip_context *ctx;
-      const gt4hip_list *dev;
-      GT4HipWordList *l = to_device (lists[i], &ctx, &dev);
-      if (command == CMD_MEDIAN) print_median (&maps[i], ctx, dev);
-      else if (command == CMD_DISTRO) print_distro (ctx, dev, distro + 1);
-      else print_gc (&maps[i], ctx, dev);
-      gt4_hip_word_list_delete (l);
-    }
-    exit (0);
+/* ------------------------------------------------------------------ the jobs; each returns the exit code */
+
+/* --stat: the headers, no device */
+static int run_stat (const Options *o, const Input *maps)
+{
+  for (unsigned int i = 0; i < o->n_lists; i++) print_list_header (&maps[i]);
+  return 0;
+}
+
+/* --median / --distribution / --gc, list by list */
+static int run_statistics (const Options *o, const Input *maps)
+{
+  for (unsigned int i = 0; i < o->n_lists; i++) {
+    gt4hip_context *ctx;
+    const gt4hip_list *dev;
+    GT4HipWordList *l = to_device (o->lists[i], &ctx, &dev);
+    if (o->command == CMD_MEDIAN) print_median (&maps[i], ctx, dev, o->debug);
+    else if (o->command == CMD_DISTRO) print_distro (ctx, dev, o->distro + 1);
+    else print_gc (&maps[i], ctx, dev);
+    gt4_hip_word_list_delete (l);
   }
+  return 0;
+}
 
-  g_wlen = wlen;
-  g_n_lists = n_lists;
-
-  /* If no options is given print all lists/indices */
-  if (!seqfilename && !querylistfilename && !queryfilename && !querystring) {
-    if (n_lists > 1) {
-      if (print_header) {
-        fprintf (stdout, "KMER");
-        for (unsigned int i = 0; i < n_lists; i++) fprintf (stdout, "\t%s", lists[i]);
-        fprintf (stdout, "\n");
-      }
-      static GT4HipWordList *objs[MAX_LISTS];
-      for (unsigned int i = 0; i < n_lists; i++) objs[i] = to_device (lists[i], NULL, NULL);
-      const unsigned int r = is_union ? gt4_is_union (objs, n_lists, dump_cb, NULL) : gt4_union (objs, n_lists, dump_cb, NULL);
-      if (r) {
-        fprintf (stderr, "Error: the union of the lists failed (%u)\n", r);
-        exit (1);
-      }
-    } else {
-      print_full_map (&maps[0]);
-    }
-    exit (0);
+/* no query option, one list: the mapped records, no device */
+static int run_dump (const Input *in)
+{
+  char b[64];
+  for (uint64_t i = 0; i < in->file.header.n_words; i++) {
+    gt4_word2string (b, input_word (in, i), in->file.header.word_length);
+    fprintf (stdout, "%s\t%u\n", b, input_count (in, i));
   }
+  return 0;
+}
 
-  /* Search one list against multiple */
-  if (querylistfilename && n_lists > 1) {
-    if (nmm || pm3) {
-      fprintf (stderr, "Error: Searching multiple lists is incompatible with mismatches\n");
-      exit (1);
-    }
-    static GT4HipWordList *objs[MAX_LISTS];
-    GT4HipWordList *q = to_device (querylistfilename, NULL, NULL);
-    for (unsigned int i = 0; i < n_lists; i++) objs[i] = to_device (lists[i], NULL, NULL);
-    const unsigned int result = gt4_search_lists_multi (q, objs, n_lists, multi_cb, NULL);
-    if (multi_open) fputc ('\n', stdout);
-    exit ((int) result);
+/* no query option, several lists: every word of their union (--is_union: gt4_is_union) with its count in each */
+static int run_union_dump (const Options *o, unsigned int wlen)
+{
+  static GT4HipWordList *objs[MAX_LISTS];
+  PrintState st = { .wlen = wlen, .n_lists = o->n_lists };
+  if (o->print_header) {
+    fprintf (stdout, "KMER");
+    for (unsigned int i = 0; i < o->n_lists; i++) fprintf (stdout, "\t%s", o->lists[i]);
+    fprintf (stdout, "\n");
   }
+  for (unsigned int i = 0; i < o->n_lists; i++) objs[i] = to_device (o->lists[i], NULL, NULL);
+  const unsigned int r = (o->is_union ? gt4_is_union : gt4_union) (objs, o->n_lists, dump_cb, &st);
+  if (r) fprintf (stderr, "Error: the union of the lists failed (%u)\n", r);
+  return r != 0;
+}
 
-  if (n_lists > 1) {
-    fprintf (stderr, "Error: Query is incompatible with multiple lists/indices\n");
-    exit (1);
-  }
-  if (nmm + pm3 > wlen) {
-    fprintf (stderr, "Error: Number of mismatches (%u) and 3' perfect match (%u) are longer than word length %u\n", nmm, pm3, wlen);
+/* -l against several lists; the query list goes to the device first */
+static int run_multi_search (const Options *o, unsigned int wlen)
+{
+  static GT4HipWordList *objs[MAX_LISTS];
+  PrintState st = { .wlen = wlen, .n_lists = o->n_lists };
+  if (o->nmm || o->pm3) {
+    fprintf (stderr, "Error: Searching multiple lists is incompatible with mismatches\n");
     return 1;
   }
+  GT4HipWordList *q = to_device (o->querylistfilename, NULL, NULL);
+  for (unsigned int i = 0; i < o->n_lists; i++) objs[i] = to_device (o->lists[i], NULL, NULL);
+  const unsigned int result = gt4_search_lists_multi (q, objs, o->n_lists, multi_cb, &st);
+  if (st.open) fputc ('\n', stdout);
+  return (int) result;
+}
 
-  /* one list against a query list without mismatches: the zipper (min / max / --all do not apply, as in the reference) */
-  if (!querystring && !queryfilename && !seqfilename && querylistfilename && !nmm && !words_only) {
-    GT4HipWordList *l = to_device (lists[0], NULL, NULL);
-    GT4HipWordList *q = to_device (querylistfilename, NULL, NULL);
-    const unsigned int r = gt4_search_list_zipper (l, q, zipper_cb, NULL);
-    if (r) {
-      fprintf (stderr, "Error: the search of %s in %s failed (%u)\n", querylistfilename, lists[0], r);
-      exit (1);
-    }
-    exit (0);
-  }
+/* -l against one list without mismatches: the list goes to the device first (min / max / --all do not apply, as in the reference) */
+static int run_zipper (const Options *o, unsigned int wlen)
+{
+  PrintState st = { .wlen = wlen, .n_lists = 1 };
+  GT4HipWordList *l = to_device (o->lists[0], NULL, NULL);
+  GT4HipWordList *q = to_device (o->querylistfilename, NULL, NULL);
+  const unsigned int r = gt4_search_list_zipper (l, q, zipper_cb, &st);
+  if (r) fprintf (stderr, "Error: the search of %s in %s failed (%u)\n", o->querylistfilename, o->lists[0], r);
+  return r != 0;
+}
 
-  Searcher s;
-  memset (&s, 0, sizeof s);
-  s.k = wlen;
-  s.prm.n_mm = nmm;
-  s.prm.pm_3 = pm3;
-  s.prm.canonize = 1;
-  s.min_freq = minfreq;
-  s.max_freq = maxfreq;
-  s.print_all = printall;
+/* -q / -f / -s / -l against one list, in batches; --words-only prints the words and opens no device */
+static int run_lookups (const Options *o, unsigned int wlen, const Input *query_input)
+{
+  int v = 0;
+  Searcher s = { .o = o, .k = wlen, .prm = { .n_mm = o->nmm, .pm_3 = o->pm3, .canonize = 1 } };
   s.words = (uint64_t *) or_oom (malloc ((size_t) QUERY_BATCH * 8), "query batch");
   s.values = (uint32_t *) or_oom (malloc ((size_t) QUERY_BATCH * 4), "query batch");
   s.found = (uint8_t *) or_oom (malloc (QUERY_BATCH), "query batch");
-  s.hit_capacity = printall ? QUERY_BATCH : 0;
-  s.hits = printall ? (gt4hip_query_hit *) or_oom (malloc ((size_t) s.hit_capacity * sizeof (gt4hip_query_hit)), "query batch") : NULL;
+  s.hit_capacity = o->printall ? QUERY_BATCH : 0;
+  s.hits = o->printall ? (gt4hip_query_hit *) or_oom (malloc ((size_t) s.hit_capacity * sizeof (gt4hip_query_hit)), "query batch") : NULL;
   GT4HipWordList *l = NULL;
-  if (!words_only) {
+  if (!o->words_only) {
     const gt4hip_list *dev = NULL;
-    l = to_device (lists[0], &s.ctx, &dev);
+    l = to_device (o->lists[0], &s.ctx, &dev);
     CHK (s.ctx, gt4hip_query_index_create (s.ctx, dev, &s.qindex));
   }
-
-  if (querystring) {
+  if (o->querystring) {
     uint64_t word;
-    v = query_string_word ("search_one_query_string", querystring, wlen, &word);
+    v = query_string_word ("search_one_query_string", o->querystring, &s, &word);
     if (!v) search_one_word (&s, word);
-  } else if (queryfilename) {
-    v = search_n_query_strings (&s, queryfilename);
-  } else if (seqfilename) {
-    v = search_fasta (&s, seqfilename);
-  } else if (querylistfilename) {
-    for (uint64_t i = 0; i < query_input.file.header.n_words; i++) search_one_word (&s, input_word (&query_input, i));
+  } else if (o->queryfilename) {
+    v = search_n_query_strings (&s, o->queryfilename);
+  } else if (o->seqfilename) {
+    v = search_fasta (&s, o->seqfilename);
+  } else if (o->querylistfilename) {
+    for (uint64_t i = 0; i < query_input->file.header.n_words; i++) search_one_word (&s, input_word (query_input, i));
   }
-  flush_batch (&s);
+  flush_batch (&s); /* what was looked up before a parser error is printed all the same */
   fflush (stdout);
   if (s.qindex) gt4hip_query_index_free (s.qindex);
   if (l) gt4_hip_word_list_delete (l);
-  if (v) return v;
-  exit (0);
+  free (s.words);
+  free (s.values);
+  free (s.found);
+  free (s.hits);
+  return v;
+}
+
+int main (int argc, const char *argv[])
+{
+  static Options o;
+  static Input maps[MAX_LISTS], query_input;
+  parse_argv (argc, argv, &o);
+  validate (&o);
+  const unsigned int wlen = open_inputs (&o, maps, &query_input);
+  if (o.command == CMD_STATS) return run_stat (&o, maps);
+  if (o.command != CMD_QUERY) return run_statistics (&o, maps); /* median, distribution or gc: validate refused the rest */
+  if (!o.seqfilename && !o.querylistfilename && !o.queryfilename && !o.querystring) return o.n_lists > 1 ? run_union_dump (&o, wlen) : run_dump (&maps[0]);
+  if (o.querylistfilename && o.n_lists > 1) return run_multi_search (&o, wlen);
+  if (o.n_lists > 1) {
+    fprintf (stderr, "Error: Query is incompatible with multiple lists/indices\n");
+    return 1;
+  }
+  if (o.nmm + o.pm3 > wlen) {
+    fprintf (stderr, "Error: Number of mismatches (%u) and 3' perfect match (%u) are longer than word length %u\n", o.nmm, o.pm3, wlen);
+    return 1;
+  }
+  if (!o.querystring && !o.queryfilename && !o.seqfilename && !o.nmm && !o.words_only) return run_zipper (&o, wlen);
+  return run_lookups (&o, wlen, &query_input);
 }

@@ -1,6 +1,6 @@
 /*
  * gt4hip_stub.c -- TEST INFRASTRUCTURE ONLY: a CPU stand-in for the part of include/gt4hip.h that the
- * C host (csrc/gt4_glistcompare_cli.c, gt4_shard.c, gt4_listfile.c) calls, so that the host's
+ * C host (csrc/gt4_glistcompare_cli.c, gt4_cli.c, gt4_shard.c, gt4_listfile.c) calls, so that the host's
  * argv handling, key-range planning, fork / barrier / semaphore pipeline, shared totals, pwrite
  * extents, header back-patching and failure paths run WITHOUT a GPU -- under AddressSanitizer,
  * UndefinedBehaviorSanitizer and ThreadSanitizer, with two or three worker processes

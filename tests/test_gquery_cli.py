@@ -91,8 +91,9 @@ def test_parsers_give_the_model_s_words(name, workdir):
 
 
 def test_host_source_names_no_reference_file():
-    src = open(os.path.join(U.ROOT, "genometester4_amd", "csrc", "gt4_glistquery_cli.c")).read()
-    assert "#include \"gt4hip.h\"" in src and "word-map.h" not in src
+    for name in ("gt4_glistquery_cli.c", "gt4_cli.c"):
+        src = open(os.path.join(U.ROOT, "genometester4_amd", "csrc", name)).read()
+        assert "#include \"gt4hip.h\"" in src and "word-map.h" not in src, name
 
 
 @pytest.mark.gpu

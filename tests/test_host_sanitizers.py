@@ -1,5 +1,6 @@
 """The C host of the product under AddressSanitizer + UndefinedBehaviorSanitizer and under
-ThreadSanitizer, WITHOUT a GPU: csrc/gt4_glistcompare_cli.c, gt4_shard.c (key-range plan, fork, barriers,
+ThreadSanitizer, WITHOUT a GPU: csrc/gt4_glistcompare_cli.c, gt4_cli.c (what the three command lines share: the resident
+multi_* cases write their output through its list writer), gt4_shard.c (key-range plan, fork, barriers,
 semaphore pipeline, shared totals, pwrite extents, header back-patching, failure paths) and
 gt4_listfile.c linked against tests/harness/gt4hip_stub.c -- a CPU stand-in for the device layer that
 runs the set operations through the CPU oracle.  The golden reference invocations are replayed resident (no worker: the
