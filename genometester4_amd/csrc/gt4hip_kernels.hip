@@ -18,13 +18,14 @@
  *                     with 16-byte stores.
  *   K3 k_scan_*       tile-count scan for the two-pass fallback.
  *   K0 k_generate     synthetic ascending lists written straight into HBM (bench only).
+ *
+ * Which k_pair_merge<...> instantiation a call takes is decided in gt4hip_pair_variant.h (pair_variant); pair_kernel, at
+ * the bottom of this file, turns that choice into the kernel's address for the launch and for the occupancy query.
  */
 #define GT4_RESOLVE_LOOKBACK 3
 #include "gt4hip_device.h"
 
-#define GT4_IPT_UNION 4 /* 6 (one staging slot written out late) measured 3 % slower than 4 with two slots */
-#define GT4_IPT_INTERSECT 6
-#define GT4_IPT_INTERSECT_SMALL 4 /* positions per thread of the 512-thread intersection (experiments: 6) */
+#include <type_traits>
 
 namespace gt4 {
 
@@ -204,23 +205,6 @@ __global__ void k_partition (const u32 *__restrict__ A, u64 nA, const u32 *__res
  * Keys are unique inside a list (reference precondition), so "both" pairs are found by the match
  * test alone; the B record of a pair keeps nothing (its A partner carries both counts).
  */
-/* launch bound (waves per SIMD): count-only kernels of the small geometry fit 85 VGPRs and 26 KB of
- * LDS -> three workgroups per CU; everything else runs at 4 waves per SIMD */
-__host__ __device__ constexpr int merge_waves_per_simd (int nt, int mode, int ops = 0, int fast = 0)
-{
-  /* the small geometry's folded intersection fits 80 registers and 50 KB too: three workgroups per CU */
-  return (nt == 512 && (mode == MODE_COUNT || (ops == 2 && fast == 1 && GT4_IPT_INTERSECT_SMALL <= 4))) ? 6 : 4;
-}
-
-/* records per thread: an intersection does per-record work on the A half of a tile only and
- * stages at most half a tile, so its tiles are 1.5x as long (6 positions per thread, 6080 records:
- * the per-tile costs -- barriers, ring, scan, fetch set-up -- are paid two thirds as often) */
-__host__ __device__ constexpr int merge_ipt (int nt, int ops_class)
-{
-  return (nt == 1024 && ops_class == 2) ? GT4_IPT_INTERSECT
-         : ((nt == 1024 && ops_class == 1) ? GT4_IPT_UNION : ((nt == 512 && ops_class == 2) ? GT4_IPT_INTERSECT_SMALL : MERGE_VT)); /* 0 (any) and 4 (complement): MERGE_VT */
-}
-
 /* staging layout of a kernel's LDS (third parameter of RankShared) */
 enum : int { STAGE_NONE = 0, STAGE_UNION = 1, STAGE_INTRSEC = 2, STAGE_ANY = 3, STAGE_UNION_LATE = 4, STAGE_COMPLEMENT = 5 };
 
@@ -481,7 +465,7 @@ k_pair_merge (const u32 *__restrict__ A, u64 nA, const u32 *__restrict__ B, u64 
   constexpr bool OPAQUE_TID = OPS == 0 && !(FAST == 1 && (OPSET == 3 || OPSET == 5) && MODE != MODE_COUNT);
   int tid = threadIdx.x, lane = tid & (WAVE - 1); /* (not const: OPAQUE_TID) */
   const int wid = __builtin_amdgcn_readfirstlane (tid / WAVE); /* wave-uniform: scalar branches on it */
-  static_assert (OPSET == 0 || OPS == 0, "a compile-time stream set belongs to the any-combination kernel");
+  static_assert (pair_variant_exists ({ NT, IPT, MODE, OPS, FAST, OPSET }), "not an instantiation the selection can return (a compile-time stream set belongs to the any-combination kernel)");
   const u32 ops = OPS ? (u32) OPS : (OPSET ? (u32) OPSET : p.ops);
   /* every "both" pair is evaluated at its A record, so A records always matter; B records only
    * where a B-only key can be kept (union, diff2) */
@@ -1276,141 +1260,67 @@ hipError_t launch_partition (hipStream_t s, const uint32_t *A, uint64_t nA, cons
   return hipGetLastError ();
 }
 
-/* Two workgroup geometries (measured): count-only calls run fastest with 512 threads
- * and 2048-record tiles (two workgroups per CU overlap their phases); calls that materialise
- * records run fastest with 1024 threads and 4096-record tiles (half as many tiles on the scan
- * chain, whose hop latency is fixed, and room for the staging slots in one workgroup per CU). */
-/* the rule-folded variant a call takes (see FAST in k_pair_merge); 0: the general coefficient form */
-static int fast_variant (int ops_cls, const PairParams &p)
+/* the address of a variant's instantiation: the only place that names one.  lift finds the runtime value among the
+ * template's candidates and hands it on as a type; what pair_variant (gt4hip_pair_variant.h) cannot return is not
+ * instantiated (nullptr) */
+typedef void (*PairKernel) (const u32 *, u64, const u32 *, u64, u64 *, u64, PairParams, PairOutputs, u64 *, PairControl *);
+
+template <int... Vs, class F>
+static PairKernel lift (int v, F f)
 {
-  int fast = 0;
-  if (p.filter == FILTER_REFERENCE) {
-    if (ops_cls == 1 && p.rule[0] == 1u) fast = 1;
-    if (ops_cls == 2 && p.rule[1] == 3u) fast = 1;
-    if (ops_cls == 4 && p.rule[2] == 2u && !p.subtract) fast = 1;
-  } else if (ops_cls == 1 && p.rule[0] == 1u) {
-    fast = p.filter == FILTER_RAW ? 2 : 3; /* N-way union levels: keep every key / keep sums >= cutoff (union_multi, :574) */
-  } else if (ops_cls == 2 && p.rule[1] == RULE_MINZ) {
-    fast = p.filter == FILTER_RAW ? 2 : 3; /* the steps of intersect_multi's chain under its default rule (:655-683) */
-  }
-  /* any combination of outputs with every requested stream on its default rule, any cutoff, no -du */
-  if (ops_cls == 0 && p.filter == FILTER_REFERENCE && !p.subtract && (!(p.ops & 1u) || p.rule[0] == 1u) && (!(p.ops & 2u) || p.rule[1] == 3u) &&
-      (!(p.ops & 4u) || p.rule[2] == 2u) && (!(p.ops & 8u) || p.rule[3] == 2u))
-    fast = 1;
-  return fast;
+  PairKernel k = nullptr;
+  ((v == Vs ? (void) (k = f (std::integral_constant<int, Vs>{})) : (void) 0), ...);
+  return k;
 }
 
-template <int NT, int OPS>
-static hipError_t launch_pair_merge_ops (hipStream_t s, int mode, int grid, const uint32_t *A, uint64_t nA, const uint32_t *B, uint64_t nB,
-                                         const uint64_t *part, uint64_t num_tiles, const PairParams &p, const PairOutputs &o,
-                                         unsigned long long *desc, PairControl *ctl)
+static PairKernel pair_kernel (const PairVariant &v)
 {
-  /* the commonest single-output calls take the variant with the rule folded in (see FAST) */
-  const int fast = fast_variant (OPS, p);
-  constexpr int F1 = 1, F2 = (OPS == 1 || OPS == 2) ? 2 : 0, F3 = (OPS == 1 || OPS == 2) ? 3 : 0;
-#define GT4_LAUNCH_MERGE(M, F) hipLaunchKernelGGL ((k_pair_merge<NT, merge_ipt (NT, OPS), M, OPS, F>), dim3 (grid), dim3 (NT), 0, s, A, nA, B, nB, (u64 *) part, num_tiles, p, o, desc, ctl)
-  if (OPS == 0 && fast == 1 && (p.ops == 3u || p.ops == 5u || p.ops == 15u) && (mode == MODE_COUNT ? NT == 512 : NT == 1024)) {
-    /* the commonest output sets with the default rules (-u -i, -u -d, all four): the stream set is a
-     * compile-time constant */
-#define GT4_LAUNCH_SET(M, SET) hipLaunchKernelGGL ((k_pair_merge<NT, merge_ipt (NT, OPS), M, OPS, 1, (OPS == 0 ? SET : 0)>), dim3 (grid), dim3 (NT), 0, s, A, nA, B, nB, (u64 *) part, num_tiles, p, o, desc, ctl)
-#define GT4_LAUNCH_SET_MODE(SET)                          \
-    do {                                                  \
-      if (mode == MODE_COUNT) GT4_LAUNCH_SET (MODE_COUNT, SET);          \
-      else if (mode == MODE_LOOKBACK) GT4_LAUNCH_SET (MODE_LOOKBACK, SET); \
-      else GT4_LAUNCH_SET (MODE_OFFSETS, SET);            \
-    } while (0)
-    if (p.ops == 3u) GT4_LAUNCH_SET_MODE (3);
-    else if (p.ops == 5u) GT4_LAUNCH_SET_MODE (5);
-    else GT4_LAUNCH_SET_MODE (15);
-#undef GT4_LAUNCH_SET_MODE
-#undef GT4_LAUNCH_SET
-    return hipGetLastError ();
-  }
-  if (mode == MODE_COUNT) {
-    if (fast == 1 && F1) GT4_LAUNCH_MERGE (MODE_COUNT, F1);
-    else if (fast == 2 && F2) GT4_LAUNCH_MERGE (MODE_COUNT, F2);
-    else if (fast == 3 && F3) GT4_LAUNCH_MERGE (MODE_COUNT, F3);
-    else GT4_LAUNCH_MERGE (MODE_COUNT, 0);
-  } else if (mode == MODE_LOOKBACK) {
-    if (fast == 1 && F1) GT4_LAUNCH_MERGE (MODE_LOOKBACK, F1);
-    else if (fast == 2 && F2) GT4_LAUNCH_MERGE (MODE_LOOKBACK, F2);
-    else if (fast == 3 && F3) GT4_LAUNCH_MERGE (MODE_LOOKBACK, F3);
-    else GT4_LAUNCH_MERGE (MODE_LOOKBACK, 0);
-  } else {
-    if (fast == 1 && F1) GT4_LAUNCH_MERGE (MODE_OFFSETS, F1);
-    else if (fast == 2 && F2) GT4_LAUNCH_MERGE (MODE_OFFSETS, F2);
-    else if (fast == 3 && F3) GT4_LAUNCH_MERGE (MODE_OFFSETS, F3);
-    else GT4_LAUNCH_MERGE (MODE_OFFSETS, 0);
-  }
-#undef GT4_LAUNCH_MERGE
-  return hipGetLastError ();
+  return lift<512, 1024> (v.nt, [&] (auto nt) {
+    return lift<MODE_COUNT, MODE_LOOKBACK, MODE_OFFSETS> (v.mode, [&] (auto mode) {
+      return lift<0, 1, 2, 4> (v.cls, [&] (auto cls) {
+        return lift<0, 1, 2, 3> (v.fast, [&] (auto fast) {
+          return lift<0, 3, 5, 15> (v.opset, [&] (auto opset) -> PairKernel {
+            constexpr int NT = decltype (nt)::value, MODE = decltype (mode)::value, OPS = decltype (cls)::value, FAST = decltype (fast)::value,
+                          OPSET = decltype (opset)::value, IPT = merge_ipt (NT, OPS);
+            if constexpr (pair_variant_exists ({ NT, IPT, MODE, OPS, FAST, OPSET }))
+              if (v.ipt == IPT) return k_pair_merge<NT, IPT, MODE, OPS, FAST, OPSET>;
+            return nullptr;
+          });
+        });
+      });
+    });
+  });
 }
 
-template <int NT, int OPS>
-static int blocks_per_cu_ops (int mode)
-{
-  int n = 0;
-  hipError_t e;
-  if (mode == MODE_COUNT) e = hipOccupancyMaxActiveBlocksPerMultiprocessor (&n, k_pair_merge<NT, merge_ipt (NT, OPS), MODE_COUNT, OPS>, NT, 0);
-  else if (mode == MODE_LOOKBACK) e = hipOccupancyMaxActiveBlocksPerMultiprocessor (&n, k_pair_merge<NT, merge_ipt (NT, OPS), MODE_LOOKBACK, OPS>, NT, 0);
-  else e = hipOccupancyMaxActiveBlocksPerMultiprocessor (&n, k_pair_merge<NT, merge_ipt (NT, OPS), MODE_OFFSETS, OPS>, NT, 0);
-  if (e != hipSuccess || n < 1) n = 1;
-  /* never more than the register file admits for the declared launch bounds */
-  const int by_regs = merge_waves_per_simd (NT, mode) * 4 / (NT / 64);
-  if (by_regs >= 1 && n > by_regs) n = by_regs;
-  return n;
-}
-
-/* the kernel specialisation of a set of outputs: one of {union, intersection, first complement} alone, else 0 */
-static int ops_class (uint32_t ops) { return (ops == 1u || ops == 2u || ops == 4u) ? (int) ops : 0; }
-
-uint64_t merge_tile_records (int geom, uint32_t ops)
-{
-  const int nt = geom ? 1024 : 512;
-  return (uint64_t) nt * merge_ipt (nt, ops_class (ops)) - MERGE_TILE_SLACK;
-}
-
-/* workgroups of the merge kernel that are resident per CU (the single-pass path needs every
+/* workgroups of the launched kernel that are resident per CU (the single-pass path needs every
  * worker resident: see k_pair_merge) */
-int merge_blocks_per_cu (int geom, int mode, uint32_t ops, const PairParams *p)
+int merge_blocks_per_cu (const PairVariant &v)
 {
-  /* the small geometry's folded intersection is built for three workgroups per CU (80 registers, 50 KB) */
-  if (!geom && mode != MODE_COUNT && ops == 2u && p && fast_variant (2, *p) == 1) {
-    static int c3 = 0;
-    if (!c3) {
-      int n = 0;
-      const hipError_t e = mode == MODE_LOOKBACK ? hipOccupancyMaxActiveBlocksPerMultiprocessor (&n, k_pair_merge<512, merge_ipt (512, 2), MODE_LOOKBACK, 2, 1>, 512, 0)
-                                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor (&n, k_pair_merge<512, merge_ipt (512, 2), MODE_OFFSETS, 2, 1>, 512, 0);
-      c3 = (e != hipSuccess || n < 1) ? 1 : (n > 3 ? 3 : n);
-    }
-    return c3;
-  }
-  static int cache[2][3][5];
-  const int oi = ops_class (ops);
-  int &c = cache[geom ? 1 : 0][mode][oi];
+  static int cache[2][3][5][4][16]; /* [nt == 1024][mode][cls][fast][opset] */
+  const PairKernel k = pair_kernel (v);
+  if (!k) return 1;
+  int &c = cache[v.nt == 1024][v.mode][v.cls][v.fast][v.opset];
   if (!c) {
-    if (geom) c = oi == 1 ? blocks_per_cu_ops<1024, 1> (mode) : (oi == 2 ? blocks_per_cu_ops<1024, 2> (mode) : (oi == 4 ? blocks_per_cu_ops<1024, 4> (mode) : blocks_per_cu_ops<1024, 0> (mode)));
-    else c = oi == 1 ? blocks_per_cu_ops<512, 1> (mode) : (oi == 2 ? blocks_per_cu_ops<512, 2> (mode) : (oi == 4 ? blocks_per_cu_ops<512, 4> (mode) : blocks_per_cu_ops<512, 0> (mode)));
+    int n = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor (&n, k, v.nt, 0);
+    if (e != hipSuccess || n < 1) n = 1;
+    /* never more than the register file admits for the declared launch bounds */
+    const int by_regs = merge_waves_per_simd (v.nt, v.mode, v.cls, v.fast) * 4 / (v.nt / 64);
+    if (by_regs >= 1 && n > by_regs) n = by_regs;
+    c = n;
   }
   return c;
 }
 
-hipError_t launch_pair_merge (hipStream_t s, int geom, int mode, int grid, const uint32_t *A, uint64_t nA,
+hipError_t launch_pair_merge (hipStream_t s, const PairVariant &v, int grid, const uint32_t *A, uint64_t nA,
                               const uint32_t *B, uint64_t nB, const uint64_t *part, uint64_t num_tiles,
                               const PairParams &p, const PairOutputs &o, unsigned long long *desc,
                               PairControl *ctl)
 {
-  /* single-output calls (glistcompare -u / -i, every N-way level) take a specialised kernel */
-  if (geom) {
-    if (p.ops == 1u) return launch_pair_merge_ops<1024, 1> (s, mode, grid, A, nA, B, nB, part, num_tiles, p, o, desc, ctl);
-    if (p.ops == 2u) return launch_pair_merge_ops<1024, 2> (s, mode, grid, A, nA, B, nB, part, num_tiles, p, o, desc, ctl);
-    if (p.ops == 4u) return launch_pair_merge_ops<1024, 4> (s, mode, grid, A, nA, B, nB, part, num_tiles, p, o, desc, ctl);
-    return launch_pair_merge_ops<1024, 0> (s, mode, grid, A, nA, B, nB, part, num_tiles, p, o, desc, ctl);
-  }
-  if (p.ops == 1u) return launch_pair_merge_ops<512, 1> (s, mode, grid, A, nA, B, nB, part, num_tiles, p, o, desc, ctl);
-  if (p.ops == 2u) return launch_pair_merge_ops<512, 2> (s, mode, grid, A, nA, B, nB, part, num_tiles, p, o, desc, ctl);
-  if (p.ops == 4u) return launch_pair_merge_ops<512, 4> (s, mode, grid, A, nA, B, nB, part, num_tiles, p, o, desc, ctl);
-  return launch_pair_merge_ops<512, 0> (s, mode, grid, A, nA, B, nB, part, num_tiles, p, o, desc, ctl);
+  const PairKernel k = pair_kernel (v);
+  if (!k) return hipErrorInvalidDeviceFunction;
+  hipLaunchKernelGGL (k, dim3 (grid), dim3 (v.nt), 0, s, A, nA, B, nB, (u64 *) part, num_tiles, p, o, desc, ctl);
+  return hipGetLastError ();
 }
 
 hipError_t launch_scan_tiles (hipStream_t s, unsigned long long *desc, uint64_t num_tiles, unsigned long long *block_sums)

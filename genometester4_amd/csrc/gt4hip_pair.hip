@@ -55,9 +55,13 @@ int gt4hip_run_pair (gt4hip_context *ctx, const uint32_t *A, uint64_t nA, const 
   memset (run, 0, sizeof *run);
   const uint64_t total = nA + nB;
   if (!total || !p.ops) return GT4HIP_OK;
+  const bool two_pass = (ctx->two_pass || force_two_pass) && !count_only;
   /* count-only calls: 512-thread workgroups; everything that materialises records: 1024 */
   const int geom = ctx->force_geom ? (ctx->force_geom > 0 ? 1 : 0) : (count_only ? 0 : 1);
-  const uint64_t tile_records = merge_tile_records (geom, p.ops);
+  /* the kernels of this call: the first launch (the only one unless two_pass), and pass 2 of the two-pass path */
+  const PairVariant v1 = pair_variant (geom, (count_only || two_pass) ? MODE_COUNT : MODE_LOOKBACK, p);
+  const PairVariant v2 = pair_variant (geom, MODE_OFFSETS, p);
+  const uint64_t tile_records = merge_tile_records (v1);
   const uint64_t tiles = (total + tile_records - 1) / tile_records;
   if (tiles >= 0xffffffffull) return gt4hip_fail (ctx, GT4HIP_EINVAL, "lists too long: %llu merge tiles", (unsigned long long) tiles);
   run->tiles = tiles;
@@ -74,18 +78,16 @@ int gt4hip_run_pair (gt4hip_context *ctx, const uint32_t *A, uint64_t nA, const 
   p.scan_group = ctx->scan_group > 0 ? 1u : (ctx->scan_group < 0 ? 0u : (tiles > (20000ull << 6) ? 1u : 0u));
   int rc;
   if ((rc = gt4hip_grow (ctx, (void **) &ctx->part, &ctx->part_bytes, (size_t) (tiles + 1) * 16 + (size_t) (tiles / 64 + 3) * 8))) return rc; /* tile ranges + coarse co-ranks */
-  const bool two_pass = (ctx->two_pass || force_two_pass) && !count_only;
   const bool need_desc = !count_only;
   if (need_desc && (rc = gt4hip_grow (ctx, (void **) &ctx->desc, &ctx->desc_bytes, desc_bytes_for (tiles)))) return rc;
   if (two_pass) {
     const size_t nb = (size_t) ((tiles + 2047) / 2048) * 32;
     if ((rc = gt4hip_grow (ctx, (void **) &ctx->block_sums, &ctx->block_sums_bytes, nb))) return rc;
   }
-  const int first_mode = count_only ? MODE_COUNT : (two_pass ? MODE_COUNT : MODE_LOOKBACK);
-  int grid = ctx->n_cus * merge_blocks_per_cu (geom, first_mode, p.ops, &p);
+  int grid = ctx->n_cus * merge_blocks_per_cu (v1);
   if (ctx->grid_override > 0) grid = (int) ctx->grid_override;
   if ((uint64_t) grid > tiles + 1) grid = (int) tiles + 1; /* workers + the scanner workgroup */
-  int grid2 = ctx->n_cus * merge_blocks_per_cu (geom, MODE_OFFSETS, p.ops, &p);
+  int grid2 = ctx->n_cus * merge_blocks_per_cu (v2);
   if ((uint64_t) grid2 > tiles) grid2 = (int) tiles;
 
   PairOutputs outs;
@@ -98,14 +100,14 @@ int gt4hip_run_pair (gt4hip_context *ctx, const uint32_t *A, uint64_t nA, const 
   HIPCHK (ctx, launch_partition (st, A, nA, B, nB, tiles, tile_records, ctx->part));
   HIPCHK (ctx, hipEventRecord (ctx->ev[1], st));
   if (count_only) {
-    HIPCHK (ctx, launch_pair_merge (st, geom, MODE_COUNT, grid, A, nA, B, nB, ctx->part, tiles, p, outs, NULL, ctx->ctl));
+    HIPCHK (ctx, launch_pair_merge (st, v1, grid, A, nA, B, nB, ctx->part, tiles, p, outs, NULL, ctx->ctl));
   } else if (two_pass) {
-    HIPCHK (ctx, launch_pair_merge (st, geom, MODE_COUNT, grid, A, nA, B, nB, ctx->part, tiles, p, outs, ctx->desc, ctx->ctl));
+    HIPCHK (ctx, launch_pair_merge (st, v1, grid, A, nA, B, nB, ctx->part, tiles, p, outs, ctx->desc, ctx->ctl));
     HIPCHK (ctx, launch_scan_tiles (st, ctx->desc, tiles, ctx->block_sums));
     HIPCHK (ctx, hipMemsetAsync (ctx->ctl, 0, sizeof (PairControl), st));
-    HIPCHK (ctx, launch_pair_merge (st, geom, MODE_OFFSETS, grid2, A, nA, B, nB, ctx->part, tiles, p, outs, ctx->desc, ctx->ctl));
+    HIPCHK (ctx, launch_pair_merge (st, v2, grid2, A, nA, B, nB, ctx->part, tiles, p, outs, ctx->desc, ctx->ctl));
   } else {
-    HIPCHK (ctx, launch_pair_merge (st, geom, MODE_LOOKBACK, grid, A, nA, B, nB, ctx->part, tiles, p, outs, ctx->desc, ctx->ctl));
+    HIPCHK (ctx, launch_pair_merge (st, v1, grid, A, nA, B, nB, ctx->part, tiles, p, outs, ctx->desc, ctx->ctl));
   }
   HIPCHK (ctx, hipEventRecord (ctx->ev[2], st));
   HIPCHK (ctx, hipMemcpyAsync (ctx->ctl_host, ctx->ctl, sizeof (PairControl), hipMemcpyDeviceToHost, st));

@@ -15,7 +15,7 @@ def merge_tile(geom=0):
         import os
         import re
         root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-        txt = open(os.path.join(root, "genometester4_amd", "csrc", "gt4hip_internal.h")).read()
+        txt = open(os.path.join(root, "genometester4_amd", "csrc", "gt4hip_pair_variant.h")).read()
         vt = int(re.search(r"MERGE_VT\s*=\s*(\d+)", txt).group(1))
         slack = int(re.search(r"MERGE_TILE_SLACK\s*=\s*(\d+)", txt).group(1))
         MERGE_TILE = 512 * vt - slack  # the small geometry; sizes around it and its double are exercised

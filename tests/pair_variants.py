@@ -6,22 +6,21 @@ The restated C++ (genometester4_amd/csrc), by file: function:
                       first for an intersection, geometry, "dynamic", "scan_group", the two-pass path)
   gt4hip_multi.hip    gt4hip_nway_params, gt4hip_union_multi (the pairwise tree), gt4hip_intersect_multi (the chain)
   gt4hip_table.hip    table_column_by_union, gt4hip_probe_table_ex
-  gt4hip_kernels.hip  merge_ipt, fast_variant, launch_pair_merge_ops (OPSET), ops_class, merge_tile_records,
-                      launch_pair_merge
-tests/test_pair_variant_map.py ties this map to the instantiations the compiler emits.
+  gt4hip_pair_variant.h  merge_ipt, pair_variant (the class of p.ops, FAST, OPSET), merge_tile_records
+tests/test_pair_variant_map.py ties this map to the instantiations the compiler emits and to pair_variant itself.
 No GPU and no library are needed to import this module."""
 from __future__ import annotations
 
 from collections import namedtuple
 
-MODE_COUNT, MODE_LOOKBACK, MODE_OFFSETS = 0, 1, 2        # gt4hip_internal.h: enum MergeMode
-FILTER_REFERENCE, FILTER_RAW, FILTER_RESULT = 0, 1, 2    # gt4hip_internal.h: enum Filter
+MODE_COUNT, MODE_LOOKBACK, MODE_OFFSETS = 0, 1, 2        # gt4hip_pair_variant.h: enum MergeMode
+FILTER_REFERENCE, FILTER_RAW, FILTER_RESULT = 0, 1, 2    # gt4hip_pair_variant.h: enum Filter
 RULE_DEFAULT, RULE_ADD, RULE_SUBTRACT, RULE_MIN, RULE_MAX, RULE_FIRST, RULE_SECOND, RULE_NUMBER = range(8)
-RULE_MINZ = 8                                            # gt4hip_internal.h: RULE_MINZ
+RULE_MINZ = 8                                            # gt4hip_pair_variant.h: RULE_MINZ
 OP_UNION, OP_INTRSEC, OP_DIFF1, OP_DIFF2 = 1, 2, 4, 8
 
-GT4_IPT_UNION, GT4_IPT_INTERSECT, GT4_IPT_INTERSECT_SMALL, MERGE_VT = 4, 6, 4, 4   # gt4hip_kernels.hip: GT4_IPT_*, gt4hip_internal.h: MERGE_VT
-MERGE_TILE_SLACK = 64                                                             # gt4hip_internal.h: MERGE_TILE_SLACK
+GT4_IPT_UNION, GT4_IPT_INTERSECT, GT4_IPT_INTERSECT_SMALL, MERGE_VT = 4, 6, 4, 4   # gt4hip_pair_variant.h: GT4_IPT_*, MERGE_VT
+MERGE_TILE_SLACK = 64                                                             # gt4hip_pair_variant.h: MERGE_TILE_SLACK
 
 # PairParams, reduced to what the selection reads
 Params = namedtuple("Params", "ops rule cutoff subtract filter")
@@ -40,12 +39,12 @@ def nway_params(op_bit, rule, cutoff, filt):
 
 
 def ops_class(ops):
-    """gt4hip_kernels.hip: ops_class"""
+    """gt4hip_pair_variant.h: pair_variant, cls"""
     return ops if ops in (1, 2, 4) else 0
 
 
 def merge_ipt(nt, cls):
-    """gt4hip_kernels.hip: merge_ipt"""
+    """gt4hip_pair_variant.h: merge_ipt"""
     if nt == 1024 and cls == 2:
         return GT4_IPT_INTERSECT
     if nt == 1024 and cls == 1:
@@ -56,13 +55,13 @@ def merge_ipt(nt, cls):
 
 
 def merge_tile_records(geom, ops):
-    """gt4hip_kernels.hip: merge_tile_records"""
+    """gt4hip_pair_variant.h: merge_tile_records of pair_variant (geom, any mode, p)"""
     nt = 1024 if geom else 512
     return nt * merge_ipt(nt, ops_class(ops)) - MERGE_TILE_SLACK
 
 
 def fast_variant(cls, p):
-    """gt4hip_kernels.hip: fast_variant"""
+    """gt4hip_pair_variant.h: pair_variant, fast"""
     fast = 0
     if p.filter == FILTER_REFERENCE:
         if cls == 1 and p.rule[0] == RULE_ADD:
@@ -83,14 +82,14 @@ def fast_variant(cls, p):
 
 
 def kernel_name(nt, mode, p):
-    """gt4hip_kernels.hip: launch_pair_merge (the class from p.ops) -> launch_pair_merge_ops"""
+    """gt4hip_pair_variant.h: pair_variant, as the compiler prints the instantiation"""
     cls = ops_class(p.ops)
     fast = fast_variant(cls, p)
     ipt = merge_ipt(nt, cls)
-    # launch_pair_merge_ops, the fixed output sets: any-combination kernel, FAST 1, ops 3 / 5 / 15, and (512, COUNT) or (1024, not COUNT)
+    # the fixed output sets: any-combination kernel, FAST 1, ops 3 / 5 / 15, and (512, COUNT) or (1024, not COUNT)
     if cls == 0 and fast == 1 and p.ops in (3, 5, 15) and (nt == 512 if mode == MODE_COUNT else nt == 1024):
         return "k_pair_merge<%d, %d, %d, 0, 1, %d>" % (nt, ipt, mode, p.ops)
-    # (the same) F2 / F3 exist for the union and the intersection only; any other FAST falls back to 0
+    # F2 / F3 exist for the union and the intersection only; any other FAST falls back to 0
     if fast in (2, 3) and cls not in (1, 2):
         fast = 0
     return "k_pair_merge<%d, %d, %d, %d, %d, 0>" % (nt, ipt, mode, cls, fast)

@@ -1,9 +1,11 @@
-"""The variant map of tests/pair_variants.py against what the compiler emits: every compiled k_pair_merge<...>
-instantiation is either reached by a case of the GPU matrix (tests/test_pair_variants.py) or listed here as unreachable,
-with the reason.  Adding an instantiation, or changing the selection so that a variant drops out of the matrix, fails
-here first (hipcc cross-compiles gfx950 without a GPU)."""
+"""The variant map of tests/pair_variants.py against the product, without a GPU: every compiled k_pair_merge<...>
+instantiation is reached by a case of the GPU matrix (tests/test_pair_variants.py), and for every call the map is asked
+about, the product's own selection (gt4hip_pair_variant.h, compiled here into tests/harness/pair_variant_print.cc) names
+the same instantiation and the same tile length.  Adding an instantiation, or changing the selection so that a variant
+drops out of the matrix or the map no longer follows it, fails here first (hipcc cross-compiles gfx950 without a GPU)."""
 import os
 import shutil
+import subprocess
 import sys
 
 import pytest
@@ -12,19 +14,6 @@ import pair_variants as V
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-_OPSET = "launch_pair_merge_ops (gt4hip_kernels.hip:1312) takes the fixed output set only at (512, COUNT) or (1024, not COUNT)"
-UNREACHABLE = {
-    "k_pair_merge<1024, 4, 0, 0, 1, 3>": "1024-thread COUNT: " + _OPSET,
-    "k_pair_merge<1024, 4, 0, 0, 1, 5>": "1024-thread COUNT: " + _OPSET,
-    "k_pair_merge<1024, 4, 0, 0, 1, 15>": "1024-thread COUNT: " + _OPSET,
-    "k_pair_merge<512, 4, 1, 0, 1, 3>": "512-thread LOOKBACK: " + _OPSET,
-    "k_pair_merge<512, 4, 1, 0, 1, 5>": "512-thread LOOKBACK: " + _OPSET,
-    "k_pair_merge<512, 4, 1, 0, 1, 15>": "512-thread LOOKBACK: " + _OPSET,
-    "k_pair_merge<512, 4, 2, 0, 1, 3>": "512-thread OFFSETS: " + _OPSET,
-    "k_pair_merge<512, 4, 2, 0, 1, 5>": "512-thread OFFSETS: " + _OPSET,
-    "k_pair_merge<512, 4, 2, 0, 1, 15>": "512-thread OFFSETS: " + _OPSET,
-}
 
 MAIN = (3_300_000,) * 5   # sizes of the GPU matrix's main lists (test_pair_variants.py asserts its inputs against the map's tiles)
 
@@ -46,16 +35,9 @@ def _predicted():
     return names
 
 
-def test_every_compiled_instantiation_is_reached_or_listed(compiled):
-    reached = _predicted()
-    missing = sorted(compiled - reached - set(UNREACHABLE))
-    assert not missing, "compiled, not reached by the GPU matrix and not on the unreachable list: %s" % missing
-    both = sorted(reached & set(UNREACHABLE))
-    assert not both, "listed as unreachable, yet the matrix launches them: %s" % both
-
-
-def test_unreachable_list_holds_only_compiled_names(compiled):
-    assert not sorted(set(UNREACHABLE) - compiled)
+def test_every_compiled_instantiation_is_reached(compiled):
+    missing = sorted(compiled - _predicted())
+    assert not missing, "compiled and not reached by the GPU matrix: %s" % missing
 
 
 def test_matrix_predicts_only_compiled_names(compiled):
@@ -97,3 +79,40 @@ def test_map_names_the_nway_filters():
     # the count tables: SECOND / NUMBER under RAW, the general kernels (FAST 0)
     names = V.multi_launches(V.union_table_steps(9, [4, 5], presence=True))
     assert set(names) == {"k_pair_merge<1024, 6, 1, 2, 0, 0>", "k_pair_merge<1024, 4, 1, 1, 0, 0>"}
+
+
+@pytest.fixture(scope="module")
+def selection(tmp_path_factory):
+    """the product's selection as a function of [(nt, mode, Params)]: [(name, records per tile)]"""
+    exe = str(tmp_path_factory.mktemp("pair_variant") / "pair_variant_print")
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "genometester4_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "harness", "pair_variant_print.cc"), "-o", exe], check=True)
+
+    def ask(cases):
+        text = "".join("%d %d %d %d %d %d %d %d %d %d\n" % ((nt == 1024, mode, p.ops) + tuple(p.rule) + (p.cutoff, p.subtract, p.filter))
+                       for nt, mode, p in cases)
+        out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
+        assert len(out) == len(cases)
+        return [(ln.rsplit(" ", 1)[0], int(ln.rsplit(" ", 1)[1])) for ln in out]
+    return ask
+
+
+def test_map_agrees_with_the_compiled_selection(selection, monkeypatch):
+    asked = []
+    kernel_name = V.kernel_name
+    monkeypatch.setattr(V, "kernel_name", lambda nt, mode, p: asked.append((nt, mode, p)) or kernel_name(nt, mode, p))
+    _predicted()                                                                   # V.matrix()
+    for c in V.SIDE_CALLS:
+        for path in V.SIDE_PATHS:
+            V.predicted(("pair",) + c, path, (3_000_000, 300_000))
+            V.predicted(("pair",) + c, path, (300_000, 3_000_000))
+    for presence in (False, True):
+        for path in ({}, {"two_pass": True}, {"geom": 0}):
+            V.multi_launches(V.union_table_steps(9, [4, 5], presence=presence), **path)
+    test_map_restates_the_argument_swaps()
+    test_map_names_the_nway_filters()
+    cases = sorted(set(asked))
+    assert len(cases) > 100
+    expected = [(kernel_name(nt, mode, p), V.merge_tile_records(nt == 1024, p.ops)) for nt, mode, p in cases]
+    wrong = [(c, got, exp) for c, got, exp in zip(cases, selection(cases), expected) if got != exp]
+    assert not wrong, "(nt, mode, Params), the product's selection, the map's: %s" % wrong[:5]

@@ -5,8 +5,8 @@ Usage: tools/device_asm_diff.py OTHER_TREE [THIS_TREE]
 Every .hip of <tree>/genometester4_amd/csrc is compiled with the command its Makefile would run for it (make -n), with
 -S --offload-device-only in place of -c.  For every kernel (.amdhsa_kernel NAME) the text from its label to its
 .end_amdhsa_kernel is compared between the trees; lines that name __hip_cuid_* (a fresh random symbol per compile) are
-dropped, and so is the number of the function inside its file in the assembler's local labels (.LBB<n>_, .Lfunc_end<n>),
-which changes when a kernel moves to another file.  Files present in both trees are compared whole as they are.  Exit status 0: every kernel of either tree is in the
+dropped, and so is the number of the function inside its file in the assembler's local labels (.LBB<n>_, .Lfunc_end<n>)
+and in its loop comments (BB<n>_), which changes when a kernel moves to another file or is instantiated in another order.  Files present in both trees are compared whole as they are.  Exit status 0: every kernel of either tree is in the
 other with the same text."""
 import concurrent.futures
 import os
@@ -37,7 +37,8 @@ def kernels(lines):
         m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", ln)
         if m:
             end = next(j for j in range(i, len(lines)) if ".end_amdhsa_kernel" in lines[j])
-            found[m.group(1)] = re.sub(r"\.(LBB|Lfunc_begin|Lfunc_end)\d+", r".\1", "\n".join(lines[label[m.group(1)]:end + 1]))
+            text = re.sub(r"(\.LBB|\.Lfunc_begin|\.Lfunc_end|\bBB)\d+", r"\1", "\n".join(lines[label[m.group(1)]:end + 1]))
+            found[m.group(1)] = re.sub(r"[ \t]+;", " ;", text)   # comments are aligned to a column: a shorter number, other padding
     return found
 
 
