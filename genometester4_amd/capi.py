@@ -64,6 +64,26 @@ class MakerCarry(C.Structure):
                 ("ended", C.c_uint32), ("error", C.c_uint32), ("codes", C.c_uint8 * 32)]
 
 
+class Subseq(C.Structure):
+    _fields_ = [("name_pos", C.c_uint64), ("name_len", C.c_uint64), ("seq_pos", C.c_uint64), ("seq_len", C.c_uint64)]
+
+
+class LocationsCarry(C.Structure):
+    _fields_ = [("reader", MakerCarry), ("offset", C.c_uint64), ("n_events", C.c_uint64), ("n_subseqs", C.c_uint64),
+                ("seq_codes", C.c_uint64), ("max_position", C.c_uint64), ("name_pos", C.c_uint64), ("seq_pos", C.c_uint64),
+                ("seq_open", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class LocationsPiece(C.Structure):
+    _fields_ = [("n_words", C.c_uint64), ("n_subseqs", C.c_uint64), ("subseqs", C.POINTER(Subseq)),
+                ("closed_seq_len", C.c_uint64), ("closed", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class IndexArrays(C.Structure):
+    _fields_ = [("n_kmers", C.c_uint64), ("n_locations", C.c_uint64), ("n_values", C.c_uint64),
+                ("d_kmers", C.c_void_p), ("d_locations", C.c_void_p)]
+
+
 class MultiResult(C.Structure):
     _fields_ = [("n_words", C.c_uint64), ("total_count", C.c_uint64), ("out", C.c_void_p), ("device_ms", C.c_double),
                 ("records_read", C.c_uint64), ("records_written", C.c_uint64)]
@@ -91,6 +111,8 @@ SYMBOLS = [
     "gt4hip_query_variant_mask", "gt4hip_query_lookup", "gt4hip_query_lookup_all", "gt4hip_list_count_stats",
     "gt4hip_list_count_split", "gt4hip_list_count_histogram", "gt4hip_list_gc",
     "gt4hip_text_to_words", "gt4hip_words_free", "gt4hip_words_download", "gt4hip_text_to_list",
+    "gt4hip_sort_pairs", "gt4hip_pairs_to_index", "gt4hip_index_free",
+    "gt4hip_text_to_locations", "gt4hip_locations_free", "gt4hip_pack_locations", "gt4hip_pairs_reserve", "gt4hip_pairs_release",
 ]
 
 _lib = None
@@ -185,6 +207,15 @@ def lib():
             "gt4hip_words_free": (None, [vp, vp]),
             "gt4hip_words_download": (C.c_int, [vp, vp, u64, vp]),
             "gt4hip_text_to_list": (C.c_int, [vp, vp, C.c_size_t, C.c_uint, C.c_uint, C.POINTER(vp)]),
+            "gt4hip_sort_pairs": (C.c_int, [vp, vp, vp, u64, u32]),
+            "gt4hip_pairs_to_index": (C.c_int, [vp, vp, vp, u64, u32, u32, u32, C.POINTER(IndexArrays)]),
+            "gt4hip_index_free": (None, [vp]),
+            "gt4hip_text_to_locations": (C.c_int, [vp, vp, C.c_size_t, C.c_uint, C.c_uint, C.POINTER(LocationsCarry), C.POINTER(LocationsCarry),
+                                                   vp, vp, u64, C.POINTER(LocationsPiece), C.POINTER(u64)]),
+            "gt4hip_locations_free": (None, [vp]),
+            "gt4hip_pack_locations": (C.c_int, [vp, vp, u64, u64, C.c_uint, C.c_uint]),
+            "gt4hip_pairs_reserve": (C.c_int, [vp, u64, C.POINTER(vp), C.POINTER(vp)]),
+            "gt4hip_pairs_release": (None, [vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -440,6 +471,45 @@ class Context:
             self._chk(rc)
         return words, out
 
+    def text_to_locations(self, pieces, word_length):
+        """The pieces of one file, in order -> (words, raw locations: ordinal << 33 | position << 1 | strand, subsequence
+        records as rows of (name_pos, name_len, seq_pos, seq_len), largest position) (gt4hip_text_to_locations into a
+        block of gt4hip_pairs_reserve, one call per piece, the carry handed on; the end of the file closes the open
+        sequence)."""
+        total = sum(len(p) for p in pieces)
+        dw, dv = C.c_void_p(), C.c_void_p()
+        self._chk(lib().gt4hip_pairs_reserve(self.h, total, C.byref(dw), C.byref(dv)))
+        try:
+            carry, at, subs = None, 0, []
+            for p in pieces:
+                out, piece, err = LocationsCarry(), LocationsPiece(), C.c_uint64()
+                buf = (C.c_char * max(len(p), 1)).from_buffer_copy(bytes(p) or b"\0")
+                rc = lib().gt4hip_text_to_locations(self.h, buf, len(p), word_length, 0, C.byref(carry) if carry is not None else None, C.byref(out),
+                                                    C.c_void_p((dw.value or 0) + 8 * at), C.c_void_p((dv.value or 0) + 8 * at), total - at, C.byref(piece), C.byref(err))
+                if rc:
+                    e = Gt4HipError(rc, lib().gt4hip_last_error(self.h).decode())
+                    e.error_offset, e.kind = err.value, out.reader.error
+                    raise e
+                if piece.closed:
+                    subs[-1][3] = piece.closed_seq_len
+                subs += [[r.name_pos, r.name_len, r.seq_pos, r.seq_len] for r in piece.subseqs[:piece.n_subseqs]]
+                at += piece.n_words
+                carry = out
+            if carry is not None and carry.seq_open:
+                subs[-1][3] = total - subs[-1][2]
+            words, raw = np.empty(at, dtype=np.uint64), np.empty(at, dtype=np.uint64)
+            if at:
+                self._chk(lib().gt4hip_words_download(self.h, dw, at, words.ctypes.data))
+                self._chk(lib().gt4hip_words_download(self.h, dv, at, raw.ctypes.data))
+            return words, raw, subs, carry.max_position if carry is not None else 0
+        finally:
+            lib().gt4hip_locations_free(self.h)
+            lib().gt4hip_pairs_release(self.h)
+
+    def pack_locations(self, raw_ptr, n, file, subseq_bits, pos_bits):
+        """n raw locations of file number `file` (device memory) -> location words, in place (gt4hip_pack_locations)."""
+        self._chk(lib().gt4hip_pack_locations(self.h, C.c_void_p(raw_ptr), n, file, subseq_bits, pos_bits))
+
     def text_to_list(self, text: bytes, word_length, flags=0) -> "DeviceList":
         """One whole text -> the list glistmaker writes for it (gt4hip_text_to_list)."""
         h = C.c_void_p()
@@ -450,6 +520,23 @@ class Context:
     def sort_words(self, device_ptr, n_words, word_length):
         """Sorts n_words packed words at `device_ptr` (device memory) ascending, in place."""
         self._chk(lib().gt4hip_sort_words(self.h, C.c_void_p(device_ptr), n_words, word_length))
+
+    def sort_pairs(self, words_ptr, values_ptr, n_pairs, word_length):
+        """Sorts n_pairs (word, value) pairs (two device arrays) by word, in place and stably (gt4hip_sort_pairs)."""
+        self._chk(lib().gt4hip_sort_pairs(self.h, C.c_void_p(words_ptr), C.c_void_p(values_ptr), n_pairs, word_length))
+
+    def pairs_to_index(self, words_ptr, values_ptr, n_pairs, word_length, min_locations=1, max_locations=0xffffffff):
+        """(word, value) pairs in device memory -> (k-mer section as an (n_kmers, 2) array of (word, first location),
+        n_locations, location section: every value, sorted by word) (gt4hip_pairs_to_index)."""
+        a = IndexArrays()
+        self._chk(lib().gt4hip_pairs_to_index(self.h, C.c_void_p(words_ptr), C.c_void_p(values_ptr), n_pairs, word_length, min_locations, max_locations, C.byref(a)))
+        kmers, locs = np.empty((a.n_kmers, 2), dtype=np.uint64), np.empty(a.n_values, dtype=np.uint64)
+        rc = lib().gt4hip_words_download(self.h, a.d_kmers, 2 * a.n_kmers, kmers.ctypes.data) if a.n_kmers else 0
+        if not rc and a.n_values:
+            rc = lib().gt4hip_words_download(self.h, a.d_locations, a.n_values, locs.ctypes.data)
+        lib().gt4hip_index_free(self.h)
+        self._chk(rc)
+        return kmers, a.n_locations, locs
 
     def device_words_to_list(self, device_ptr, n_words, word_length) -> "DeviceList":
         """The same for n_words packed words at `device_ptr` (device memory; sorted in place)."""

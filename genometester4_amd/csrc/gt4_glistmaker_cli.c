@@ -16,8 +16,13 @@
  * files are read.  The reference keeps such lists in temporary files; here they stay in device memory, so the collated
  * lists of the levels (in the end: the result) have to fit there.  Several input files pool their words; a run of bases
  * never crosses from one file into the next.
+ * --index writes `<out>_<k>.index` instead (reference write_index, :366-782): every word of every input with where it
+ * stands stays in device memory -- 16 bytes a word, sized from the inputs' bytes -- until one sort by word behind the last
+ * file, since the bit sizes of a location are known only then; the sort needs as much again.  What does not fit is an
+ * error that names --index and the bytes, and no file is written.  Offsets in the file block count from the start of the
+ * file throughout (the reference cuts files above 10^8 bytes into blocks and counts seq_pos from the block's start).
  * Deliberate differences, all an error message + exit 1:
- *   - --index (the location tables are not built);
+ *   - --index with standard input (the file block records a file's name and size);
  *   - input that starts with the gzip magic (the reference goes by the name's .gz): decompress it first;
  *   - without a usable GPU the program fails: there is no CPU path;
  *   - malformed text (a first byte that is neither '>' nor '@'; FastQ without its '+' line or its '@'): the reference's
@@ -345,21 +350,184 @@ static gt4hip_list *collate (gt4hip_context *ctx, Lists *ls)
   return up;
 }
 
+/* ------------------------------------------------------------------ --index: text -> pairs -> index file */
+
+_Static_assert (sizeof (GT4IndexSubseq) == sizeof (gt4hip_subseq), "the library's records are handed to the writer as they are");
+
+static unsigned int bit_size (uint64_t v) /* get_bitsize, reference :116-126 */
+{
+  unsigned int n = 1;
+  while (v >>= 1) n++;
+  return n;
+}
+
+static void index_no_room (uint64_t text_bytes, uint64_t need)
+{
+  fprintf (stderr, "Error: --index: the words of %llu bytes of text and their locations need %llu bytes of device memory, which do not fit: no index written\n",
+           (unsigned long long) text_bytes, (unsigned long long) need);
+  exit (1);
+}
+
+/* one file through the device, a piece at a time: its words and raw locations behind the `at` pairs there are, its records into `in` */
+static uint64_t file_to_pairs (const Options *o, gt4hip_context *ctx, const Text *t, uint64_t chunk, uint64_t *d_words, uint64_t *d_raw, uint64_t at, uint64_t capacity,
+                               GT4IndexInput *in, uint64_t *max_pos)
+{
+  gt4hip_locations_carry carry, next;
+  GT4IndexSubseq *subs = NULL;
+  uint64_t n_subs = 0, cap_subs = 0, n_words = 0;
+  int have = 0;
+  size_t pos = 0;
+  unsigned int pieces = 0;
+  while (pos < t->size) {
+    size_t len = t->size - pos;
+    if (len > chunk) {
+      len = (size_t) chunk;
+      const unsigned char *nl = (const unsigned char *) memrchr (t->data + pos + len / 2, '\n', len - len / 2);
+      if (nl) len = (size_t) (nl - (t->data + pos)) + 1;
+    }
+    gt4hip_locations_piece piece;
+    uint64_t err_at = 0;
+    const int rc = gt4hip_text_to_locations (ctx, t->data + pos, len, o->wordlength, 0, have ? &carry : NULL, &next, d_words + at + n_words, d_raw + at + n_words,
+                                             capacity - at - n_words, &piece, &err_at);
+    if (rc == GT4HIP_EFORMAT) format_error_exit (t, next.reader.error, pos + err_at);
+    if (rc) {
+      fprintf (stderr, "Error: --index: %s\n", gt4hip_last_error (ctx));
+      exit (1);
+    }
+    if (piece.closed && n_subs) subs[n_subs - 1].seq_len = piece.closed_seq_len;
+    if (n_subs + piece.n_subseqs > cap_subs) {
+      cap_subs = (n_subs + piece.n_subseqs) * 2;
+      subs = (GT4IndexSubseq *) realloc (subs, cap_subs * sizeof *subs);
+      if (!subs) {
+        fprintf (stderr, "Error: out of memory (%llu sequence records)\n", (unsigned long long) cap_subs);
+        exit (1);
+      }
+    }
+    if (piece.n_subseqs) memcpy (subs + n_subs, piece.subseqs, piece.n_subseqs * sizeof *subs);
+    n_subs += piece.n_subseqs;
+    n_words += piece.n_words;
+    carry = next;
+    have = 1;
+    pos += len;
+    pieces++;
+    if (o->verbose && pos < t->size) fprintf (stderr, "%s: piece %u ends at byte %zu\n", t->id, pieces, pos);
+    if (carry.reader.ended) break;
+  }
+  if (have && !carry.reader.ended && carry.reader.file_type == GT4HIP_MAKER_FASTQ && carry.reader.line_phase == 2)
+    format_error_exit (t, carry.reader.at_line_start ? GT4HIP_MAKER_ERR_PLUS : GT4HIP_MAKER_ERR_PLUS_EOF, t->size);
+  if (have && carry.seq_open && n_subs) subs[n_subs - 1].seq_len = t->size - subs[n_subs - 1].seq_pos; /* (src/fasta.c:109) */
+  if (have && carry.max_position > *max_pos) *max_pos = carry.max_position;
+  if (o->verbose) fprintf (stderr, "%s: %zu bytes in %u piece(s); %llu words in %llu sequences\n", t->id, t->size, pieces, (unsigned long long) n_words, (unsigned long long) n_subs);
+  in->n_subseqs = n_subs;
+  in->subseqs = subs;
+  return n_words;
+}
+
+/* n 64-bit words of device memory behind what the file holds */
+static int write_device_words (gt4hip_context *ctx, FILE *f, const uint64_t *d, uint64_t n, uint64_t *buf)
+{
+  for (uint64_t first = 0; first < n; first += DOWNLOAD_CHUNK) {
+    const uint64_t cnt = n - first < DOWNLOAD_CHUNK ? n - first : DOWNLOAD_CHUNK;
+    if (gt4hip_words_download (ctx, d + first, cnt, buf)) {
+      fprintf (stderr, "Error: reading results back from the GPU failed: %s\n", gt4hip_last_error (ctx));
+      return 1;
+    }
+    if (fwrite (buf, 8, cnt, f) != cnt) return 1;
+  }
+  return 0;
+}
+
+static int make_index (const Options *o, gt4hip_context *ctx, Text *texts, uint64_t chunk)
+{
+  uint64_t text_bytes = 0, free_b = 0, total_b = 0;
+  for (unsigned int i = 0; i < o->nfiles; i++) text_bytes += texts[i].size;
+  /* a word per byte at the most: 16 bytes each resident, as much again for the sort's other side, and the pieces' staging */
+  gt4hip_device_memory (ctx, &free_b, &total_b);
+  if (text_bytes > (~0ull >> 6) || text_bytes * 16 > free_b) index_no_room (text_bytes, text_bytes * 16);
+  uint64_t *d_words = NULL, *d_raw = NULL;
+  if (gt4hip_pairs_reserve (ctx, text_bytes, &d_words, &d_raw)) index_no_room (text_bytes, text_bytes * 16);
+  static GT4IndexInput inputs[MAX_FILES];
+  static uint64_t first_word[MAX_FILES + 1];
+  uint64_t n_pairs = 0, max_pos = 0, max_sub = 0;
+  for (unsigned int i = 0; i < o->nfiles; i++) {
+    inputs[i].name = o->fnames[i];
+    inputs[i].size = texts[i].size;
+    first_word[i] = n_pairs;
+    n_pairs += file_to_pairs (o, ctx, &texts[i], chunk, d_words, d_raw, n_pairs, text_bytes, &inputs[i], &max_pos);
+    if (inputs[i].n_subseqs && inputs[i].n_subseqs - 1 > max_sub) max_sub = inputs[i].n_subseqs - 1;
+    text_close (&texts[i]);
+  }
+  first_word[o->nfiles] = n_pairs;
+  const unsigned int fb = bit_size (o->nfiles - 1), sb = bit_size (max_sub), pb = bit_size (max_pos);
+  if (fb + sb + pb + 1 > 64) {
+    fprintf (stderr, "Error: --index: %u file, %u sequence and %u position bits and the strand do not fit the 64 bits of a location: no index written\n", fb, sb, pb);
+    return 1;
+  }
+  gt4hip_index_arrays idx;
+  memset (&idx, 0, sizeof idx);
+  if (n_pairs) {
+    for (unsigned int i = 0; i < o->nfiles; i++)
+      CHK (ctx, gt4hip_pack_locations (ctx, d_raw + first_word[i], first_word[i + 1] - first_word[i], i, sb, pb));
+    gt4hip_device_memory (ctx, &free_b, &total_b);
+    if (n_pairs * 16 > free_b) index_no_room (text_bytes, text_bytes * 16 + n_pairs * 16);
+    if (gt4hip_pairs_to_index (ctx, d_words, d_raw, n_pairs, o->wordlength, o->min, o->max, &idx)) {
+      fprintf (stderr, "Error: --index: %s\n", gt4hip_last_error (ctx));
+      return 1;
+    }
+  }
+  void *head = NULL;
+  size_t head_bytes = 0;
+  if (gt4_index_head_build (o->wordlength, n_pairs != 0, idx.n_kmers, idx.n_locations, fb, sb, pb, inputs, o->nfiles, &head, &head_bytes)) {
+    fprintf (stderr, "Error: out of memory (file block)\n");
+    return 1;
+  }
+  char out_name[1024], tmp_name[1100];
+  snprintf (out_name, sizeof out_name, "%s_%u.index", o->outputname, o->wordlength);
+  snprintf (tmp_name, sizeof tmp_name, "%s.tmp", out_name);
+  FILE *f = fopen (tmp_name, "wb");
+  if (!f) {
+    fprintf (stderr, "Cannot create output file %s\n", tmp_name);
+    return 1;
+  }
+  const uint64_t most = idx.n_values > 2 * idx.n_kmers ? idx.n_values : 2 * idx.n_kmers;
+  uint64_t *buf = (uint64_t *) malloc ((size_t) (most < DOWNLOAD_CHUNK ? most + 1 : DOWNLOAD_CHUNK) * 8);
+  int bad = !buf || fwrite (head, 1, head_bytes, f) != head_bytes;
+  if (!bad) bad = write_device_words (ctx, f, idx.d_kmers, 2 * idx.n_kmers, buf);
+  if (!bad) bad = write_device_words (ctx, f, idx.d_locations, idx.n_values, buf);
+  bad |= fclose (f) != 0;
+  free (buf);
+  free (head);
+  if (bad) {
+    fprintf (stderr, "Error: writing %s failed\n", tmp_name);
+    unlink (tmp_name);
+    return 1;
+  }
+  if (rename (tmp_name, out_name)) fprintf (stderr, "Cannot rename %s to %s\n", tmp_name, out_name);
+  gt4hip_index_free (ctx);
+  gt4hip_pairs_release (ctx);
+  gt4hip_locations_free (ctx);
+  for (unsigned int i = 0; i < o->nfiles; i++) free ((void *) inputs[i].subseqs);
+  gt4hip_destroy (ctx);
+  return 0;
+}
+
 int main (int argc, const char *argv[])
 {
   static Options o;
   read_environment (&o);
   parse_argv (argc, argv, &o);
   validate (&o);
-  if (o.create_index) {
-    fprintf (stderr, "Error: --index is not supported: this glistmaker writes lists only\n");
-    return 1;
-  }
+  if (o.create_index)
+    for (unsigned int i = 0; i < o.nfiles; i++)
+      if (!strcmp (o.fnames[i], "-")) {
+        fprintf (stderr, "Error: --index does not read standard input: the index records every input file's name and size\n");
+        return 1;
+      }
   static Text texts[MAX_FILES];
   for (unsigned int i = 0; i < o.nfiles; i++) text_open (&o, o.fnames[i], &texts[i]);
   gt4hip_context *ctx = NULL;
   if (gt4hip_create (o.device, &ctx)) {
-    fprintf (stderr, "Error: no usable GPU: %s\n", gt4hip_last_error (NULL));
+    fprintf (stderr, "Error: %sno usable GPU: %s\n", o.create_index ? "--index: " : "", gt4hip_last_error (NULL));
     return 1;
   }
   uint64_t chunk = o.chunk;
@@ -371,6 +539,7 @@ int main (int argc, const char *argv[])
     if (chunk < (1ull << 20)) chunk = 1ull << 20;
   }
   if (o.verbose) fprintf (stderr, "Device: %s; pieces of %llu bytes\n", gt4hip_device_info (ctx), (unsigned long long) chunk);
+  if (o.create_index) return make_index (&o, ctx, texts, chunk);
   static Lists ls;
   for (unsigned int i = 0; i < o.nfiles; i++) {
     file_to_lists (&o, ctx, &texts[i], chunk, &ls);

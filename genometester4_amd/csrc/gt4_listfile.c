@@ -222,3 +222,59 @@ void gt4_listwriter_abort (GT4ListWriter *w)
   if (w->fd >= 0) close (w->fd);
   w->fd = -1;
 }
+
+/* ---- GT4I index: header + file block */
+
+static unsigned char *put_u16 (unsigned char *p, unsigned int v) { p[0] = (unsigned char) v, p[1] = (unsigned char) (v >> 8); return p + 2; }
+static unsigned char *put_u32 (unsigned char *p, uint32_t v) { memcpy (p, &v, 4); return p + 4; }
+static unsigned char *put_u64 (unsigned char *p, uint64_t v) { memcpy (p, &v, 8); return p + 8; }
+
+int gt4_index_head_build (unsigned int word_length, int have_words, uint64_t n_kmers, uint64_t n_locations, unsigned int file_bits, unsigned int subseq_bits,
+                          unsigned int pos_bits, const GT4IndexInput *inputs, unsigned int n_inputs, void **head, size_t *head_bytes)
+{
+  size_t block = 0;
+  if (have_words) {
+    block = 16;
+    for (unsigned int i = 0; i < n_inputs; i++) block += 18 + strlen (inputs[i].name) + 1 + (size_t) inputs[i].n_subseqs * 28;
+    block = (block + 7) & ~(size_t) 7;
+  }
+  unsigned char *b = (unsigned char *) calloc (1, 72 + block), *p = b;
+  if (!b) return 1;
+  memcpy (p, "I4TG", 4);
+  p = put_u32 (p + 4, 4);
+  p = put_u32 (p, 2);
+  p = put_u32 (p, word_length);
+  p = put_u64 (p, have_words ? n_kmers : 0);
+  p = put_u64 (p, have_words ? n_locations : 0);
+  p = put_u32 (p, have_words ? file_bits : 1);
+  p = put_u32 (p, have_words ? subseq_bits : 1);
+  p = put_u32 (p, have_words ? pos_bits : 1);
+  p = put_u32 (p, 0);
+  p = put_u64 (p, 72);
+  p = put_u64 (p, 72 + block);
+  p = put_u64 (p, 72 + block + (have_words ? n_kmers * 16 : 0));
+  if (have_words) {
+    memcpy (p, "F4TG", 4);
+    p = put_u32 (p + 4, 4);
+    p = put_u32 (p, 2);
+    p = put_u32 (p, n_inputs);
+    for (unsigned int i = 0; i < n_inputs; i++) {
+      const size_t len = strlen (inputs[i].name) + 1;
+      p = put_u64 (p, inputs[i].size);
+      p = put_u64 (p, inputs[i].n_subseqs);
+      p = put_u16 (p, (unsigned int) len);
+      memcpy (p, inputs[i].name, len);
+      p += len;
+      for (uint64_t j = 0; j < inputs[i].n_subseqs; j++) {
+        const GT4IndexSubseq *s = &inputs[i].subseqs[j];
+        p = put_u64 (p, s->name_pos);
+        p = put_u32 (p, (uint32_t) s->name_len);
+        p = put_u64 (p, s->seq_pos);
+        p = put_u64 (p, s->seq_len);
+      }
+    }
+  }
+  *head = b;
+  *head_bytes = 72 + block;
+  return 0;
+}

@@ -114,6 +114,9 @@ extern "C" void gt4hip_destroy (gt4hip_context *ctx)
   if (ctx->stream) hipStreamSynchronize (ctx->stream);
   gt4hip_io_destroy (ctx);
   gt4hip_words_free (ctx, NULL);
+  gt4hip_index_free (ctx);
+  gt4hip_pairs_release (ctx);
+  gt4hip_locations_free (ctx);
   if (ctx->pool) {
     pool_flush (ctx);
     delete ctx->pool;

@@ -66,6 +66,9 @@ struct gt4hip_context {
   double sort_ms, fold_ms;   /* the last gt4hip_device_words_to_list: radix sort and fold (HIP events) */
   double extract_ms;         /* the last gt4hip_text_to_words that gave words: its kernels (HIP events around them alone) */
   struct gt4hip_list *maker_words; /* the words of the last gt4hip_text_to_words, until gt4hip_words_free or the next call */
+  struct gt4hip_list *index_kmers; /* the k-mer section of the last gt4hip_pairs_to_index, until gt4hip_index_free or the next call */
+  struct gt4hip_list *index_pairs; /* the block of gt4hip_pairs_reserve, until gt4hip_pairs_release or the next call */
+  gt4hip_subseq *maker_subseqs;    /* host: the records of the last gt4hip_text_to_locations, until gt4hip_locations_free or the next call */
   double nway_kernel_ms;     /* the last one-pass launch's kernel time (HIP events on the library's stream) and tiles */
   uint64_t nway_tiles;
   int last_multi_one_pass;   /* the last gt4hip_union_multi was done by the one-pass tile kernel (counter "nway_one_pass") */

@@ -1,5 +1,7 @@
 /* gt4hip_maker.hip -- glistmaker's front on the device: FastA / FastQ text in HBM -> packed k-mer words
  * (gt4hip_text_to_words), and with the table step of gt4hip_sort.hip behind it, text -> list (gt4hip_text_to_list).
+ * gt4hip_text_to_locations is the same reader for glistmaker --index: beside every word where it stands, and the text's
+ * name and sequence boundaries for the file block (the second half of the kernels below).
  *
  * The reader restated is fasta_reader_read_nwords (reference src/fasta.c:87-291), a byte-serial state machine.  Every
  * decision in it is local once two carries are known at the start of a tile of text: FastA "a '>' was seen on this line"
@@ -29,6 +31,7 @@
 #include "gt4hip_host.h"
 #include "gt4hip_index.h"
 
+#include <stdlib.h>
 #include <string.h>
 
 namespace gt4 {
@@ -47,6 +50,10 @@ struct MakerInfo {
   u64 n_codes;  /* codes of the text in front of nul_pos */
   u64 n_words;
   u32 in_name, phase, at_line_start, pad; /* the carries behind the last byte */
+  /* gt4hip_text_to_locations alone (behind what the kernels of gt4hip_text_to_words read and write) */
+  u64 n_events;  /* name starts, sequence starts and (FastQ) sequence ends of the text */
+  u64 max_pos;   /* largest position of a word */
+  u64 overflow;  /* a word's ordinal or position does not fit its raw field */
 };
 
 /* 16 bytes of text at `off` as four dwords; bytes at `limit` and behind read as 0 */
@@ -306,6 +313,208 @@ __global__ __launch_bounds__ (MK_THREADS) void k_mk_emit (const unsigned char *_
   }
 }
 
+/* ---- locations (glistmaker --index): where every word stands, and the subsequences of the file block
+ *
+ * The reader's callbacks for an index (reference src/glistmaker.c:1031-1067) need three things per word: the ordinal of
+ * its sequence within the file, its position -- bytes >= ' ' of the sequence in front of the word's first base (:1064,
+ * src/fasta.c:254-264), which is the distance in codes from the sequence's start, since the codes of a sequence are
+ * contiguous in the code stream -- and the strand.  So the text's *events* are compacted, in text order, each with the
+ * index of the code that follows it:
+ *   FastA  0 a '>' outside a name (the name starts behind it), 1 the '\n' that ends a name (the sequence starts behind it);
+ *          they alternate, so event g of a file is a sequence start iff g is odd, and that sequence's ordinal is g / 2
+ *   FastQ  1 the '\n' of a name line, 2 the '\n' of a sequence line (the sequence ends), 0 the '\n' of a quality line (a
+ *          name starts two bytes on); event g is a sequence start iff g % 3 == 0, ordinal g / 3
+ * A word that ends at code j lies in the sequence of the last event whose code index is <= j: every name and every
+ * '+' / quality line holds a code that ends the run, so no other event can lie between a word and its sequence's start.
+ * The host puts the 28-byte records of the file block together from the same events (a name or a sequence may cover any
+ * number of tiles or pieces: the open record travels in the carry).
+ *   k_mk_events<.., 0>  events per tile of text (the classification of k_mk_codes again, nothing written)
+ *   k_tile_scan         -> where each tile's events go
+ *   k_mk_events<.., 1>  (offset in the file << 2 | kind, index of the next code) per event
+ *   k_mk_emit_loc       k_mk_emit<1> with, beside every word, ordinal << 33 | position << 1 | strand */
+/* 1 when the byte c is x, as arithmetic: sixteen compares a thread would each hold a pair of scalar registers */
+#define IS_BYTE(c, x) ((((c) ^ (u32) (x)) - 1u) >> 31)
+
+template <bool FASTQ, bool WRITE>
+__global__ __launch_bounds__ (MK_THREADS) void k_mk_events (const unsigned char *__restrict__ text, u64 n, u64 n_tiles, const u64 *tile_off, const u32 *tile_state, u64 file_off,
+                                                            u32 *ev_cnt, const u64 *ev_off, u64 *ev, const MakerInfo *info)
+{
+  __shared__ u32 s_sum[MK_THREADS / WAVE], s_has[MK_THREADS / WAVE], s_tail[MK_THREADS / WAVE], s_ev[MK_THREADS / WAVE];
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  const u64 nul = info->nul_pos, n_eff = nul < n ? nul : n;
+  for (u64 t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    if (t * MK_TILE >= n_eff) { /* (uniform) */
+      if (!WRITE && threadIdx.x == 0) ev_cnt[t] = 0;
+      continue;
+    }
+    const u64 off = t * MK_TILE + (u64) threadIdx.x * MK_PER;
+    u32 w[4], kept, nl, tail;
+    load16 (text, n_eff, off, w);
+    scan16 (w, &kept, &nl, &tail);
+    const u32 incl = dpp_inclusive_scan_u32 (kept | (nl << 16));
+    const u64 m_nl = __builtin_amdgcn_ballot_w64 (nl != 0), m_tail = __builtin_amdgcn_ballot_w64 (tail != 0);
+    u32 has, wt;
+    wave_line_state (m_nl, m_tail, &has, &wt);
+    if (lane == WAVE - 1) s_sum[wv] = incl;
+    if (lane == 0) s_has[wv] = has, s_tail[wv] = wt;
+    __syncthreads ();
+    const u32 st = tile_state[t];
+    u32 before = 0, name = st & 1u;
+    for (int i = 0; i < wv; i++) {
+      before += s_sum[i];
+      name = s_has[i] ? s_tail[i] : (name | s_tail[i]);
+    }
+    const u32 excl = before + incl - (kept | (nl << 16));
+    u32 rank = excl & 0xffffu;
+    u32 phase = ((st >> 1) + (excl >> 16)) & 3u;
+    {
+      const u64 below = ((u64) 1 << lane) - 1, b_nl = m_nl & below, b_tail = m_tail & below;
+      name = b_nl ? (b_tail >> (63 - __builtin_clzll (b_nl))) != 0 : (name | (b_tail != 0));
+    }
+    /* this thread's events */
+    u32 ne = 0;
+    {
+      u32 nm = name, ph = phase;
+#pragma unroll
+      for (int j = 0; j < MK_PER; j++) { /* (load16 gives 0 for the bytes behind n_eff: no event there) */
+        const u32 c = MK_BYTE (w, j), is_nl = IS_BYTE (c, '\n'), is_gt = IS_BYTE (c, '>');
+        if (FASTQ) {
+          ne += is_nl & (ph != 2u);
+          ph = (ph + is_nl) & 3u;
+        } else {
+          ne += (is_nl & nm) | (is_gt & (nm ^ 1u));
+          nm = (nm | is_gt) & (is_nl ^ 1u);
+        }
+      }
+    }
+    const u32 einc = dpp_inclusive_scan_u32 (ne);
+    if (lane == WAVE - 1) s_ev[wv] = einc;
+    __syncthreads ();
+    u32 ebefore = 0, etotal = 0;
+    for (int i = 0; i < MK_THREADS / WAVE; i++) {
+      if (i < wv) ebefore += s_ev[i];
+      etotal += s_ev[i];
+    }
+    if (!WRITE) {
+      if (threadIdx.x == 0) ev_cnt[t] = etotal;
+    } else if (ne) {
+      u64 slot = ev_off[t] + ebefore + einc - ne;
+      const u64 code0 = tile_off[t];
+#pragma unroll
+      for (int j = 0; j < MK_PER; j++) {
+        const u32 c = MK_BYTE (w, j), is_nl = IS_BYTE (c, '\n'), is_gt = IS_BYTE (c, '>');
+        u32 kind, is_ev;
+        if (FASTQ) {
+          kind = (phase + 1u) & 3u; /* name line 1, sequence line 2, '+' line none, quality line 0 */
+          is_ev = is_nl & (kind != 3u);
+          phase = (phase + is_nl) & 3u;
+        } else {
+          kind = is_nl;
+          is_ev = (is_nl & name) | (is_gt & (name ^ 1u));
+          name = (name | is_gt) & (is_nl ^ 1u);
+        }
+        if (is_ev) {
+          ev[2 * slot] = ((file_off + off + j) << 2) | kind;
+          ev[2 * slot + 1] = code0 + rank;
+          slot++;
+        }
+        if (c >= 0x20u) rank++;
+      }
+    }
+    __syncthreads ();
+  }
+}
+
+/* k_mk_emit<true> with the raw location beside every word.  ev: the piece's events, n_ev of them, the first is event g0
+ * of the file; ord0 / codes0: the ordinal of the sequence the piece starts in and its codes in front of the piece. */
+template <int PERIOD>
+__global__ __launch_bounds__ (MK_THREADS) void k_mk_emit_loc (const unsigned char *__restrict__ buf, MakerInfo *info, u64 n_tiles, u32 k, const u64 *tile_off, u64 *words,
+                                                              u64 *raw, const u64 *__restrict__ ev, u64 n_ev, u64 g0, u64 ord0, u64 codes0)
+{
+  __shared__ u32 s_sum[MK_THREADS / WAVE];
+  __shared__ unsigned long long s_max, s_over;
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  const u64 n_codes = info->n_codes;
+  const u64 mask = k >= 32 ? ~0ull : (1ull << (2 * k)) - 1;
+  for (u64 t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    const u64 j0 = t * MK_TILE + (u64) threadIdx.x * MK_PER;
+    if (threadIdx.x == 0) s_max = 0, s_over = 0;
+    u32 w[12];
+    if (j0 < n_codes) {
+#pragma unroll
+      for (int q = 0; q < 3; q++) {
+        const u32x4 v = *(const u32x4 *) (buf + j0 + 16 * q);
+        w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 12; q++) w[q] = 0x04040404u;
+    }
+    u32 len = 0, cnt = 0;
+#pragma unroll
+    for (int i = 0; i < MK_HALO + MK_PER; i++) {
+      const u32 c = MK_BYTE (w, i);
+      len = c < 4u ? len + 1u : 0u;
+      if (i >= MK_HALO && j0 + (u64) (i - MK_HALO) < n_codes && len >= k) cnt++;
+    }
+    const u32 incl = dpp_inclusive_scan_u32 (cnt);
+    if (lane == WAVE - 1) s_sum[wv] = incl;
+    __syncthreads ();
+    u32 before = 0;
+    for (int i = 0; i < wv; i++) before += s_sum[i];
+    if (cnt) {
+      /* a thread's words and locations lie together (up to 128 bytes each), written from the thread: not staged in LDS as
+       * k_mk_emit<true> stages the words, which would take the two streams through it one after the other */
+      u64 at = tile_off[t] + before + incl - cnt;
+      /* events whose code index is <= j0: the last of them is where the sequence of code j0 starts */
+      u64 lo = 0, hi = n_ev;
+      while (lo < hi) {
+        const u64 mid = lo + (hi - lo) / 2;
+        if (ev[2 * mid + 1] <= j0) lo = mid + 1;
+        else hi = mid;
+      }
+      u64 fw = 0, rv = 0, pmax = 0, over = 0;
+      len = 0;
+#pragma unroll
+      for (int i = 0; i < MK_HALO + MK_PER; i++) {
+        const u32 c = MK_BYTE (w, i);
+        fw = (fw << 2) | (c & 3u);
+        rv = (rv >> 2) | ((u64) (~c & 3u) << (2 * (k - 1)));
+        len = c < 4u ? len + 1u : 0u;
+        if (i >= MK_HALO && j0 + (u64) (i - MK_HALO) < n_codes && len >= k) {
+          const u64 j = j0 + (u64) (i - MK_HALO);
+          while (lo < n_ev && ev[2 * lo + 1] <= j) lo++;
+          const u64 ord = lo ? (g0 + lo - 1) / PERIOD : ord0;
+          const u64 pos = (lo ? j - ev[2 * lo - 1] : j + codes0) + 1 - k;
+          const u64 f = fw & mask;
+          words[at] = f < rv ? f : rv;
+          raw[at] = (ord << 33) | ((pos & 0xffffffffull) << 1) | (u64) (rv < f);
+          at++;
+          pmax = pos > pmax ? pos : pmax;
+          over |= (ord >> 31) | (pos >> 32);
+        }
+      }
+      atomicMax (&s_max, (unsigned long long) pmax);
+      if (over) s_over = 1;
+    }
+    __syncthreads ();
+    if (threadIdx.x == 0) {
+      if (s_max) atomicMax ((unsigned long long *) &info->max_pos, s_max);
+      if (s_over) info->overflow = 1;
+    }
+    __syncthreads ();
+  }
+}
+
+/* raw locations of one file -> the words of the location section (reference :1066): file | ordinal | position | strand */
+__global__ __launch_bounds__ (256) void k_pack_locations (u64 *__restrict__ raw, u64 n, u64 file, u32 sb, u32 pb)
+{
+  for (u64 i = (u64) blockIdx.x * 256 + threadIdx.x; i < n; i += (u64) gridDim.x * 256) {
+    const u64 r = raw[i];
+    raw[i] = (file << (sb + pb + 1)) | ((r >> 33) << (pb + 1)) | (r & 0x1ffffffffull);
+  }
+}
+
 }  // namespace
 }  // namespace gt4
 
@@ -354,8 +563,23 @@ extern "C" int gt4hip_words_download (gt4hip_context *ctx, const uint64_t *d_wor
   return gt4hip_read_back (ctx, host_words, d_words, (size_t) n_words * 8, "gt4hip_words_download failed");
 }
 
-extern "C" int gt4hip_text_to_words (gt4hip_context *ctx, const void *text, size_t n_bytes, unsigned word_length, unsigned flags, const gt4hip_maker_carry *in,
-                                     gt4hip_maker_carry *out, uint64_t **d_words, uint64_t *n_words, uint64_t *error_offset)
+namespace {
+
+/* what gt4hip_text_to_locations adds to a call of the reader */
+struct LocCall {
+  const gt4hip_locations_carry *in;
+  u64 *dst_words, *dst_raw; /* the caller's device arrays */
+  uint64_t capacity;
+  gt4hip_locations_piece *piece;
+  gt4hip_locations_carry *out;
+};
+
+int finish_locations (gt4hip_context *ctx, LocCall *loc, const gt4hip_maker_carry *reader, const u64 *d_ev, uint64_t n_ev, uint64_t n_codes, uint64_t end_offset, uint64_t max_pos);
+
+/* gt4hip_text_to_words; with `loc`, gt4hip_text_to_locations: the same kernels up to the words' count, then the events and
+ * k_mk_emit_loc into the caller's arrays instead of k_mk_emit<true> into a block of the context */
+int text_to_words (gt4hip_context *ctx, const void *text, size_t n_bytes, unsigned word_length, unsigned flags, const gt4hip_maker_carry *in,
+                   gt4hip_maker_carry *out, uint64_t **d_words, uint64_t *n_words, uint64_t *error_offset, LocCall *loc)
 {
   if (!ctx || !d_words || !n_words || (n_bytes && !text) || !word_length || word_length > 32 ||
       (flags & ~(unsigned) (GT4HIP_MAKER_FORWARD_ONLY | GT4HIP_MAKER_TEXT_ON_DEVICE)))
@@ -363,7 +587,7 @@ extern "C" int gt4hip_text_to_words (gt4hip_context *ctx, const void *text, size
   if ((flags & GT4HIP_MAKER_TEXT_ON_DEVICE) && ((size_t) text & 15)) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_text_to_words: device text must be 16-byte aligned");
   if (in && (in->file_type > GT4HIP_MAKER_FASTQ || in->line_phase > 3)) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_text_to_words: carry not from this library");
   HIPCHK (ctx, hipSetDevice (ctx->device));
-  gt4hip_words_free (ctx, NULL); /* (the words of the call before, if the caller still left them) */
+  if (!loc) gt4hip_words_free (ctx, NULL); /* (the words of the call before, if the caller still left them) */
   *d_words = NULL;
   *n_words = 0;
   if (error_offset) *error_offset = 0;
@@ -379,7 +603,7 @@ extern "C" int gt4hip_text_to_words (gt4hip_context *ctx, const void *text, size
   gt4hip_maker_carry dummy;
   if (!out) out = &dummy;
   *out = c;
-  if (!n_bytes || c.ended) return GT4HIP_OK;
+  if (!n_bytes || c.ended) return loc ? finish_locations (ctx, loc, out, NULL, 0, 0, loc->in ? loc->in->offset : 0, 0) : GT4HIP_OK;
   hipStream_t st = ctx->stream;
   Blocks blk;
   int rc;
@@ -402,7 +626,7 @@ extern "C" int gt4hip_text_to_words (gt4hip_context *ctx, const void *text, size
     if (!first) {
       hipStreamSynchronize (st); /* (the upload reads the caller's text) */
       out->ended = 1;
-      return GT4HIP_OK;
+      return loc ? finish_locations (ctx, loc, out, NULL, 0, 0, loc->in ? loc->in->offset : 0, 0) : GT4HIP_OK;
     }
     if (first != '>' && first != '@') {
       hipStreamSynchronize (st);
@@ -422,6 +646,17 @@ extern "C" int gt4hip_text_to_words (gt4hip_context *ctx, const void *text, size
   if ((rc = blk.get (ctx, tiles * 4, (void **) &tile_state))) return rc;
   if ((rc = blk.get (ctx, tiles * 8, (void **) &tile_off))) return rc;
   if ((rc = blk.get (ctx, tiles * MK_TILE + MK_HALO + 64, (void **) &buf))) return rc;
+  /* with locations the codes' offsets are still read after the words are counted: the emit stage gets arrays of its own */
+  u32 *emit_cnt = tile_cnt, *ev_cnt = NULL;
+  u64 *emit_off = tile_off, *ev_off = NULL;
+  if (loc) {
+    if ((rc = blk.get (ctx, tiles * 4, (void **) &emit_cnt))) return rc;
+    if ((rc = blk.get (ctx, tiles * 8, (void **) &emit_off))) return rc;
+    if ((rc = blk.get (ctx, tiles * 4, (void **) &ev_cnt))) return rc;
+    if ((rc = blk.get (ctx, tiles * 8, (void **) &ev_off))) return rc;
+  }
+  const bool fastq = c.file_type == GT4HIP_MAKER_FASTQ;
+  const u64 file_off = loc && loc->in ? loc->in->offset : 0;
   MakerInfo h;
   memset (&h, 0, sizeof h);
   h.nul_pos = n_bytes;
@@ -439,8 +674,15 @@ extern "C" int gt4hip_text_to_words (gt4hip_context *ctx, const void *text, size
   else
     hipLaunchKernelGGL (k_mk_codes<false>, dim3 (grid), dim3 (MK_THREADS), 0, st, d_text, (u64) n_bytes, (u64) tiles, tile_off, tile_state, c.at_line_start, buf + MK_HALO, info);
   /* (tile_cnt and tile_off now serve the emit stage: at most as many codes as bytes, so at most as many tiles) */
-  hipLaunchKernelGGL (k_mk_emit<false>, dim3 (grid), dim3 (MK_THREADS), 0, st, buf, info, (u64) tiles, word_length, 0u, tile_cnt, tile_off, (u64 *) NULL);
-  hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, st, tile_cnt, (u64) tiles, tile_off, &info->n_words);
+  hipLaunchKernelGGL (k_mk_emit<false>, dim3 (grid), dim3 (MK_THREADS), 0, st, buf, info, (u64) tiles, word_length, 0u, emit_cnt, emit_off, (u64 *) NULL);
+  hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, st, emit_cnt, (u64) tiles, emit_off, &info->n_words);
+  if (loc) {
+    if (fastq)
+      hipLaunchKernelGGL ((k_mk_events<true, false>), dim3 (grid), dim3 (MK_THREADS), 0, st, d_text, (u64) n_bytes, (u64) tiles, tile_off, tile_state, file_off, ev_cnt, ev_off, (u64 *) NULL, info);
+    else
+      hipLaunchKernelGGL ((k_mk_events<false, false>), dim3 (grid), dim3 (MK_THREADS), 0, st, d_text, (u64) n_bytes, (u64) tiles, tile_off, tile_state, file_off, ev_cnt, ev_off, (u64 *) NULL, info);
+    hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, st, ev_cnt, (u64) tiles, ev_off, &info->n_events);
+  }
   hipEventRecord (ctx->ev[1], st);
   HIPCHK (ctx, hipGetLastError ());
   if ((rc = gt4hip_read_back (ctx, &h, info, sizeof h, "reading the extraction's totals back failed"))) return rc;
@@ -452,6 +694,35 @@ extern "C" int gt4hip_text_to_words (gt4hip_context *ctx, const void *text, size
   HIPCHK (ctx, hipStreamSynchronize (st));
   if (h.err != ~0ull) return format_error (ctx, out, (uint32_t) (h.err & 7u), h.err >> 3, error_offset);
   if (out->ended && end_error (out)) return format_error (ctx, out, end_error (out), h.nul_pos, error_offset);
+  if (loc) {
+    if (h.n_words > loc->capacity)
+      return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_text_to_locations: %llu words, room for %llu", (unsigned long long) h.n_words, (unsigned long long) loc->capacity);
+    u64 *ev = NULL;
+    if ((rc = blk.get (ctx, (size_t) h.n_events * 16, (void **) &ev))) return rc;
+    hipEventRecord (ctx->ev[2], st);
+    if (h.n_events) {
+      if (fastq)
+        hipLaunchKernelGGL ((k_mk_events<true, true>), dim3 (grid), dim3 (MK_THREADS), 0, st, d_text, (u64) n_bytes, (u64) tiles, tile_off, tile_state, file_off, ev_cnt, ev_off, ev, info);
+      else
+        hipLaunchKernelGGL ((k_mk_events<false, true>), dim3 (grid), dim3 (MK_THREADS), 0, st, d_text, (u64) n_bytes, (u64) tiles, tile_off, tile_state, file_off, ev_cnt, ev_off, ev, info);
+    }
+    if (h.n_words) {
+      const u64 g0 = loc->in ? loc->in->n_events : 0, ord0 = loc->in && loc->in->n_subseqs ? loc->in->n_subseqs - 1 : 0, codes0 = loc->in ? loc->in->seq_codes : 0;
+      if (fastq)
+        hipLaunchKernelGGL (k_mk_emit_loc<3>, dim3 (grid), dim3 (MK_THREADS), 0, st, buf, info, (u64) tiles, word_length, emit_off, loc->dst_words, loc->dst_raw, ev, h.n_events, g0, ord0, codes0);
+      else
+        hipLaunchKernelGGL (k_mk_emit_loc<2>, dim3 (grid), dim3 (MK_THREADS), 0, st, buf, info, (u64) tiles, word_length, emit_off, loc->dst_words, loc->dst_raw, ev, h.n_events, g0, ord0, codes0);
+    }
+    hipEventRecord (ctx->ev[3], st);
+    HIPCHK (ctx, hipGetLastError ());
+    if ((rc = gt4hip_read_back (ctx, &h, info, sizeof h, "reading the locations' totals back failed"))) return rc;
+    float ms = 0, ms2 = 0;
+    if (hipEventElapsedTime (&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess && hipEventElapsedTime (&ms2, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->extract_ms = ms + ms2;
+    if (h.overflow) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_text_to_locations: a sequence ordinal of 2^31 or a position of 2^32 or more does not fit a raw location");
+    if (h.n_words) *d_words = (uint64_t *) loc->dst_words;
+    *n_words = h.n_words;
+    return finish_locations (ctx, loc, out, ev, h.n_events, h.n_codes, file_off + (out->ended ? h.nul_pos : n_bytes), h.max_pos);
+  }
   if (h.n_words) {
     void *w = NULL, *owner = NULL;
     if (gt4hip_block_alloc (ctx, (size_t) h.n_words * 8, &w, &owner))
@@ -473,6 +744,138 @@ extern "C" int gt4hip_text_to_words (gt4hip_context *ctx, const void *text, size
     *d_words = (uint64_t *) w;
     *n_words = h.n_words;
   }
+  return GT4HIP_OK;
+}
+
+/* the piece's events -> its subsequence records and the carry behind it (reference start_sequence_index / end_sequence_index,
+ * src/glistmaker.c:1031-1052); `reader`: the reader's carry behind the piece, end_offset: where the piece (or the text) ends */
+int finish_locations (gt4hip_context *ctx, LocCall *loc, const gt4hip_maker_carry *reader, const u64 *d_ev, uint64_t n_ev, uint64_t n_codes, uint64_t end_offset, uint64_t max_pos)
+{
+  gt4hip_locations_carry c;
+  if (loc->in) {
+    c = *loc->in;
+  } else {
+    memset (&c, 0, sizeof c);
+    c.name_pos = 1; /* (a FastQ file's first name has no event) */
+  }
+  gt4hip_locations_piece *pc = loc->piece;
+  memset (pc, 0, sizeof *pc);
+  std::vector<u64> ev (2 * n_ev);
+  if (n_ev) {
+    const int rc = gt4hip_read_back (ctx, ev.data (), d_ev, (size_t) n_ev * 16, "reading the text's events back failed");
+    if (rc) return rc;
+  }
+  uint64_t n_new = 0;
+  for (uint64_t i = 0; i < n_ev; i++) n_new += (ev[2 * i] & 3u) == 1u;
+  gt4hip_locations_free (ctx);
+  gt4hip_subseq *recs = NULL;
+  if (n_new) {
+    recs = (gt4hip_subseq *) malloc (n_new * sizeof *recs);
+    if (!recs) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_text_to_locations: %llu subsequence records", (unsigned long long) n_new);
+    ctx->maker_subseqs = recs;
+  }
+  const bool fastq = reader->file_type == GT4HIP_MAKER_FASTQ;
+  uint64_t n = 0, last_start = ~0ull;
+  auto close_at = [&] (uint64_t at) {
+    if (!c.seq_open) return;
+    if (n) recs[n - 1].seq_len = at - recs[n - 1].seq_pos;
+    else pc->closed = 1, pc->closed_seq_len = at - c.seq_pos;
+    c.seq_open = 0;
+  };
+  for (uint64_t i = 0; i < n_ev; i++) {
+    const uint64_t at = ev[2 * i] >> 2;
+    switch (ev[2 * i] & 3u) {
+      case 0: /* a name starts: behind the '>', or two bytes behind a quality line's '\n' */
+        if (!fastq) close_at (at);
+        c.name_pos = at + (fastq ? 2 : 1);
+        break;
+      case 1: /* the sequence starts behind this '\n' */
+        recs[n].name_pos = c.name_pos, recs[n].name_len = at - c.name_pos, recs[n].seq_pos = at + 1, recs[n].seq_len = 0;
+        n++;
+        c.seq_open = 1, c.seq_pos = at + 1;
+        last_start = ev[2 * i + 1];
+        break;
+      default: close_at (at); break; /* a FastQ sequence line ends */
+    }
+  }
+  if (reader->ended) close_at (end_offset); /* (src/fasta.c:109: a NUL ends the sequence as the end of the file does) */
+  c.reader = *reader;
+  c.offset = end_offset;
+  c.n_events += n_ev;
+  c.n_subseqs += n;
+  c.seq_codes = last_start != ~0ull ? n_codes - last_start : c.seq_codes + n_codes;
+  if (max_pos > c.max_position) c.max_position = max_pos;
+  pc->n_subseqs = n;
+  pc->subseqs = recs;
+  if (loc->out) *loc->out = c;
+  return GT4HIP_OK;
+}
+
+}  // namespace
+
+extern "C" void gt4hip_locations_free (gt4hip_context *ctx)
+{
+  if (!ctx) return;
+  free (ctx->maker_subseqs);
+  ctx->maker_subseqs = NULL;
+}
+
+extern "C" int gt4hip_text_to_words (gt4hip_context *ctx, const void *text, size_t n_bytes, unsigned word_length, unsigned flags, const gt4hip_maker_carry *in,
+                                     gt4hip_maker_carry *out, uint64_t **d_words, uint64_t *n_words, uint64_t *error_offset)
+{
+  return text_to_words (ctx, text, n_bytes, word_length, flags, in, out, d_words, n_words, error_offset, NULL);
+}
+
+extern "C" int gt4hip_text_to_locations (gt4hip_context *ctx, const void *text, size_t n_bytes, unsigned word_length, unsigned flags, const gt4hip_locations_carry *in,
+                                         gt4hip_locations_carry *out, uint64_t *d_words, uint64_t *d_raw, uint64_t capacity, gt4hip_locations_piece *piece, uint64_t *error_offset)
+{
+  if (!ctx || !out || !piece || (capacity && (!d_words || !d_raw)) || (flags & GT4HIP_MAKER_FORWARD_ONLY)) return GT4HIP_EINVAL;
+  LocCall loc = { in, (u64 *) d_words, (u64 *) d_raw, capacity, piece, out };
+  memset (piece, 0, sizeof *piece);
+  gt4hip_maker_carry reader;
+  uint64_t *w = NULL, n = 0;
+  if (in) *out = *in;
+  else memset (out, 0, sizeof *out);
+  const int rc = text_to_words (ctx, text, n_bytes, word_length, flags, in ? &in->reader : NULL, &reader, &w, &n, error_offset, &loc);
+  if (rc) out->reader = reader; /* (the kind of a GT4HIP_EFORMAT) */
+  else piece->n_words = n;
+  return rc;
+}
+
+extern "C" int gt4hip_pack_locations (gt4hip_context *ctx, uint64_t *d_raw, uint64_t n, uint64_t file, unsigned subseq_bits, unsigned pos_bits)
+{
+  if (!ctx || (n && !d_raw)) return GT4HIP_EINVAL;
+  if (!subseq_bits || !pos_bits || pos_bits > 32 || subseq_bits > 31 || subseq_bits + pos_bits + 1 > 63 || (file >> (63 - subseq_bits - pos_bits)))
+    return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_pack_locations: file %llu with %u + %u + 1 bits behind it does not fit 64 bits", (unsigned long long) file, subseq_bits, pos_bits);
+  HIPCHK (ctx, hipSetDevice (ctx->device));
+  if (!n) return GT4HIP_OK;
+  hipLaunchKernelGGL (k_pack_locations, dim3 (grid_for (ctx, n, 256)), dim3 (256), 0, ctx->stream, (u64 *) d_raw, (u64) n, (u64) file, subseq_bits, pos_bits);
+  HIPCHK (ctx, hipGetLastError ());
+  HIPCHK (ctx, hipStreamSynchronize (ctx->stream));
+  return GT4HIP_OK;
+}
+
+/* The pairs of an index -- every word of every input and its location -- are one pooled block of the context. */
+extern "C" void gt4hip_pairs_release (gt4hip_context *ctx)
+{
+  if (!ctx || !ctx->index_pairs) return;
+  gt4hip_list_free (ctx->index_pairs);
+  ctx->index_pairs = NULL;
+}
+
+extern "C" int gt4hip_pairs_reserve (gt4hip_context *ctx, uint64_t n_pairs, uint64_t **d_words, uint64_t **d_values)
+{
+  if (!ctx || !d_words || !d_values) return GT4HIP_EINVAL;
+  HIPCHK (ctx, hipSetDevice (ctx->device));
+  gt4hip_pairs_release (ctx);
+  *d_words = *d_values = NULL;
+  if (!n_pairs) return GT4HIP_OK;
+  void *p = NULL, *owner = NULL;
+  if (n_pairs >= (1ull << 59) || gt4hip_block_alloc (ctx, (size_t) n_pairs * 16, &p, &owner))
+    return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_pairs_reserve: %llu pairs need %llu bytes of device memory", (unsigned long long) n_pairs, (unsigned long long) n_pairs * 16);
+  ctx->index_pairs = (gt4hip_list *) owner;
+  *d_words = (uint64_t *) p;
+  *d_values = (uint64_t *) p + n_pairs;
   return GT4HIP_OK;
 }
 

@@ -130,6 +130,8 @@ __global__ __launch_bounds__ (RADIX_MAX_DIGITS) void k_radix_bases (u64 *__restr
  *      meets a PREFIX; the tile's own PREFIX is published;
  *   5. the tile leaves LDS in digit order: runs of one digit go to consecutive addresses. */
 /* (cache-policy switches of the words' streaming load and scattered store, as in gt4hip_device.h) */
+/* k_radix_scatter_pairs below repeats steps 1 to 5 line by line: a change to the ranks, the look-back or its bounded
+ * wait goes into both. */
 template <int B>
 __global__ __launch_bounds__ (RADIX_NT, GT4_RADIX_WAVES) void k_radix_scatter (const u64 *__restrict__ in, u64 *__restrict__ out, u64 n, u32 pass, u32 shift, const u64 *__restrict__ gbase,
                                                                               u64 *__restrict__ state, u32 *__restrict__ ticket, u32 *__restrict__ err, u32 spin_limit)
@@ -263,6 +265,173 @@ __global__ __launch_bounds__ (RADIX_NT, GT4_RADIX_WAVES) void k_radix_scatter (c
       const u64 k = keys[q];
       out[gofs[(u32) (k >> shift) & (u32) (ND - 1)] + q] = k; /* (plain: non-temporal scattered stores measured slower, profiles/round5/r5_cache_policy.log) */
     }
+  }
+}
+
+/* The same pass over (word, value) pairs: 32 bytes moved per pair.  A sibling of k_radix_scatter and not an instantiation
+ * of a shared body: with the body shared the keys-only kernel came out with other registers, and its code is to stay as
+ * it is; steps 1 to 5 are the same, line by line.  The values are fetched only when the words have left LDS and take the
+ * same way through the same 64 KB of it, so the kernel keeps its two workgroups per CU: what stays in registers between
+ * the two rounds is each word's place in the sorted tile (16 bits, where its rank was) and the digit of the word each
+ * thread wrote out (16 bits). */
+template <int B>
+__global__ __launch_bounds__ (RADIX_NT, GT4_RADIX_WAVES) void k_radix_scatter_pairs (const u64 *__restrict__ in, u64 *__restrict__ out, const u64 *__restrict__ vin, u64 *__restrict__ vout, u64 n,
+                                                                                    u32 pass, u32 shift, const u64 *__restrict__ gbase, u64 *__restrict__ state, u32 *__restrict__ ticket,
+                                                                                    u32 *__restrict__ err, u32 spin_limit)
+{
+  constexpr int ND = 1 << B, NDW = ND / WAVE; /* digits; wavefronts that own one digit per lane */
+  static_assert (ND <= RADIX_NT && ND <= RADIX_MAX_DIGITS && RADIX_TILE <= 65535, "a digit per thread; 16-bit places");
+  __shared__ u64 keys[RADIX_TILE];
+  __shared__ unsigned short wcnt[RADIX_NW][ND]; /* per wavefront: words of each digit so far; later: where the wavefront's words of the digit start in the sorted tile */
+  __shared__ u32 hcnt[ND];          /* words of each digit in the tile */
+  __shared__ u64 gofs[ND];          /* address of the tile's first word of each digit in `out`, minus its place in the sorted tile */
+  __shared__ u32 wtot[NDW];
+  __shared__ u32 tile_s;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  if (tid == 0) tile_s = atomicAdd (ticket, 1u);
+  for (int i = tid; i < RADIX_NW * ND / 2; i += RADIX_NT) reinterpret_cast<u32 *> (&wcnt[0][0])[i] = 0;
+  if (tid < ND) hcnt[tid] = 0;
+  __syncthreads ();
+  const u64 tile = tile_s;
+  const u64 base = tile * RADIX_TILE;
+  const u32 nv = n - base < (u64) RADIX_TILE ? (u32) (n - base) : (u32) RADIX_TILE;
+  u64 key[RADIX_ITEMS];
+  {
+    /* a range-checked descriptor over the tile: no per-lane bounds, no addresses in registers */
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc ((void *) (in + base), 0, (int) (8 * nv), 0x00020000);
+#pragma unroll
+    for (int r = 0; r < RADIX_ITEMS; r++) {
+      const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64 (rs, 8 * lane, 8 * WAVE * (wid * RADIX_ITEMS + r), 0);
+      key[r] = (u64) v.x | ((u64) v.y << 32);
+    }
+  }
+  /* what the tile holds of every digit, as early as it can be known (the stable ranks below take several
+   * times as long): the later tiles look back for it */
+#pragma unroll
+  for (int r = 0; r < RADIX_ITEMS; r++) {
+    const u32 q = (u32) (wid * RADIX_ITEMS + r) * WAVE + (u32) lane;
+    if (q < nv) atomicAdd (&hcnt[(u32) (key[r] >> shift) & (u32) (ND - 1)], 1u);
+  }
+  __syncthreads ();
+  u32 cnt_d = 0;
+  if (tid < ND) {
+    cnt_d = hcnt[tid];
+    __hip_atomic_store (&state[tile * ND + tid], (tile == 0 ? RADIX_PREFIX : RADIX_AGG) | radix_tag (pass) | (u64) cnt_d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  u32 rk[RADIX_ITEMS / 2]; /* 16 bits each */
+#pragma unroll
+  for (int r = 0; r < RADIX_ITEMS; r++) {
+    const u32 q = (u32) (wid * RADIX_ITEMS + r) * WAVE + (u32) lane;
+    const bool valid = q < nv;
+    const u32 d = (u32) (key[r] >> shift) & (u32) (ND - 1);
+    u64 m = __builtin_amdgcn_ballot_w64 (valid);
+#pragma unroll
+    for (int b = 0; b < B; b++) {
+      const u64 bal = __builtin_amdgcn_ballot_w64 ((d >> b) & 1u);
+      m &= ((d >> b) & 1u) ? bal : ~bal;
+    }
+    const u32 below = __builtin_amdgcn_mbcnt_hi ((u32) (m >> 32), __builtin_amdgcn_mbcnt_lo ((u32) m, 0u));
+    /* every lane of the group reads the counter, then its first lane adds the group (LDS executes a
+     * wavefront's accesses in order) */
+    const u32 old = valid ? wcnt[wid][d] : 0u;
+    if (valid && below == 0) wcnt[wid][d] = (unsigned short) (old + (u32) __popcll (m));
+    rk[r / 2] = (r & 1) ? rk[r / 2] | ((old + below) << 16) : old + below;
+  }
+  /* digit d = tid: its first place in the sorted tile */
+  u32 ls = 0;
+  if (tid < ND) {
+    const u32 incl = dpp_inclusive_scan_u32 (cnt_d);
+    if (lane == 63) wtot[wid] = incl;
+    ls = incl - cnt_d;
+  }
+  __syncthreads ();
+  if (tid < ND) {
+    for (int w = 0; w < wid; w++) ls += wtot[w];
+    u32 run = ls;
+#pragma unroll
+    for (int w = 0; w < RADIX_NW; w++) { /* -> where wavefront w's words of the digit start */
+      const u32 c = wcnt[w][tid];
+      wcnt[w][tid] = (unsigned short) run;
+      run += c;
+    }
+  }
+  __syncthreads ();
+  /* the tile sorted by digit, in LDS */
+#pragma unroll
+  for (int r = 0; r < RADIX_ITEMS; r++) {
+    const u32 q = (u32) (wid * RADIX_ITEMS + r) * WAVE + (u32) lane;
+    const u32 d = (u32) (key[r] >> shift) & (u32) (ND - 1);
+    const u32 place = (u32) wcnt[wid][d] + ((rk[r / 2] >> (16 * (r & 1))) & 0xffffu);
+    if (q < nv) keys[place] = key[r];
+    rk[r / 2] = (r & 1) ? (rk[r / 2] & 0xffffu) | (place << 16) : (rk[r / 2] & 0xffff0000u) | place;
+  }
+  /* look back: what the earlier tiles hold of digit tid */
+  if (tid < ND) {
+    u64 excl = 0;
+    if (tile > 0) {
+      /* RADIX_LOOK earlier tiles per round trip: the states are asked for together and summed in order
+       * up to the first PREFIX (a serial walk meets ~20 AGG states per tile: 20 dependent round trips) */
+      const u64 mine = radix_tag (pass) >> 56;
+      auto ready = [&] (u64 v) { return (v >> 62) != 0 && ((v >> 56) & 63u) == mine; };
+      bool done = false;
+      for (u64 j = tile; !done; j -= RADIX_LOOK) {
+        u64 v[RADIX_LOOK];
+#pragma unroll
+        for (int i = 0; i < RADIX_LOOK; i++)
+          v[i] = j >= (u64) (1 + i) ? __hip_atomic_load (&state[(j - 1 - i) * ND + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (RADIX_PREFIX | radix_tag (pass));
+#pragma unroll
+        for (int i = 0; i < RADIX_LOOK; i++) {
+          if (done) continue;
+          /* bounded: a predecessor that never publishes (a fault, a device shared with a stuck process) must
+           * not hang the sort.  The wait that gives up raises *err (the host returns GT4HIP_EHIP; the output
+           * is garbage) and goes on as if it had met a PREFIX, so its own PREFIX lets the successors drain;
+           * every other wait notices the flag at its next look. */
+          for (u32 spins = 0; !ready (v[i]);) {
+            if (++spins >= spin_limit || ((spins & 255u) == 0 && peek_u32 (err))) {
+              atomicOr (err, 1u);
+              v[i] = RADIX_PREFIX | radix_tag (pass);
+              break;
+            }
+            v[i] = __hip_atomic_load (&state[(j - 1 - i) * ND + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
+          excl += v[i] & RADIX_VALUE;
+          done = (v[i] & RADIX_PREFIX) != 0;
+        }
+      }
+      __hip_atomic_store (&state[tile * ND + tid], RADIX_PREFIX | radix_tag (pass) | (excl + cnt_d), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    gofs[tid] = gbase[pass * RADIX_MAX_DIGITS + tid] + excl - ls;
+  }
+  __syncthreads ();
+  u32 dg[RADIX_ITEMS / 2]; /* the digits of the words this thread writes out, 16 bits each */
+#pragma unroll
+  for (int r = 0; r < RADIX_ITEMS; r++) {
+    const u32 q = (u32) r * RADIX_NT + (u32) tid;
+    if (!(r & 1)) dg[r / 2] = 0;
+    if (q < nv) {
+      const u64 k = keys[q];
+      out[gofs[(u32) (k >> shift) & (u32) (ND - 1)] + q] = k; /* (plain: non-temporal scattered stores measured slower, profiles/round5/r5_cache_policy.log) */
+      dg[r / 2] = (r & 1) ? dg[r / 2] | (((u32) (k >> shift) & (u32) (ND - 1)) << 16) : (u32) (k >> shift) & (u32) (ND - 1);
+    }
+  }
+  /* the values: read as the words were, to the words' places in LDS, out behind the words' digits */
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc ((void *) (vin + base), 0, (int) (8 * nv), 0x00020000);
+#pragma unroll
+  for (int r = 0; r < RADIX_ITEMS; r++) {
+    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64 (rs, 8 * lane, 8 * WAVE * (wid * RADIX_ITEMS + r), 0);
+    key[r] = (u64) v.x | ((u64) v.y << 32);
+  }
+  __syncthreads (); /* (every word has been read out of LDS) */
+#pragma unroll
+  for (int r = 0; r < RADIX_ITEMS; r++) {
+    const u32 q = (u32) (wid * RADIX_ITEMS + r) * WAVE + (u32) lane;
+    if (q < nv) keys[(rk[r / 2] >> (16 * (r & 1))) & 0xffffu] = key[r];
+  }
+  __syncthreads ();
+#pragma unroll
+  for (int r = 0; r < RADIX_ITEMS; r++) {
+    const u32 q = (u32) r * RADIX_NT + (u32) tid;
+    if (q < nv) vout[gofs[(dg[r / 2] >> (16 * (r & 1))) & 0xffffu] + q] = keys[q];
   }
 }
 
@@ -423,6 +592,97 @@ __global__ __launch_bounds__ (FOLD_NT) void k_fold_records (const u64 *__restric
   }
 }
 
+/* ---- folded words -> the k-mer section of a location index */
+
+constexpr int INDEX_NT = 256;
+constexpr int INDEX_ITEMS = 4;
+constexpr int INDEX_TILE = INDEX_NT * INDEX_ITEMS;
+
+/* A tile of (word, occurrences) records, INDEX_ITEMS consecutive ones per thread: how many of them the cut-offs keep and
+ * how many occurrences those have, in front of every thread's records (*rank, *locs) and in the tile (the return value,
+ * *tile_locs).  A word is kept when lo <= occurrences <= hi (reference src/glistmaker.c:486). */
+__device__ __forceinline__ u32 index_tile_ranks (const u32 *__restrict__ rec, u64 n, u64 base, u32 lo, u32 hi, u32 (&cnt)[INDEX_ITEMS], u32 *rank, u64 *locs, u64 *tile_locs)
+{
+  __shared__ u64 w_locs[INDEX_NT / WAVE];
+  __shared__ u32 w_kept[INDEX_NT / WAVE];
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  u32 kept = 0;
+  u64 sum = 0;
+#pragma unroll
+  for (int r = 0; r < INDEX_ITEMS; r++) {
+    const u64 i = base + (u64) threadIdx.x * INDEX_ITEMS + r;
+    const u32 c = i < n ? rec[3 * i + 2] : 0u;
+    cnt[r] = c >= lo && c <= hi ? c : 0u; /* (lo >= 1: a record behind the end is never kept) */
+    kept += cnt[r] != 0;
+    sum += cnt[r];
+  }
+  const u32 ki = dpp_inclusive_scan_u32 (kept);
+  const u64 si = wave_inclusive_scan (sum, lane);
+  if (lane == WAVE - 1) w_kept[wv] = ki, w_locs[wv] = si;
+  __syncthreads ();
+  u32 kb = 0, kt = 0;
+  u64 sb = 0, stt = 0;
+  for (int i = 0; i < INDEX_NT / WAVE; i++) {
+    if (i < wv) kb += w_kept[i], sb += w_locs[i];
+    kt += w_kept[i], stt += w_locs[i];
+  }
+  *rank = kb + ki - kept;
+  *locs = sb + si - sum;
+  *tile_locs = stt;
+  return kt;
+}
+
+__global__ __launch_bounds__ (INDEX_NT) void k_index_sums (const u32 *__restrict__ rec, u64 n, u32 lo, u32 hi, u64 *__restrict__ tile_kept, u64 *__restrict__ tile_locs)
+{
+  u32 cnt[INDEX_ITEMS], rank;
+  u64 locs, tl;
+  const u32 kt = index_tile_ranks (rec, n, (u64) blockIdx.x * INDEX_TILE, lo, hi, cnt, &rank, &locs, &tl);
+  if (threadIdx.x == 0) tile_kept[blockIdx.x] = kt, tile_locs[blockIdx.x] = tl;
+}
+
+/* exclusive scan of both tile sums in place (one workgroup); total[0] = words kept, total[1] = their occurrences */
+__global__ __launch_bounds__ (1024) void k_index_scan (u64 *__restrict__ tile_kept, u64 *__restrict__ tile_locs, u64 tiles, unsigned long long *__restrict__ total)
+{
+  __shared__ u64 wa[1024 / WAVE], wb[1024 / WAVE];
+  __shared__ u64 carry[2];
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  if (threadIdx.x == 0) carry[0] = carry[1] = 0;
+  __syncthreads ();
+  for (u64 base = 0; base < tiles; base += 1024) {
+    const u64 i = base + threadIdx.x;
+    const u64 a = i < tiles ? tile_kept[i] : 0, b = i < tiles ? tile_locs[i] : 0;
+    const u64 ai = wave_inclusive_scan (a, lane), bi = wave_inclusive_scan (b, lane);
+    if (lane == WAVE - 1) wa[wv] = ai, wb[wv] = bi;
+    __syncthreads ();
+    u64 ab = carry[0], bb = carry[1];
+    for (int w = 0; w < wv; w++) ab += wa[w], bb += wb[w];
+    if (i < tiles) tile_kept[i] = ab + ai - a, tile_locs[i] = bb + bi - b;
+    __syncthreads ();
+    if (threadIdx.x == 1023) carry[0] = ab + ai, carry[1] = bb + bi;
+    __syncthreads ();
+  }
+  if (threadIdx.x == 0) total[0] = carry[0], total[1] = carry[1];
+}
+
+/* kmers[2 j], kmers[2 j + 1] = the j-th kept word and the occurrences of the kept words in front of it */
+__global__ __launch_bounds__ (INDEX_NT) void k_index_write (const u32 *__restrict__ rec, u64 n, u32 lo, u32 hi, const u64 *__restrict__ tile_kept, const u64 *__restrict__ tile_locs,
+                                                           u64 *__restrict__ kmers)
+{
+  u32 cnt[INDEX_ITEMS], rank;
+  u64 locs, tl;
+  index_tile_ranks (rec, n, (u64) blockIdx.x * INDEX_TILE, lo, hi, cnt, &rank, &locs, &tl);
+  u64 j = tile_kept[blockIdx.x] + rank, at = tile_locs[blockIdx.x] + locs;
+#pragma unroll
+  for (int r = 0; r < INDEX_ITEMS; r++) {
+    if (!cnt[r]) continue;
+    const u64 i = (u64) blockIdx.x * INDEX_TILE + (u64) threadIdx.x * INDEX_ITEMS + r;
+    kmers[2 * j] = (u64) rec[3 * i] | ((u64) rec[3 * i + 1] << 32);
+    kmers[2 * j + 1] = at;
+    j++;
+    at += cnt[r];
+  }
+}
+
 }  // namespace
 
 }  // namespace gt4
@@ -430,12 +690,15 @@ __global__ __launch_bounds__ (FOLD_NT) void k_fold_records (const u64 *__restric
 using namespace gt4;
 
 /* Sorts n 64-bit words in device memory ascending; `tmp` holds n more.  The sorted words end up in
- * `words` or in `tmp` (odd number of passes): *result says where. */
-static int radix_sort_device (gt4hip_context *ctx, u64 *words, u64 *tmp, uint64_t n, uint32_t word_length, u64 **result)
+ * `words` or in `tmp` (odd number of passes): *result says where.  `who` names the entry point in the messages.  With `vals` (and `vtmp`, n more) every word takes
+ * its value along, stably: values of equal words stay in the order they came; *vresult says where they end up. */
+static int radix_sort_device (gt4hip_context *ctx, u64 *words, u64 *tmp, uint64_t n, uint32_t word_length, u64 **result, const char *who = "gt4hip_sort_words",
+                              u64 *vals = NULL, u64 *vtmp = NULL, u64 **vresult = NULL)
 {
   *result = words;
+  if (vresult) *vresult = vals;
   if (n < 2) return GT4HIP_OK;
-  if (n >= RADIX_VALUE) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_sort_words: %llu words", (unsigned long long) n);
+  if (n >= RADIX_VALUE) return gt4hip_fail (ctx, GT4HIP_EINVAL, "%s: %llu words", who, (unsigned long long) n);
   const uint32_t bits = word_length >= 32 ? 64 : 2 * word_length;
   /* ceil (bits / 9) passes; as many of them take 9 bits as it takes to cover the word, the others 8
    * (k = 25: 50 bits = 9 + 9 + 8 + 8 + 8 + 8, six passes instead of seven) */
@@ -453,14 +716,14 @@ static int radix_sort_device (gt4hip_context *ctx, u64 *words, u64 *tmp, uint64_
   }
   const uint32_t passes = plan.passes;
   const uint64_t tiles = (n + RADIX_TILE - 1) / RADIX_TILE;
-  if (tiles >= (1ull << 32)) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_sort_words: %llu words", (unsigned long long) n);
+  if (tiles >= (1ull << 32)) return gt4hip_fail (ctx, GT4HIP_EINVAL, "%s: %llu words", who, (unsigned long long) n);
   /* workspace: digit bases of every pass, a ticket per pass, the tile states */
   const size_t head = (size_t) RADIX_MAX_PASSES * RADIX_MAX_DIGITS * 8 + 64;
   const size_t state_bytes = (size_t) tiles * RADIX_MAX_DIGITS * 8;
   char *ws = NULL;
   void *ws_owner = NULL;
   if (gt4hip_block_alloc (ctx, head + state_bytes, (void **) &ws, &ws_owner))
-    return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_sort_words: workspace of %llu bytes", (unsigned long long) (head + state_bytes));
+    return gt4hip_fail (ctx, GT4HIP_ENOMEM, "%s: workspace of %llu bytes", who, (unsigned long long) (head + state_bytes));
   u64 *ghist = (u64 *) ws;
   u32 *tickets = (u32 *) (ws + (size_t) RADIX_MAX_PASSES * RADIX_MAX_DIGITS * 8);
   u32 *err = tickets + 15; /* (the 64 bytes behind the digit bases: a ticket per pass, then the error word) */
@@ -472,9 +735,15 @@ static int radix_sort_device (gt4hip_context *ctx, u64 *words, u64 *tmp, uint64_
   if (hb > (u64) ctx->n_cus * 8) hb = (u64) ctx->n_cus * 8;
   hipLaunchKernelGGL (k_radix_hist, dim3 ((unsigned) hb), dim3 (HIST_NT), 0, st, words, n, plan, ghist);
   hipLaunchKernelGGL (k_radix_bases, dim3 (passes), dim3 (RADIX_MAX_DIGITS), 0, st, ghist);
-  u64 *src = words, *dst = tmp;
+  u64 *src = words, *dst = tmp, *vsrc = vals, *vdst = vtmp;
   for (uint32_t p = 0; p < passes; p++) {
-    if (plan.bits[p] == 9) hipLaunchKernelGGL (k_radix_scatter<9>, dim3 ((unsigned) tiles), dim3 (RADIX_NT), 0, st, src, dst, n, p, plan.shift[p], ghist, state, tickets + p, err, spin_limit);
+    if (vals) {
+      if (plan.bits[p] == 9)
+        hipLaunchKernelGGL (k_radix_scatter_pairs<9>, dim3 ((unsigned) tiles), dim3 (RADIX_NT), 0, st, src, dst, vsrc, vdst, n, p, plan.shift[p], ghist, state, tickets + p, err, spin_limit);
+      else
+        hipLaunchKernelGGL (k_radix_scatter_pairs<8>, dim3 ((unsigned) tiles), dim3 (RADIX_NT), 0, st, src, dst, vsrc, vdst, n, p, plan.shift[p], ghist, state, tickets + p, err, spin_limit);
+      std::swap (vsrc, vdst);
+    } else if (plan.bits[p] == 9) hipLaunchKernelGGL (k_radix_scatter<9>, dim3 ((unsigned) tiles), dim3 (RADIX_NT), 0, st, src, dst, n, p, plan.shift[p], ghist, state, tickets + p, err, spin_limit);
     else hipLaunchKernelGGL (k_radix_scatter<8>, dim3 ((unsigned) tiles), dim3 (RADIX_NT), 0, st, src, dst, n, p, plan.shift[p], ghist, state, tickets + p, err, spin_limit);
     u64 *const t = src;
     src = dst;
@@ -484,9 +753,10 @@ static int radix_sort_device (gt4hip_context *ctx, u64 *words, u64 *tmp, uint64_
   if (e == hipSuccess) e = hipMemcpyAsync (ctx->scratch_host, err, 4, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize (st);
   gt4hip_block_free (ws_owner);
-  if (e != hipSuccess) return gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_sort_words: %s", hipGetErrorString (e));
-  if ((u32) ctx->scratch_host[0]) return gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_sort_words: a chained-scan wait gave up (device shared with a stuck workgroup?)");
+  if (e != hipSuccess) return gt4hip_fail (ctx, GT4HIP_EHIP, "%s: %s", who, hipGetErrorString (e));
+  if ((u32) ctx->scratch_host[0]) return gt4hip_fail (ctx, GT4HIP_EHIP, "%s: a chained-scan wait gave up (device shared with a stuck workgroup?)", who);
   *result = src;
+  if (vresult) *vresult = vsrc;
   return GT4HIP_OK;
 }
 
@@ -591,4 +861,105 @@ extern "C" int gt4hip_words_to_list (gt4hip_context *ctx, const uint64_t *host_w
   if (!rc) rc = gt4hip_device_words_to_list (ctx, words, n_words, word_length, out);
   hipFree (words);
   return rc;
+}
+
+/* ---- (word, value) pairs: glistmaker --index */
+
+extern "C" int gt4hip_sort_pairs (gt4hip_context *ctx, void *device_words, void *device_values, uint64_t n_pairs, uint32_t word_length)
+{
+  if (!ctx || (n_pairs && (!device_words || !device_values)) || !word_length || word_length > 32) return GT4HIP_EINVAL;
+  HIPCHK (ctx, hipSetDevice (ctx->device));
+  if (n_pairs < 2) return GT4HIP_OK;
+  u64 *tmp = NULL;
+  void *tmp_owner = NULL;
+  if (gt4hip_block_alloc (ctx, (size_t) n_pairs * 16, (void **) &tmp, &tmp_owner))
+    return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_sort_pairs: %llu bytes of scratch", (unsigned long long) n_pairs * 16);
+  u64 *res = NULL, *vres = NULL;
+  hipEventRecord (ctx->ev[0], ctx->stream);
+  int rc = radix_sort_device (ctx, (u64 *) device_words, tmp, n_pairs, word_length, &res, "gt4hip_sort_pairs", (u64 *) device_values, tmp + n_pairs, &vres);
+  hipEventRecord (ctx->ev[1], ctx->stream);
+  if (!rc && res != (u64 *) device_words) { /* (an odd number of passes: both streams lie in the scratch) */
+    hipError_t e = hipMemcpyAsync (device_words, res, (size_t) n_pairs * 8, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync (device_values, vres, (size_t) n_pairs * 8, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e != hipSuccess) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_sort_pairs: %s", hipGetErrorString (e));
+  }
+  hipError_t e = hipStreamSynchronize (ctx->stream);
+  if (!rc && e != hipSuccess) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_sort_pairs: %s", hipGetErrorString (e));
+  float ms = 0;
+  if (hipEventElapsedTime (&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->sort_ms = ms;
+  gt4hip_block_free (tmp_owner);
+  return rc;
+}
+
+/* The k-mer section of an index is a pooled block that the context owns, as the words of gt4hip_text_to_words are: one at a time. */
+extern "C" void gt4hip_index_free (gt4hip_context *ctx)
+{
+  if (!ctx || !ctx->index_kmers) return;
+  gt4hip_list_free (ctx->index_kmers);
+  ctx->index_kmers = NULL;
+}
+
+extern "C" int gt4hip_pairs_to_index (gt4hip_context *ctx, void *device_words, void *device_values, uint64_t n_pairs, uint32_t word_length, uint32_t min_locations,
+                                      uint32_t max_locations, gt4hip_index_arrays *out)
+{
+  if (!ctx || !out || (n_pairs && (!device_words || !device_values)) || !word_length || word_length > 32 || !min_locations || max_locations < min_locations) return GT4HIP_EINVAL;
+  HIPCHK (ctx, hipSetDevice (ctx->device));
+  gt4hip_index_free (ctx);
+  memset (out, 0, sizeof *out);
+  out->n_values = n_pairs;
+  out->d_locations = (const uint64_t *) device_values;
+  if (!n_pairs) return GT4HIP_OK;
+  int rc = gt4hip_sort_pairs (ctx, device_words, device_values, n_pairs, word_length);
+  if (rc) return rc;
+  gt4hip_list *runs = NULL;
+  if ((rc = fold_sorted_words (ctx, (const u64 *) device_words, n_pairs, word_length, &runs))) return rc;
+  TempLists tmp;
+  tmp.adopt (runs);
+  const uint64_t n_runs = runs->n_words, tiles = (n_runs + INDEX_TILE - 1) / INDEX_TILE;
+  if (tiles >= (1ull << 31)) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_pairs_to_index: %llu distinct words", (unsigned long long) n_runs);
+  u64 *sums = NULL;
+  void *sums_owner = NULL;
+  if (gt4hip_block_alloc (ctx, (size_t) tiles * 16, (void **) &sums, &sums_owner)) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_pairs_to_index: workspace");
+  hipStream_t st = ctx->stream;
+  const u32 *rec = (const u32 *) runs->dev;
+  if (n_pairs > 0xffffffffull) {
+    /* the fold keeps a word's occurrences in 32 bits, as the reference does: with that many pairs one word may have more,
+     * and its record would then hold the count mod 2^32.  All records kept, the counts must add up to the pairs. */
+    hipLaunchKernelGGL (k_index_sums, dim3 ((unsigned) tiles), dim3 (INDEX_NT), 0, st, rec, n_runs, 1u, 0xffffffffu, sums, sums + tiles);
+    hipLaunchKernelGGL (k_index_scan, dim3 (1), dim3 (1024), 0, st, sums, sums + tiles, tiles, ctx->scratch);
+    rc = gt4hip_read_scratch (ctx, 2);
+    if (!rc && ctx->scratch_host[1] != n_pairs)
+      rc = gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_pairs_to_index: a word with 2^32 or more locations (the counts of %llu pairs add up to %llu)", (unsigned long long) n_pairs,
+                        (unsigned long long) ctx->scratch_host[1]);
+    if (rc) {
+      gt4hip_block_free (sums_owner);
+      return rc;
+    }
+  }
+  hipLaunchKernelGGL (k_index_sums, dim3 ((unsigned) tiles), dim3 (INDEX_NT), 0, st, rec, n_runs, min_locations, max_locations, sums, sums + tiles);
+  hipLaunchKernelGGL (k_index_scan, dim3 (1), dim3 (1024), 0, st, sums, sums + tiles, tiles, ctx->scratch);
+  rc = gt4hip_read_scratch (ctx, 2);
+  const uint64_t n_kmers = ctx->scratch_host[0], n_locations = ctx->scratch_host[1];
+  if (!rc && n_kmers) {
+    void *kmers = NULL, *owner = NULL;
+    if (gt4hip_block_alloc (ctx, (size_t) n_kmers * 16, &kmers, &owner)) {
+      rc = gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_pairs_to_index: %llu k-mers", (unsigned long long) n_kmers);
+    } else {
+      ctx->index_kmers = (gt4hip_list *) owner;
+      hipLaunchKernelGGL (k_index_write, dim3 ((unsigned) tiles), dim3 (INDEX_NT), 0, st, rec, n_runs, min_locations, max_locations, sums, sums + tiles, (u64 *) kmers);
+      hipError_t e = hipGetLastError ();
+      if (e == hipSuccess) e = hipStreamSynchronize (st);
+      if (e != hipSuccess) {
+        gt4hip_index_free (ctx);
+        rc = gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_pairs_to_index: %s", hipGetErrorString (e));
+      } else {
+        out->d_kmers = (const uint64_t *) kmers;
+      }
+    }
+  }
+  gt4hip_block_free (sums_owner);
+  if (rc) return rc;
+  out->n_kmers = n_kmers;
+  out->n_locations = n_locations;
+  return GT4HIP_OK;
 }

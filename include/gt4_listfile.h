@@ -114,6 +114,29 @@ int gt4_listwriter_finish (GT4ListWriter *w, uint64_t n_words, uint64_t total_co
 /* Closes without finishing (caller unlinks). */
 void gt4_listwriter_abort (GT4ListWriter *w);
 
+/* ---- the head of a GT4I index file as glistmaker --index writes it (reference src/glistmaker.c:366-422, :576-626) */
+
+/* one sequence of an input file: byte offsets in the file (name_len is written in 32 bits) */
+typedef struct {
+  uint64_t name_pos, name_len, seq_pos, seq_len;
+} GT4IndexSubseq;
+
+typedef struct {
+  const char *name; /* as given on the command line */
+  uint64_t size;    /* of the file, bytes */
+  uint64_t n_subseqs;
+  const GT4IndexSubseq *subseqs;
+} GT4IndexInput;
+
+/* The 72-byte header and, when there is a k-mer at all (have_words), the file block behind it, zero-padded to 8 bytes:
+ * everything in front of the k-mer section, in malloc'ed memory (*head, *head_bytes; the caller frees it).  The k-mer
+ * section (16 bytes a k-mer) and the locations (8 bytes each) follow it in the file.  The two version fields of the file
+ * block are written with their upper halves zero (the reference writes four bytes from a two-byte variable there).
+ * Without words the header says what write_index_header says for an empty index: one bit per field, every offset 72.
+ * Returns nonzero when memory runs out. */
+int gt4_index_head_build (unsigned int word_length, int have_words, uint64_t n_kmers, uint64_t n_locations, unsigned int file_bits, unsigned int subseq_bits,
+                          unsigned int pos_bits, const GT4IndexInput *inputs, unsigned int n_inputs, void **head, size_t *head_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -398,6 +398,37 @@ int gt4hip_words_to_list (gt4hip_context *ctx, const uint64_t *host_words, uint6
 int gt4hip_device_words_to_list (gt4hip_context *ctx, void *device_words, uint64_t n_words, uint32_t word_length,
                                  gt4hip_list **out);
 
+/* ---------------------------------------------------------------- glistmaker --index: words with a value each */
+
+/* gt4hip_sort_words for (word, value) pairs: n_pairs words and as many 64-bit values (two device arrays), both in
+ * place, ascending by word over its 2 * word_length significant bits.  The same digits and chained scan; every pass
+ * moves 32 bytes per pair.  Stable: the values of equal words stay in the order they came, so values that ascend in
+ * the input -- packed locations in text order -- ascend within every word afterwards (the order the reference sorts
+ * them into, src/glistmaker.c:569).  Needs n_pairs * 16 bytes of scratch + the scan state of gt4hip_sort_words. */
+int gt4hip_sort_pairs (gt4hip_context *ctx, void *device_words, void *device_values, uint64_t n_pairs,
+                       uint32_t word_length);
+
+/* The two arrays behind the file block of a GT4I index (reference src/glistmaker.c:425-574), in device memory. */
+typedef struct {
+  uint64_t n_kmers;             /* words kept by the cut-offs                                                        */
+  uint64_t n_locations;         /* values of the kept words: what the index header calls n_locations                 */
+  uint64_t n_values;            /* values in d_locations: all of them, the cut-offs do not filter this section (:568) */
+  const uint64_t *d_kmers;      /* n_kmers x (word, index of its first value counting the kept words' values only)   */
+  const uint64_t *d_locations;  /* the caller's values, sorted by word, in text order within a word                   */
+} gt4hip_index_arrays;
+
+/* write_kmers + write_locations (:425-574) for pairs in device memory: gt4hip_sort_pairs, equal words folded, words
+ * with fewer than min_locations or more than max_locations values dropped from the k-mer section (:486).  Start
+ * indices advance over the kept words only, and the values stay unfiltered, as in the reference: with cut-offs the two
+ * sections do not agree, and a reader gets what the reference's file gives it.  Both input arrays are sorted in place;
+ * d_locations is device_values.  d_kmers is the context's, one at a time: it lasts until gt4hip_index_free, the
+ * context's next gt4hip_pairs_to_index or gt4hip_destroy.  Download either with gt4hip_words_download.  A word's values are
+ * counted in 32 bits, as the reference counts them (:459): a word with 2^32 or more is GT4HIP_EINVAL, nothing is returned. */
+int gt4hip_pairs_to_index (gt4hip_context *ctx, void *device_words, void *device_values, uint64_t n_pairs,
+                           uint32_t word_length, uint32_t min_locations, uint32_t max_locations,
+                           gt4hip_index_arrays *out);
+void gt4hip_index_free (gt4hip_context *ctx);
+
 /* ---------------------------------------------------------------- glistmaker's front: sequence text -> words */
 
 enum {
@@ -446,6 +477,61 @@ int gt4hip_words_download (gt4hip_context *ctx, const uint64_t *d_words, uint64_
 /* One whole text -> the list glistmaker writes for it: gt4hip_text_to_words, then gt4hip_device_words_to_list. */
 int gt4hip_text_to_list (gt4hip_context *ctx, const void *text, size_t n_bytes, unsigned word_length, unsigned flags,
                          gt4hip_list **out);
+
+/* ---------------------------------------------------------------- glistmaker --index: where every word stands */
+
+/* One sequence of a file as the file block of a GT4I index records it (reference src/glistmaker.c:659-692): byte offsets
+ * in the file; seq_len runs to the next name's tag or the end of the file (FastA, line breaks included) or to the end of
+ * the sequence line (FastQ).  The file holds name_len in 32 bits. */
+typedef struct {
+  uint64_t name_pos, name_len, seq_pos, seq_len;
+} gt4hip_subseq;
+
+/* gt4hip_maker_carry for gt4hip_text_to_locations: hand the `out` of a piece to the next piece as `in`; NULL starts a file. */
+typedef struct {
+  gt4hip_maker_carry reader;
+  uint64_t offset;        /* bytes of the file in front of the next piece                                               */
+  uint64_t n_events;      /* name starts, sequence starts and FastQ sequence ends so far                                */
+  uint64_t n_subseqs;     /* sequences begun so far: the ordinal of the next one                                        */
+  uint64_t seq_codes;     /* bytes >= ' ' since the last sequence began                                                 */
+  uint64_t max_position;  /* largest position of a word so far (the reference's max_lpos)                               */
+  uint64_t name_pos;      /* of the name begun last                                                                     */
+  uint64_t seq_pos;       /* of the sequence begun last                                                                 */
+  uint32_t seq_open;      /* that sequence has not ended: at the end of the file its seq_len is file size - seq_pos     */
+  uint32_t pad;
+} gt4hip_locations_carry;
+
+/* what a piece gave beside its words */
+typedef struct {
+  uint64_t n_words;
+  uint64_t n_subseqs;            /* sequences that begin in the piece                                                   */
+  const gt4hip_subseq *subseqs;  /* host memory of the context: until gt4hip_locations_free, the context's next
+                                    gt4hip_text_to_locations or gt4hip_destroy.  seq_len is 0 where the sequence -- the
+                                    last one -- is still open behind the piece (out->seq_open)                          */
+  uint64_t closed_seq_len;       /* closed: the sequence that was open in front of the piece ended in it, this long     */
+  uint32_t closed, pad;
+} gt4hip_locations_piece;
+
+/* gt4hip_text_to_words that also says where every word stands (read_word_index, src/glistmaker.c:1054-1067): word i of
+ * the piece into d_words[i] and ordinal << 33 | position << 1 | strand into d_raw[i] -- the ordinal of its sequence
+ * within the file, the bytes >= ' ' of that sequence in front of the word (:1064), and 1 when the canonical word is the
+ * reverse complement.  d_words and d_raw are the caller's device arrays of `capacity` words each (gt4hip_pairs_reserve,
+ * or any device memory): a piece with more words is GT4HIP_ENOMEM and writes nothing.  An ordinal of 2^31 or a position
+ * of 2^32 or more is GT4HIP_EINVAL.  GT4HIP_MAKER_FORWARD_ONLY is not accepted.  Errors of the text as in gt4hip_text_to_words,
+ * the kind in out->reader.error. */
+int gt4hip_text_to_locations (gt4hip_context *ctx, const void *text, size_t n_bytes, unsigned word_length, unsigned flags,
+                              const gt4hip_locations_carry *in, gt4hip_locations_carry *out, uint64_t *d_words,
+                              uint64_t *d_raw, uint64_t capacity, gt4hip_locations_piece *piece, uint64_t *error_offset);
+void gt4hip_locations_free (gt4hip_context *ctx);
+/* n raw locations of file number `file` (device memory, in place) -> the words of an index's location section:
+ * file << (subseq_bits + pos_bits + 1) | ordinal << (pos_bits + 1) | position << 1 | strand (:1066).  The bit sizes are
+ * known behind the last file only, hence a step of its own.  Sizes that do not fit 64 bits together are GT4HIP_EINVAL. */
+int gt4hip_pack_locations (gt4hip_context *ctx, uint64_t *d_raw, uint64_t n, uint64_t file, unsigned subseq_bits,
+                           unsigned pos_bits);
+/* Device memory for n_pairs words and as many values, one block of the context (one at a time): until
+ * gt4hip_pairs_release, the context's next gt4hip_pairs_reserve or gt4hip_destroy.  GT4HIP_ENOMEM names the bytes. */
+int gt4hip_pairs_reserve (gt4hip_context *ctx, uint64_t n_pairs, uint64_t **d_words, uint64_t **d_values);
+void gt4hip_pairs_release (gt4hip_context *ctx);
 
 /* ---------------------------------------------------------------- synthetic lists (bench) */
 
