@@ -110,6 +110,8 @@ SYMBOLS = [
     "gt4hip_query_index_create", "gt4hip_query_index_free", "gt4hip_query_index_last_ms", "gt4hip_query_variants",
     "gt4hip_query_variant_mask", "gt4hip_query_lookup", "gt4hip_query_lookup_all", "gt4hip_list_count_stats",
     "gt4hip_list_count_split", "gt4hip_list_count_histogram", "gt4hip_list_gc",
+    "gt4hip_location_index_create", "gt4hip_location_index_free", "gt4hip_location_index_list", "gt4hip_location_index_n_locations",
+    "gt4hip_query_lookup_locations", "gt4hip_query_index_gather_ms",
     "gt4hip_text_to_words", "gt4hip_words_free", "gt4hip_words_download", "gt4hip_text_to_list",
     "gt4hip_sort_pairs", "gt4hip_pairs_to_index", "gt4hip_index_free",
     "gt4hip_text_to_locations", "gt4hip_locations_free", "gt4hip_pack_locations", "gt4hip_pairs_reserve", "gt4hip_pairs_release",
@@ -198,6 +200,12 @@ def lib():
             "gt4hip_query_variant_mask": (C.c_int, [u32, C.POINTER(QueryParams), u64, C.POINTER(u64)]),
             "gt4hip_query_lookup": (C.c_int, [vp, vp, vp, u64, C.POINTER(QueryParams), vp, vp]),
             "gt4hip_query_lookup_all": (C.c_int, [vp, vp, vp, u64, C.POINTER(QueryParams), vp, u64, C.POINTER(u64)]),
+            "gt4hip_location_index_create": (C.c_int, [vp, vp, u64, vp, u64, u32, u32, u32, u32, C.POINTER(vp)]),
+            "gt4hip_location_index_free": (None, [vp]),
+            "gt4hip_location_index_list": (vp, [vp]),
+            "gt4hip_location_index_n_locations": (u64, [vp]),
+            "gt4hip_query_lookup_locations": (C.c_int, [vp, vp, vp, vp, u64, C.POINTER(QueryParams), vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64)]),
+            "gt4hip_query_index_gather_ms": (C.c_double, [vp]),
             "gt4hip_list_count_stats": (C.c_int, [vp, vp, C.POINTER(u32), C.POINTER(u32)]),
             "gt4hip_list_count_split": (C.c_int, [vp, vp, u32, C.POINTER(u64), C.POINTER(u64)]),
             "gt4hip_list_count_histogram": (C.c_int, [vp, vp, u32, vp]),
@@ -392,6 +400,65 @@ class QueryIndex:
         if self.h and self.ctx.h:
             lib().gt4hip_query_index_free(self.h)
         self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+LOCATION_DTYPE = np.dtype([("pos_dir", "<u8"), ("file", "<u4"), ("seq", "<u4")])  # gt4hip_location
+
+
+class LocationIndex:
+    """Owning handle of a gt4hip_location_index: a GT4I index resident with its locations, and the bucket index of its
+    k-mer list.  `kmers`: (n, 2) u64 (word, first location); `locations`: the packed words; `bits`: (file, sequence,
+    position) bit sizes.  Creation raises Gt4HipError (EFORMAT) for first locations that descend or pass the end."""
+
+    def __init__(self, ctx, kmers, locations, word_length, bits, num_locations=None):
+        self.ctx = ctx
+        km = np.ascontiguousarray(kmers, dtype=np.uint64).reshape(-1, 2)
+        loc = np.ascontiguousarray(locations, dtype=np.uint64)
+        n_loc = len(loc) if num_locations is None else num_locations
+        self.h, self.q = C.c_void_p(), C.c_void_p()
+        ctx._chk(lib().gt4hip_location_index_create(ctx.h, km.ctypes.data if len(km) else None, len(km), loc.ctypes.data if len(loc) else None, n_loc,
+                                                    word_length, bits[0], bits[1], bits[2], C.byref(self.h)))
+        ctx._lists.add(self)
+        ctx._chk(lib().gt4hip_query_index_create(ctx.h, lib().gt4hip_location_index_list(self.h), C.byref(self.q)))
+
+    @property
+    def gather_ms(self) -> float:
+        return lib().gt4hip_query_index_gather_ms(self.q)
+
+    def lookup_raw(self, words, n_mm=0, pm_3=0, canonize=True, hit_capacity=0, loc_capacity=0, fill=0xA5):
+        """One call of gt4hip_query_lookup_locations: (n_hits, n_locations, hits, locations), the two arrays of the given
+        capacities preset to the byte `fill` (None: left as allocated)."""
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        prm, nh, nl = QueryParams(n_mm, pm_3, 1 if canonize else 0), C.c_uint64(), C.c_uint64()
+        hits, locs = np.empty(hit_capacity, dtype=QUERY_HIT_DTYPE), np.empty(loc_capacity, dtype=LOCATION_DTYPE)
+        if fill is not None:
+            hits.view(np.uint8)[:] = fill
+            locs.view(np.uint8)[:] = fill
+        self.ctx._chk(lib().gt4hip_query_lookup_locations(self.ctx.h, self.q, self.h, w.ctypes.data if len(w) else None, len(w), C.byref(prm),
+                                                           hits.ctypes.data if hit_capacity else None, hit_capacity, C.byref(nh),
+                                                           locs.ctypes.data if loc_capacity else None, loc_capacity, C.byref(nl)))
+        return nh.value, nl.value, hits, locs
+
+    def lookup(self, words, n_mm=0, pm_3=0, canonize=True):
+        """(hits, locations) of every variant found: size, then fill."""
+        nh, nl, _, _ = self.lookup_raw(words, n_mm, pm_3, canonize)
+        nh2, nl2, hits, locs = self.lookup_raw(words, n_mm, pm_3, canonize, nh, nl)
+        assert (nh2, nl2) == (nh, nl)
+        return hits, locs
+
+    def free(self):
+        if self.ctx.h:
+            if self.q:
+                lib().gt4hip_query_index_free(self.q)
+            if self.h:
+                lib().gt4hip_location_index_free(self.h)
+        self.h = self.q = None
 
     def __del__(self):
         try:

@@ -11,21 +11,41 @@
  * looked up in one call per batch and printed in input order.
  * Deliberate differences, all loud:
  *   - gzip-compressed sequence files (-s) are refused: error + exit 1;
- *   - --locations, --files and --sequences are refused (the location tables of a GT4I index are not
- *     resident): error + exit 1.  A GT4I index given as a list is read as the sorted k-mer list it
+ *   - --locations with a plain .list on the command line is refused: error + exit 1, no device opened (the reference
+ *     ignores the option there).  --files and --sequences on anything but one index are the reference's own errors,
+ *     with a second line that names the option.  Without --locations a GT4I index is read as the sorted k-mer list it
  *     contains, as glistcompare here does;
+ *   - --sequences reads the names out of the source files on the host, as the reference does; a source that cannot be
+ *     mapped gives the reference's message and an EMPTY name (the reference prints an uninitialised buffer), and a name
+ *     is cut at the end of its source file (the reference reads past it);
+ *   - -l X.index is refused as the reference refuses it (it streams the query list, which takes a .list only:
+ *     "invalid or corrupted", exit 1); earlier versions of this program read the index as the list it holds;
+ *   - an index whose sections do not fit its file, or whose k-mer section points outside its location section, is
+ *     refused (gt4_indexfile_open, gt4hip_location_index_create): error + exit 1;
  *   - --bloom and --disable_scouts are accepted and ignored;
  *   - --distribution skips a record whose count is 0 (the reference writes before its array there);
  *   - more than 1024 lists are an error (the reference overruns its array);
  *   - -D prints "List ... loaded" and print_median's trace lines, nothing else is promised;
  *   - --stat reads headers only and -v / -h nothing at all: they work without a GPU.  The dump of ONE
- *     list (no query option) is file I/O: it prints the mapped records and opens no device either.
+ *     list (no query option) is file I/O: it prints the mapped records and opens no device either, with --locations
+ *     too; so are --files and --sequences.
  *     Everything else fails without a usable GPU: there is no CPU path;
  *   - the list must fit one device (as for glistcompare -mm); larger is an out-of-memory error;
  *   - --words-only (not in the reference) prints the packed query words -q / -f / -s / -l would look up,
  *     one decimal number per line, and opens no device: for tests of the parsers.
- * Argv is read in parse_argv() alone.  No environment variable is read here: GT4HIP_DEVICE picks the device of the
- * library's default context, GT4HIP_HBM_LIMIT and GT4HIP_VERBOSE act inside the multi-list calls (gt4_setops.c).
+ * With --locations the queries go through gt4hip_query_lookup_locations, batch by batch: every hit is printed as
+ * WORD, count, REVERSE and one line per location (search_one_word / cb_print / print_index_info, :469-476, :528-568).
+ * REVERSE is the reference's sticky flag: set by the first query whose reverse complement is the smaller word and never
+ * cleared, so every later query of the run prints 1 and flipped strands; the host carries it across batches in input
+ * order.  On the device a lookup takes 16 bytes per location and 56 per hit (the 40-byte record and two 8-byte offsets):
+ * a batch may hold at most B = A QUARTER OF THE FREE DEVICE MEMORY / 72 locations and as many hits (gt4hip_device_memory,
+ * read once behind the upload of the index; never fewer than 2^16 each), which is a quarter of that memory at worst.  A
+ * batch with more of either, or one the library still answers with out-of-memory, is cut in two halves that are looked
+ * up one after the other (and those again); a single query over the budget is an out-of-memory error.
+ * Argv is read in parse_argv() alone.  One environment variable is read here, for tests only:
+ * GT4_GLISTQUERY_LOCATION_BUDGET = the most locations a batch may hold, in place of B (the hits keep theirs).  GT4HIP_DEVICE
+ * picks the device of the library's default context, GT4HIP_HBM_LIMIT and GT4HIP_VERBOSE act inside the multi-list
+ * calls (gt4_setops.c).
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -34,6 +54,10 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
 
 #include "gt4_cli.h"
 #include "gt4_listfile.h"
@@ -42,6 +66,8 @@
 
 #define MAX_LISTS 1024
 #define QUERY_BATCH (1u << 20)
+/* device bytes of a location lookup per location (the 16-byte record) plus per hit (the 40-byte hit, its two 8-byte offsets) */
+#define LOOKUP_BYTES (sizeof (gt4hip_location) + sizeof (gt4hip_query_hit) + 16)
 
 enum { CMD_QUERY, CMD_STATS, CMD_GC, CMD_MEDIAN, CMD_DISTRO, CMD_FILES, CMD_SEQUENCES };
 
@@ -335,6 +361,13 @@ typedef struct {
   uint8_t *found;
   gt4hip_query_hit *hits;
   uint64_t hit_capacity;
+  /* --locations */
+  const gt4hip_location_index *lindex;
+  gt4hip_location *locs;
+  uint64_t loc_capacity, loc_budget, hit_budget; /* the most locations, and hits, a batch may hold */
+  uint8_t *reverse;       /* per query of the batch: the sticky flag as it stood behind that query */
+  uint32_t *query_counts; /* the zipper (-l without mismatches): the QUERY list's count of every word */
+  int sticky, zipper;
 } Searcher;
 
 /* The place of a variant in the pre-order of gt4_word_table_generate_mismatches (src/word-table.c:360-382): the
@@ -343,9 +376,20 @@ typedef struct {
 typedef struct {
   unsigned char key[36];
   const gt4hip_query_hit *hit;
+  uint64_t first_location; /* --locations: of the hit, in the batch's locations */
 } OrderedHit;
 
 static int ordered_cmp (const void *a, const void *b) { return strcmp ((const char *) ((const OrderedHit *) a)->key, (const char *) ((const OrderedHit *) b)->key); }
+
+/* print_index_info, :469-477 */
+static void print_locations (const gt4hip_location *l, uint64_t n, unsigned int reverse)
+{
+  for (uint64_t i = 0; i < n; i++)
+    fprintf (stdout, "%u\t%u\t%llu\t%u\n", l[i].file, l[i].seq, (unsigned long long) (l[i].pos_dir >> 1), (unsigned int) (l[i].pos_dir & 1) ^ reverse);
+}
+
+static void print_hits (Searcher *s, uint64_t first, uint64_t n, uint64_t n_hits, const gt4hip_location *locs);
+static void flush_locations (Searcher *s, uint64_t first, uint64_t n);
 
 static void flush_batch (Searcher *s)
 {
@@ -353,6 +397,11 @@ static void flush_batch (Searcher *s)
   if (!s->n) return;
   if (s->o->words_only) {
     for (uint64_t i = 0; i < s->n; i++) fprintf (stdout, "%llu\n", (unsigned long long) s->words[i]);
+    s->n = 0;
+    return;
+  }
+  if (s->lindex) {
+    flush_locations (s, 0, s->n);
     s->n = 0;
     return;
   }
@@ -379,10 +428,19 @@ static void flush_batch (Searcher *s)
     s->hits = (gt4hip_query_hit *) or_oom (malloc ((size_t) n_hits * sizeof (gt4hip_query_hit)), "%llu hits", (unsigned long long) n_hits);
     CHK (s->ctx, gt4hip_query_lookup_all (s->ctx, s->qindex, s->words, s->n, &s->prm, s->hits, s->hit_capacity, &n_hits));
   }
+  print_hits (s, 0, s->n, n_hits, NULL);
+  s->n = 0;
+}
+
+/* The hits of queries [first, first + n) of the batch (hit.query counts from `first`), query by query in the reference's
+ * order.  locs == NULL: WORD, count.  Else WORD, count, REVERSE and the locations of the hit, which lie in `locs` hit by hit. */
+static void print_hits (Searcher *s, uint64_t first, uint64_t n, uint64_t n_hits, const gt4hip_location *locs)
+{
+  char b[64];
   OrderedHit *ord = NULL;
   size_t ord_cap = 0;
-  uint64_t h = 0;
-  for (uint64_t i = 0; i < s->n; i++) {
+  uint64_t h = 0, at = 0;
+  for (uint64_t i = 0; i < n; i++) {
     uint64_t e = h;
     while (e < n_hits && s->hits[e].query == i) e++;
     const size_t m = (size_t) (e - h);
@@ -401,29 +459,83 @@ static void flush_batch (Searcher *s)
       }
       ord[j].key[len] = 0;
       ord[j].hit = &s->hits[h + j];
+      ord[j].first_location = at;
+      at += s->hits[h + j].count;
       sum += s->hits[h + j].count;
     }
     if (m > 1) qsort (ord, m, sizeof *ord, ordered_cmp);
     for (size_t j = 0; j < m; j++) {
       gt4_word2string (b, ord[j].hit->word, s->k);
-      fprintf (stdout, "%s\t%u\n", b, ord[j].hit->count);
+      if (!locs) {
+        fprintf (stdout, "%s\t%u\n", b, ord[j].hit->count);
+        continue;
+      }
+      const unsigned int rev = s->zipper ? 0 : s->reverse[first + i];
+      fprintf (stdout, "%s\t%u\t%u\n", b, s->zipper ? s->query_counts[first + i] : ord[j].hit->count, rev);
+      print_locations (locs + ord[j].first_location, ord[j].hit->count, rev);
     }
     /* the reference's return value: with mismatches the summed count, without them "found" */
     const int none = s->prm.n_mm ? sum == 0 : m == 0;
-    if (none && !s->o->minfreq) {
-      gt4_word2string (b, s->words[i], s->k);
+    if (none && !s->o->minfreq && !s->zipper) {
+      gt4_word2string (b, s->words[first + i], s->k);
       fprintf (stdout, "%s\t0\n", b);
     }
     h = e;
   }
   free (ord);
-  s->n = 0;
 }
 
-/* search_one_word: the query is looked up as its canonical form */
+/* queries [first, first + n) of the batch with their locations; more locations than a batch may hold: by halves */
+static void flush_locations (Searcher *s, uint64_t first, uint64_t n)
+{
+  uint64_t n_hits = 0, n_locs = 0;
+  int rc = gt4hip_query_lookup_locations (s->ctx, s->qindex, s->lindex, s->words + first, n, &s->prm, s->hits, s->hit_capacity, &n_hits, s->locs, s->loc_capacity,
+                                          &n_locs);
+  const int fits = n_locs <= s->loc_budget && n_hits <= s->hit_budget;
+  if (rc == GT4HIP_OK && fits && (n_hits > s->hit_capacity || n_locs > s->loc_capacity)) {
+    if (n_hits > s->hit_capacity) {
+      free (s->hits);
+      s->hit_capacity = n_hits;
+      s->hits = (gt4hip_query_hit *) or_oom (malloc ((size_t) n_hits * sizeof (gt4hip_query_hit)), "%llu hits", (unsigned long long) n_hits);
+    }
+    if (n_locs > s->loc_capacity) {
+      free (s->locs);
+      s->loc_capacity = n_locs;
+      s->locs = (gt4hip_location *) or_oom (malloc ((size_t) n_locs * sizeof (gt4hip_location)), "%llu locations", (unsigned long long) n_locs);
+    }
+    rc = gt4hip_query_lookup_locations (s->ctx, s->qindex, s->lindex, s->words + first, n, &s->prm, s->hits, s->hit_capacity, &n_hits, s->locs, s->loc_capacity,
+                                        &n_locs);
+  }
+  /* over the budget, or the device ran out all the same (the budget is an estimate): by halves */
+  if ((rc == GT4HIP_OK && !fits) || rc == GT4HIP_ENOMEM) {
+    if (n == 1) {
+      char b[64];
+      gt4_word2string (b, s->words[first], s->k);
+      if (rc == GT4HIP_OK)
+        fprintf (stderr, "Error: out of memory: the %llu hits and %llu locations of the query %s alone are more than a batch may hold (%llu and %llu)\n",
+                 (unsigned long long) n_hits, (unsigned long long) n_locs, b, (unsigned long long) s->hit_budget, (unsigned long long) s->loc_budget);
+      else fprintf (stderr, "Error: out of memory: the query %s alone does not fit the device: %s\n", b, gt4hip_last_error (s->ctx));
+      exit (1);
+    }
+    flush_locations (s, first, n / 2);
+    flush_locations (s, first + n / 2, n - n / 2);
+    return;
+  }
+  if (rc != GT4HIP_OK) {
+    fprintf (stderr, "Error: gt4hip_query_lookup_locations: %s\n", gt4hip_last_error (s->ctx));
+    exit (1);
+  }
+  print_hits (s, first, n, n_hits, s->locs);
+}
+
+/* search_one_word: the query is looked up as its canonical form; REVERSE is set where that is the reverse complement
+ * and stays set (:548-551) */
 static void search_one_word (Searcher *s, uint64_t word)
 {
-  s->words[s->n++] = s->o->words_only ? word : canonical_word (word, s->k);
+  const uint64_t cw = s->zipper ? word : canonical_word (word, s->k);
+  if (cw != word) s->sticky = 1;
+  if (s->reverse) s->reverse[s->n] = (uint8_t) s->sticky;
+  s->words[s->n++] = s->o->words_only ? word : cw;
   if (s->n == QUERY_BATCH) flush_batch (s);
 }
 
@@ -693,9 +805,24 @@ static void validate (const Options *o)
     fprintf (stderr, "No list/index files specified!\n");
     print_help (1);
   }
-  if (o->locations || o->command == CMD_FILES || o->command == CMD_SEQUENCES) {
-    fprintf (stderr, "Error: %s is not supported: the location tables of an index are not loaded\n",
-             o->command == CMD_FILES ? "--files" : o->command == CMD_SEQUENCES ? "--sequences" : "--locations");
+}
+
+/* what needs an index, checked behind open_inputs and in front of every device */
+static void validate_index_options (const Options *o, const Input *maps)
+{
+  const Input *list = NULL;
+  for (unsigned int i = 0; i < o->n_lists && !list; i++)
+    if (!maps[i].is_index) list = &maps[i];
+  if (o->command == CMD_FILES || o->command == CMD_SEQUENCES) {
+    if (!list && o->n_lists == 1) return;
+    fprintf (stderr, "Error: %s can only be queried from single index\n", o->command == CMD_FILES ? "Files" : "Sequences");
+    fprintf (stderr, "Error: %s needs one index", o->command == CMD_FILES ? "--files" : "--sequences");
+    if (list) fprintf (stderr, ": %s is a list\n", list->name);
+    else fprintf (stderr, ": %u were given\n", o->n_lists);
+    exit (1);
+  }
+  if (o->locations && list) {
+    fprintf (stderr, "Error: --locations needs an index: %s is a list\n", list->name);
     exit (1);
   }
 }
@@ -741,8 +868,11 @@ static unsigned int open_inputs (const Options *o, Input *maps, Input *query_inp
   }
   if (o->querylistfilename) {
     uint32_t code = 0;
-    if (list_code (o->querylistfilename, &code) || (code != GT4_LIST_CODE_VALUE && code != GT4_INDEX_CODE_VALUE) ||
-        input_open (query_input, o->querylistfilename, code)) {
+    /* the reference streams the query list (gt4_word_list_stream_new), which takes a .list only: an index is refused */
+    const int unreadable = list_code (o->querylistfilename, &code);
+    if (!unreadable && code == GT4_INDEX_CODE_VALUE)
+      fprintf (stderr, "gt4_word_list_stream_new: invalid file tag (%x, should be %x)\n", code, GT4_LIST_CODE_VALUE);
+    if (unreadable || code != GT4_LIST_CODE_VALUE || input_open (query_input, o->querylistfilename, code)) {
       fprintf (stderr, "Error: %s is invalid or corrupted\n", o->querylistfilename);
       invalid = 1;
     } else if (query_input->file.header.word_length != wlen) {
@@ -778,13 +908,92 @@ static int run_statistics (const Options *o, const Input *maps)
   return 0;
 }
 
-/* no query option, one list: the mapped records, no device */
-static int run_dump (const Input *in)
+/* one packed location of an index (index_map_get_location, src/index-map.c:197-208) as print_index_info prints it */
+static void print_packed_location (const GT4ListFile *f, uint64_t code)
+{
+  const unsigned int fb = f->index_file_bits, sb = f->index_subseq_bits, pb = f->index_pos_bits;
+#define FIELD(shift, bits) ((shift) >= 64 || !(bits) ? 0 : (code >> (shift)) & ((bits) >= 64 ? ~0ull : (1ull << (bits)) - 1))
+  fprintf (stdout, "%u\t%u\t%llu\t%u\n", (unsigned int) FIELD (sb + pb + 1, fb), (unsigned int) FIELD (pb + 1, sb), (unsigned long long) FIELD (1, pb),
+           (unsigned int) (code & 1));
+#undef FIELD
+}
+
+/* no query option, one list: the mapped records, no device; with --locations every place of every word of an index
+ * (print_full_map, :481-510).  A first location outside the location section ends the dump with an error. */
+static int run_dump (const Input *in, int locations)
 {
   char b[64];
   for (uint64_t i = 0; i < in->file.header.n_words; i++) {
+    const uint32_t count = input_count (in, i);
     gt4_word2string (b, input_word (in, i), in->file.header.word_length);
-    fprintf (stdout, "%s\t%u\n", b, input_count (in, i));
+    fprintf (stdout, "%s\t%u\n", b, count);
+    if (!locations) continue;
+    uint64_t at, code;
+    memcpy (&at, in->file.index_kmers + 16 * i + 8, 8);
+    if (at > in->file.index_locations || count > in->file.index_locations - at) {
+      fflush (stdout);
+      fprintf (stderr, "Error: %s is corrupted: the locations of word %llu lie outside its %llu locations\n", in->name, (unsigned long long) i,
+               (unsigned long long) in->file.index_locations);
+      return 1;
+    }
+    for (uint32_t j = 0; j < count; j++) {
+      memcpy (&code, in->file.index_location_words + 8 * (at + j), 8);
+      print_packed_location (&in->file, code);
+    }
+  }
+  return 0;
+}
+
+/* --files (print_files, :439-449): file I/O on the mapping */
+static int run_files (const Input *in)
+{
+  for (uint32_t i = 0; i < in->file.index_n_files; i++) {
+    GT4IndexFile f;
+    if (gt4_indexfile_file (&in->file, i, &f)) return 1;
+    fprintf (stdout, "%u\t%s\t%llu\t%llu\n", i, f.name, (unsigned long long) f.size, (unsigned long long) f.n_sequences);
+  }
+  return 0;
+}
+
+/* --sequences (print_sequences, :451-467): the names come out of the source files, mapped by their stored names
+ * (gt4_index_map_get_sequence_name, src/index-map.c:249-314): at most 1023 bytes, up to the first NUL.  The reference
+ * tries to map a missing source again for every sequence, with a message each time. */
+static int run_sequences (const Input *in)
+{
+  for (uint32_t i = 0; i < in->file.index_n_files; i++) {
+    GT4IndexFile f;
+    if (gt4_indexfile_file (&in->file, i, &f)) return 1;
+    const unsigned char *src = NULL;
+    uint64_t src_size = 0;
+    for (uint64_t j = 0; j < f.n_sequences; j++) {
+      GT4IndexSequence q;
+      char name[1024];
+      unsigned int len = 0;
+      gt4_indexfile_sequence (&f, j, &q);
+      if (!src) {
+        struct stat st;
+        const int fd = open (f.name, O_RDONLY);
+        const int open_errno = errno;
+        if (fd >= 0 && fstat (fd, &st) == 0 && st.st_size > 0) {
+          src = (const unsigned char *) mmap (NULL, (size_t) st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+          if (src == MAP_FAILED) src = NULL;
+          else src_size = (uint64_t) st.st_size;
+        }
+        if (!src) {
+          fflush (stdout);
+          fprintf (stderr, "gt4_mmap (%s): %s\n", fd < 0 ? "open" : "mmap", fd < 0 ? strerror (open_errno) : "the file cannot be mapped");
+          fprintf (stderr, "imap_map_src: could not mmap file %s\n", f.name);
+        }
+        if (fd >= 0) close (fd);
+      }
+      if (src)
+        while (len < 1023 && len < q.name_len && q.name_pos < src_size && len < src_size - q.name_pos && src[q.name_pos + len]) len++;
+      if (len) memcpy (name, src + q.name_pos, len);
+      name[len] = 0;
+      fprintf (stdout, "%u\t%llu\t%s\t%llu\t%llu\t%llu\n", i, (unsigned long long) j, name, (unsigned long long) q.name_pos, (unsigned long long) q.seq_pos,
+               (unsigned long long) q.seq_len);
+    }
+    if (src) munmap ((void *) src, (size_t) src_size);
   }
   return 0;
 }
@@ -833,17 +1042,41 @@ static int run_zipper (const Options *o, unsigned int wlen)
 }
 
 /* -q / -f / -s / -l against one list, in batches; --words-only prints the words and opens no device */
-static int run_lookups (const Options *o, unsigned int wlen, const Input *query_input)
+static int run_lookups (const Options *o, unsigned int wlen, const Input *index, const Input *query_input)
 {
   int v = 0;
   Searcher s = { .o = o, .k = wlen, .prm = { .n_mm = o->nmm, .pm_3 = o->pm3, .canonize = 1 } };
+  const int locations = o->locations && !o->words_only;
+  gt4hip_location_index *lindex = NULL;
+  /* the zipper with locations (search_list_zipper, :702-717): the words of the query list as they are, the QUERY list's
+   * count, REVERSE 0, nothing for a word that is not there */
+  s.zipper = locations && !o->querystring && !o->queryfilename && !o->seqfilename && !o->nmm;
+  if (s.zipper) s.prm.canonize = 0;
   s.words = (uint64_t *) or_oom (malloc ((size_t) QUERY_BATCH * 8), "query batch");
   s.values = (uint32_t *) or_oom (malloc ((size_t) QUERY_BATCH * 4), "query batch");
   s.found = (uint8_t *) or_oom (malloc (QUERY_BATCH), "query batch");
-  s.hit_capacity = o->printall ? QUERY_BATCH : 0;
-  s.hits = o->printall ? (gt4hip_query_hit *) or_oom (malloc ((size_t) s.hit_capacity * sizeof (gt4hip_query_hit)), "query batch") : NULL;
+  s.hit_capacity = o->printall || locations ? QUERY_BATCH : 0;
+  s.hits = s.hit_capacity ? (gt4hip_query_hit *) or_oom (malloc ((size_t) s.hit_capacity * sizeof (gt4hip_query_hit)), "query batch") : NULL;
   GT4HipWordList *l = NULL;
-  if (!o->words_only) {
+  if (locations) {
+    const GT4ListFile *f = &index->file;
+    uint64_t free_bytes = 0, total_bytes = 0;
+    s.reverse = (uint8_t *) or_oom (malloc (QUERY_BATCH), "query batch");
+    s.loc_capacity = QUERY_BATCH;
+    s.locs = (gt4hip_location *) or_oom (malloc ((size_t) s.loc_capacity * sizeof (gt4hip_location)), "query batch");
+    if (s.zipper) s.query_counts = (uint32_t *) or_oom (malloc ((size_t) QUERY_BATCH * 4), "query batch");
+    s.ctx = gt4_hip_default_context ();
+    if (!s.ctx) exit (1);
+    CHK (s.ctx, gt4hip_location_index_create (s.ctx, f->index_kmers, f->header.n_words, f->index_location_words, f->index_locations, wlen, f->index_file_bits,
+                                              f->index_subseq_bits, f->index_pos_bits, &lindex));
+    s.lindex = lindex;
+    CHK (s.ctx, gt4hip_query_index_create (s.ctx, gt4hip_location_index_list (lindex), &s.qindex));
+    CHK (s.ctx, gt4hip_device_memory (s.ctx, &free_bytes, &total_bytes));
+    s.loc_budget = s.hit_budget = free_bytes / 4 / LOOKUP_BYTES;
+    if (s.loc_budget < (1u << 16)) s.loc_budget = s.hit_budget = 1u << 16;
+    const char *e = getenv ("GT4_GLISTQUERY_LOCATION_BUDGET"); /* tests: the halving of a batch */
+    if (e && *e) s.loc_budget = strtoull (e, NULL, 10);
+  } else if (!o->words_only) {
     const gt4hip_list *dev = NULL;
     l = to_device (o->lists[0], &s.ctx, &dev);
     CHK (s.ctx, gt4hip_query_index_create (s.ctx, dev, &s.qindex));
@@ -857,12 +1090,19 @@ static int run_lookups (const Options *o, unsigned int wlen, const Input *query_
   } else if (o->seqfilename) {
     v = search_fasta (&s, o->seqfilename);
   } else if (o->querylistfilename) {
-    for (uint64_t i = 0; i < query_input->file.header.n_words; i++) search_one_word (&s, input_word (query_input, i));
+    for (uint64_t i = 0; i < query_input->file.header.n_words; i++) {
+      if (s.zipper) s.query_counts[s.n] = input_count (query_input, i);
+      search_one_word (&s, input_word (query_input, i));
+    }
   }
   flush_batch (&s); /* what was looked up before a parser error is printed all the same */
   fflush (stdout);
   if (s.qindex) gt4hip_query_index_free (s.qindex);
+  gt4hip_location_index_free (lindex);
   if (l) gt4_hip_word_list_delete (l);
+  free (s.locs);
+  free (s.reverse);
+  free (s.query_counts);
   free (s.words);
   free (s.values);
   free (s.found);
@@ -877,9 +1117,13 @@ int main (int argc, const char *argv[])
   parse_argv (argc, argv, &o);
   validate (&o);
   const unsigned int wlen = open_inputs (&o, maps, &query_input);
+  validate_index_options (&o, maps);
   if (o.command == CMD_STATS) return run_stat (&o, maps);
-  if (o.command != CMD_QUERY) return run_statistics (&o, maps); /* median, distribution or gc: validate refused the rest */
-  if (!o.seqfilename && !o.querylistfilename && !o.queryfilename && !o.querystring) return o.n_lists > 1 ? run_union_dump (&o, wlen) : run_dump (&maps[0]);
+  if (o.command == CMD_FILES) return run_files (&maps[0]);
+  if (o.command == CMD_SEQUENCES) return run_sequences (&maps[0]);
+  if (o.command != CMD_QUERY) return run_statistics (&o, maps); /* median, distribution or gc */
+  if (!o.seqfilename && !o.querylistfilename && !o.queryfilename && !o.querystring)
+    return o.n_lists > 1 ? run_union_dump (&o, wlen) : run_dump (&maps[0], o.locations);
   if (o.querylistfilename && o.n_lists > 1) return run_multi_search (&o, wlen);
   if (o.n_lists > 1) {
     fprintf (stderr, "Error: Query is incompatible with multiple lists/indices\n");
@@ -889,6 +1133,6 @@ int main (int argc, const char *argv[])
     fprintf (stderr, "Error: Number of mismatches (%u) and 3' perfect match (%u) are longer than word length %u\n", o.nmm, o.pm3, wlen);
     return 1;
   }
-  if (!o.querystring && !o.queryfilename && !o.seqfilename && !o.nmm && !o.words_only) return run_zipper (&o, wlen);
-  return run_lookups (&o, wlen, &query_input);
+  if (!o.querystring && !o.queryfilename && !o.seqfilename && !o.nmm && !o.words_only && !o.locations) return run_zipper (&o, wlen);
+  return run_lookups (&o, wlen, &maps[0], &query_input);
 }

@@ -119,6 +119,54 @@ int gt4_listfile_open (const char *path, unsigned int major_version, GT4ListFile
   return GT4_LISTFILE_OK;
 }
 
+/* Walks the file block at `at` of a mapping of `size` bytes up to file `want` (~0: to the end), never reading a byte
+ * that was not first shown to lie in the file.  0 and *n_files (and *file for `want`), or 1 where a step leaves the file. */
+static int file_block_walk (const unsigned char *map, uint64_t size, uint64_t at, uint32_t want, uint32_t *n_files, GT4IndexFile *file)
+{
+  if (size - at < 16) return 1;
+  memcpy (n_files, map + at + 12, 4);
+  at += 16;
+  for (uint32_t i = 0; i < *n_files; i++) {
+    uint64_t fsize, n_seqs;
+    uint16_t len;
+    if (size - at < 18) return 1;
+    memcpy (&fsize, map + at, 8);
+    memcpy (&n_seqs, map + at + 8, 8);
+    memcpy (&len, map + at + 16, 2);
+    at += 18;
+    if (len < 1 || size - at < len || map[at + len - 1] != 0) return 1;
+    at += len;
+    if (n_seqs > (size - at) / 28) return 1;
+    if (i == want) {
+      file->size = fsize;
+      file->n_sequences = n_seqs;
+      file->name = (const char *) map + at - len;
+      file->sequences = map + at;
+      return 0;
+    }
+    at += n_seqs * 28;
+  }
+  return want != ~0u;
+}
+
+int gt4_indexfile_file (const GT4ListFile *lf, uint32_t i, GT4IndexFile *out)
+{
+  uint32_t n = 0;
+  if (!lf || !out || !lf->index_files || i >= lf->index_n_files) return GT4_LISTFILE_ESIZE;
+  return file_block_walk (lf->file_map, lf->file_size, (uint64_t) (lf->index_files - lf->file_map), i, &n, out) ? GT4_LISTFILE_ESIZE : GT4_LISTFILE_OK;
+}
+
+int gt4_indexfile_sequence (const GT4IndexFile *file, uint64_t j, GT4IndexSequence *out)
+{
+  if (!file || !out || j >= file->n_sequences) return GT4_LISTFILE_ESIZE;
+  const unsigned char *s = file->sequences + j * 28;
+  memcpy (&out->name_pos, s, 8);
+  memcpy (&out->name_len, s + 8, 4);
+  memcpy (&out->seq_pos, s + 12, 8);
+  memcpy (&out->seq_len, s + 20, 8);
+  return GT4_LISTFILE_OK;
+}
+
 int gt4_indexfile_open (const char *path, unsigned int major_version, GT4ListFile *out)
 {
   memset (out, 0, sizeof *out);
@@ -159,9 +207,34 @@ int gt4_indexfile_open (const char *path, unsigned int major_version, GT4ListFil
     munmap ((void *) map, size);
     return GT4_LISTFILE_ESIZE;
   }
+  if (h.locations_start > size || h.num_locations > (size - h.locations_start) / 8) {
+    fprintf (stderr, "gt4_index_map_new: file size too small (%llu) for %llu locations at %llu\n", (unsigned long long) size,
+             (unsigned long long) h.num_locations, (unsigned long long) h.locations_start);
+    munmap ((void *) map, size);
+    return GT4_LISTFILE_ESIZE;
+  }
+  if (h.n_file_bits > 64 || h.n_subseq_bits > 64 || h.n_pos_bits > 64 || h.n_file_bits + h.n_subseq_bits + h.n_pos_bits + 1 > 64) {
+    fprintf (stderr, "gt4_index_map_new: a location of %u + %u + %u + 1 bits does not fit 64\n", h.n_file_bits, h.n_subseq_bits, h.n_pos_bits);
+    munmap ((void *) map, size);
+    return GT4_LISTFILE_ESIZE;
+  }
+  /* an index without words ends behind its header (files_start = size): it has no file block */
+  uint32_t n_files = 0;
+  if (h.files_start > size || (h.files_start < size && file_block_walk (map, size, h.files_start, ~0u, &n_files, NULL))) {
+    fprintf (stderr, "gt4_index_map_new: file size too small (%llu) for the file block at %llu\n", (unsigned long long) size,
+             (unsigned long long) h.files_start);
+    munmap ((void *) map, size);
+    return GT4_LISTFILE_ESIZE;
+  }
   out->filename = strdup (path);
   out->file_map = map;
   out->file_size = size;
+  out->index_location_words = map + h.locations_start;
+  out->index_file_bits = h.n_file_bits;
+  out->index_subseq_bits = h.n_subseq_bits;
+  out->index_pos_bits = h.n_pos_bits;
+  out->index_n_files = n_files;
+  out->index_files = h.files_start < size ? map + h.files_start : NULL;
   gt4_list_header_init (&out->header, h.word_length);
   out->header.n_words = h.num_words;
   out->header.total_count = h.num_locations;

@@ -175,6 +175,8 @@ void gt4hip_io_destroy (gt4hip_context *ctx);
 /* bytes of text, and codes, per tile of gt4hip_maker.hip's kernels (counters "maker_text_tile", "maker_code_tile") */
 #define GT4HIP_MAKER_TILE 4096u
 int gt4hip_io_download (gt4hip_context *ctx, const void *dev, void *host, size_t bytes);
+/* host memory (a file mapping, say) -> device memory, waited for: large extents in pieces through the staging threads */
+int gt4hip_io_upload (gt4hip_context *ctx, const void *host, void *dev, size_t bytes);
 
 #define HIPCHK(ctx, call)                                                                               \
   do {                                                                                                  \

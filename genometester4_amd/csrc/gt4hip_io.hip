@@ -520,3 +520,20 @@ int gt4hip_io_download (gt4hip_context *ctx, const void *dev, void *host, size_t
   j.bytes = bytes;
   return io_run (ctx, j, "gt4hip_list_download");
 }
+
+int gt4hip_io_upload (gt4hip_context *ctx, const void *host, void *dev, size_t bytes)
+{
+  if (!bytes) return GT4HIP_OK;
+  if (bytes < IO_THRESHOLD) {
+    HIPCHK (ctx, hipMemcpyAsync (dev, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK (ctx, hipStreamSynchronize (ctx->stream));
+    return GT4HIP_OK;
+  }
+  Job j;
+  memset (&j, 0, sizeof j);
+  j.kind = JOB_MEM_TO_DEV;
+  j.src_mem = (const char *) host;
+  j.dev = (char *) dev;
+  j.bytes = bytes;
+  return io_run (ctx, j, "gt4hip_io_upload");
+}

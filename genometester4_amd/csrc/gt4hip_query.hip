@@ -21,6 +21,11 @@
  * count their hits, one scan turns the counts into offsets, and a second pass over the same tiles repeats the probes
  * and writes every hit to its place.  Nothing of the size of the variant space is ever stored.
  *
+ * --locations (gt4hip_location_index, gt4hip_query_lookup_locations) returns the hits with every place they occur in a
+ * resident GT4I index: the --all passes also count and scan the hits' locations (64-bit), the fill pass leaves per hit
+ * where its locations start in the output and in the index, and one segmented gather, dealt by output element, copies
+ * and decodes them (k_gather_locations).
+ *
  * The statistics are one streaming pass each over the 12-byte records: four records per thread as three 16-byte
  * loads where the list is 16-byte aligned, a wavefront reduction, one atomic per wavefront.
  */
@@ -186,6 +191,239 @@ __global__ __launch_bounds__ (MM_THREADS) void k_query_all (Query Q, u64 n_tiles
   }
 }
 
+/* ------------------------------------------------------------------ --locations: the hits with where they occur */
+
+/* One pass over the k-mer section of a GT4I index, entries [i0, i0 + n) of n_all (the piece holds entry i0 + n too
+ * unless that is the end): the packed record (count = distance to the next first location, in 32 bits as
+ * imap_get_count, src/index-map.c:129-139), the first location on its own, and the check that makes every later read
+ * of the location array safe: first locations never descend and never pass num_locations. */
+__global__ __launch_bounds__ (MM_THREADS) void k_index_split (const u64 *__restrict__ kmers, u64 i0, u64 n, u64 n_all, u64 num_locations, u32 *__restrict__ rec,
+                                                              u64 *__restrict__ first, u32 *bad)
+{
+  bool wrong = false;
+  for (u64 i = (u64) blockIdx.x * MM_THREADS + threadIdx.x; i < n; i += (u64) gridDim.x * MM_THREADS) {
+    const u64 word = kmers[2 * i], loc = kmers[2 * i + 1];
+    const u64 next = i0 + i + 1 < n_all ? kmers[2 * i + 3] : num_locations;
+    wrong |= loc > next || next > num_locations;
+    rec[3 * (i0 + i)] = (u32) word;
+    rec[3 * (i0 + i) + 1] = (u32) (word >> 32);
+    rec[3 * (i0 + i) + 2] = (u32) (next - loc);
+    first[i0 + i] = loc;
+  }
+  if (__builtin_amdgcn_ballot_w64 (wrong) && (threadIdx.x & (WAVE - 1)) == 0) atomicOr (bad, 1u);
+}
+
+/* k_query_all with the locations of every hit counted beside it.  FILL == false: tile_cnt[t] = hits of the tile,
+ * tile_loc[t] = their locations.  FILL == true: the hits in item order from hits[tile_off[t]], and for hit h the place
+ * of its first location in the output (seg_off[h], from tile_loc_off[t] on) and in the index (seg_src[h]). */
+template <bool FILL>
+__global__ __launch_bounds__ (MM_THREADS) void k_query_loc (Query Q, const u64 *__restrict__ first, u64 n_tiles, u32 *tile_cnt, u64 *tile_loc, const u64 *tile_off,
+                                                            const u64 *tile_loc_off, gt4hip_query_hit *hits, u64 *seg_off, u64 *seg_src)
+{
+  __shared__ u32 part[MM_THREADS / WAVE];
+  __shared__ u64 lpart[MM_THREADS / WAVE];
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  for (u64 t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    u64 pos = FILL ? tile_off[t] : 0, lpos = FILL ? tile_loc_off[t] : 0;
+    u32 mine = 0;
+    u64 lmine = 0;
+    for (int rd = 0; rd < MM_ROUNDS; rd++) {
+      const u64 g = t * MM_TILE + (u64) rd * MM_THREADS + threadIdx.x;
+      u64 q = 0, r = 0, cv = 0, j = ~0ull;
+      if (g < Q.total) {
+        q = g / Q.n_var;
+        r = g - q * Q.n_var;
+        cv = query_variant<true> (Q, canonical (Q.words[q], Q.k, Q.canonize), r);
+        j = find (Q.ix, cv);
+      }
+      const bool hit = j != ~0ull;
+      const u32 cnt = hit ? Q.ix.rec[3 * j + 2] : 0u;
+      if (!FILL) {
+        mine += hit;
+        lmine += cnt;
+      } else {
+        const u64 m = __builtin_amdgcn_ballot_w64 (hit);
+        const u64 incl = wave_inclusive_scan ((u64) cnt, lane);
+        if (lane == 0) part[wv] = (u32) __popcll (m);
+        if (lane == WAVE - 1) lpart[wv] = incl;
+        __syncthreads ();
+        u32 before = 0, round = 0;
+        u64 lbefore = 0, lround = 0;
+        for (int x = 0; x < MM_THREADS / WAVE; x++) {
+          before += x < wv ? part[x] : 0;
+          round += part[x];
+          lbefore += x < wv ? lpart[x] : 0;
+          lround += lpart[x];
+        }
+        if (hit) {
+          const u64 h = pos + before + (u32) __popcll (m & ((1ull << lane) - 1));
+          gt4hip_query_hit o;
+          o.query = q;
+          o.rank = r;
+          o.word = cv;
+          o.count = cnt;
+          o.reserved = 0;
+          hits[h] = o;
+          seg_off[h] = lpos + lbefore + incl - cnt;
+          seg_src[h] = first[j];
+        }
+        pos += round;
+        lpos += lround;
+        __syncthreads ();
+      }
+    }
+    if (!FILL) {
+      mine = dpp_wave_sum_u32 (mine);
+      lmine = wave_sum (lmine);
+      if (lane == 0) {
+        part[wv] = mine;
+        lpart[wv] = lmine;
+      }
+      __syncthreads ();
+      if (threadIdx.x == 0) {
+        u32 s = 0;
+        u64 ls = 0;
+        for (int x = 0; x < MM_THREADS / WAVE; x++) {
+          s += part[x];
+          ls += lpart[x];
+        }
+        tile_cnt[t] = s;
+        tile_loc[t] = ls;
+      }
+      __syncthreads ();
+    }
+  }
+}
+
+/* k_tile_scan for 64-bit counts: a tile's locations do not fit 32 bits */
+__global__ __launch_bounds__ (1024) void k_tile_scan64 (const u64 *tile_cnt, u64 n_tiles, u64 *tile_off, unsigned long long *total)
+{
+  __shared__ u64 wsum[1024 / WAVE];
+  __shared__ u64 carry;
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  if (threadIdx.x == 0) carry = 0;
+  __syncthreads ();
+  for (u64 base = 0; base < n_tiles; base += 1024) {
+    const u64 i = base + threadIdx.x;
+    const u64 v = i < n_tiles ? tile_cnt[i] : 0;
+    const u64 incl = wave_inclusive_scan (v, lane);
+    if (lane == WAVE - 1) wsum[wv] = incl;
+    __syncthreads ();
+    u64 before = carry;
+    for (int w = 0; w < wv; w++) before += wsum[w];
+    if (i < n_tiles) tile_off[i] = before + incl - v;
+    __syncthreads ();
+    if (threadIdx.x == 1023) carry = before + incl;
+    __syncthreads ();
+  }
+  if (threadIdx.x == 0) *total = carry;
+}
+
+/* how a packed location comes apart (index_map_get_location, src/index-map.c:197-208) */
+struct LocationBits {
+  u32 file_shift, seq_shift; /* n_subseq_bits + n_pos_bits + 1 (0 with file_mask 0 where that is 64), n_pos_bits + 1 */
+  u64 file_mask, seq_mask, pos_mask;
+};
+
+constexpr int GATHER_ROUNDS = 8;
+constexpr u32 GATHER_TILE = MM_THREADS * GATHER_ROUNDS; /* output locations per tile */
+constexpr u32 GATHER_LDS_SEGS = GATHER_TILE + 1;        /* segments of a tile kept in LDS: every tile without zero-length ones fits */
+
+/* The first index i of the ascending a[0..n) with a[i] > o (n when there is none), by a whole wavefront: every step
+ * probes 64 evenly spaced entries of what is left and keeps the stretch between the last probe <= o and the first > o. */
+__device__ __forceinline__ u64 wave_upper_bound (const u64 *__restrict__ a, u64 n, u64 o, int lane)
+{
+  u64 lo = 0, hi = n; /* the answer lies in [lo, hi] */
+  while (lo < hi) {
+    const u64 step = (hi - lo) / WAVE + 1;
+    const u64 i = lo + (u64) lane * step;
+    const int c = __popcll (__builtin_amdgcn_ballot_w64 (i < hi && a[i] <= o)); /* a prefix of the lanes */
+    if (c == 0) {
+      hi = lo;
+    } else {
+      const u64 up = lo + (u64) c * step;
+      lo += (u64) (c - 1) * step + 1;
+      hi = up < hi ? up : hi;
+    }
+  }
+  return lo;
+}
+
+/* The segmented gather.  Segment h (one hit) is seg_off[h + 1] - seg_off[h] packed locations from locs[seg_src[h]] on,
+ * and goes to out[seg_off[h]...]; seg_off ascends, seg_off[n_segs] = n_out, equal neighbours are empty segments.  The
+ * work is dealt by OUTPUT element: a workgroup takes GATHER_TILE consecutive outputs and finds the segments that cover
+ * them with two searches of seg_off (the last segment that starts at or before the tile's first and its last output:
+ * empty segments sort in front of the one that holds an output and are never chosen); a search is a wavefront's, 64
+ * probes a step, so 10^7 segments take four dependent loads where a binary search takes 24.  A tile inside one segment (a
+ * k-mer with 10^5 locations) copies straight; otherwise the tile's segment starts go to LDS, relative to the tile, and
+ * every output finds its own by a search there (a run of more than GATHER_LDS_SEGS segments, which only empty ones can
+ * make, is searched in global memory).  Consecutive lanes read consecutive 8-byte words of a segment and write
+ * consecutive 16-byte records. */
+__global__ __launch_bounds__ (MM_THREADS) void k_gather_locations (const u64 *__restrict__ seg_off, const u64 *__restrict__ seg_src, u64 n_segs, u64 n_out,
+                                                                   const u64 *__restrict__ locs, LocationBits B, gt4hip_location *__restrict__ out)
+{
+  __shared__ u32 rel[GATHER_LDS_SEGS];
+  __shared__ u64 delta[GATHER_LDS_SEGS];
+  __shared__ u64 bound[2];
+  const u64 n_tiles = (n_out + GATHER_TILE - 1) / GATHER_TILE;
+  for (u64 t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    const u64 o0 = t * GATHER_TILE;
+    const u64 o1 = o0 + GATHER_TILE < n_out ? o0 + GATHER_TILE : n_out; /* one past the tile's last output */
+    /* first index with seg_off > o0 (wavefront 0) and with seg_off > o1 - 1 (wavefront 1), side by side */
+    if (threadIdx.x < 2 * WAVE) {
+      const u64 b = wave_upper_bound (seg_off, n_segs, threadIdx.x < WAVE ? o0 : o1 - 1, threadIdx.x & (WAVE - 1));
+      if ((threadIdx.x & (WAVE - 1)) == 0) bound[threadIdx.x / WAVE] = b;
+    }
+    __syncthreads ();
+    const u64 hA = bound[0] - 1, hB = bound[1] - 1; /* seg_off[0] = 0 <= o0: both bounds are >= 1 */
+    const u64 m = hB - hA + 1;
+    const bool one = m == 1, lds = m <= GATHER_LDS_SEGS;
+    const u64 d_one = seg_src[hA] - seg_off[hA];
+    if (!one && lds) {
+      for (u32 x = threadIdx.x; x < (u32) m; x += MM_THREADS) {
+        const u64 so = seg_off[hA + x];
+        rel[x] = so > o0 ? (u32) (so - o0) : 0u;
+        delta[x] = seg_src[hA + x] - so;
+      }
+    }
+    __syncthreads ();
+#pragma unroll
+    for (int rd = 0; rd < GATHER_ROUNDS; rd++) {
+      const u32 e = (u32) rd * MM_THREADS + threadIdx.x;
+      const u64 o = o0 + e;
+      if (o < o1) {
+        u64 d = d_one;
+        if (!one && lds) {
+          u32 lo = 0, hi = (u32) m; /* first x with rel[x] > e */
+          while (lo < hi) {
+            const u32 mid = (lo + hi) >> 1;
+            if (rel[mid] <= e) lo = mid + 1;
+            else hi = mid;
+          }
+          d = delta[lo - 1];
+        } else if (!one) {
+          u64 lo = hA, hi = hB + 1;
+          while (lo < hi) {
+            const u64 mid = (lo + hi) >> 1;
+            if (seg_off[mid] <= o) lo = mid + 1;
+            else hi = mid;
+          }
+          d = seg_src[lo - 1] - seg_off[lo - 1];
+        }
+        const u64 code = locs[d + o];
+        const u64 pos_dir = (((code >> 1) & B.pos_mask) << 1) | (code & 1);
+        u32x4 r; /* a gt4hip_location, in one 16-byte store */
+        r.x = (u32) pos_dir;
+        r.y = (u32) (pos_dir >> 32);
+        r.z = (u32) ((code >> B.file_shift) & B.file_mask);
+        r.w = (u32) ((code >> B.seq_shift) & B.seq_mask);
+        ((u32x4 *) out)[o] = r;
+      }
+    }
+    __syncthreads ();
+  }
+}
+
 /* ------------------------------------------------------------------ statistics: one pass over the records */
 
 /* f (key, count) for every record, each once: four records per thread as three 16-byte loads where the list allows it */
@@ -287,6 +525,7 @@ struct gt4hip_query_index {
   Index ix;
   void *owner;
   double last_ms;
+  double gather_ms; /* the gather kernel of the last gt4hip_query_lookup_locations */
 };
 
 namespace {
@@ -358,7 +597,7 @@ extern "C" int gt4hip_query_index_create (gt4hip_context *ctx, const gt4hip_list
   gt4hip_query_index *qi = new gt4hip_query_index ();
   qi->ctx = ctx;
   qi->list = list;
-  qi->last_ms = 0;
+  qi->last_ms = qi->gather_ms = 0;
   size_index (list, &qi->ix);
   void *off = NULL;
   int rc = gt4hip_block_alloc (ctx, (qi->ix.nb + 1) * 8, &off, &qi->owner);
@@ -594,3 +833,163 @@ extern "C" int gt4hip_list_gc (gt4hip_context *ctx, const gt4hip_list *list, uin
   *weighted_gc_bases = ctx->scratch_host[0];
   return GT4HIP_OK;
 }
+
+/* ------------------------------------------------------------------ --locations */
+
+struct gt4hip_location_index {
+  gt4hip_context *ctx;
+  gt4hip_list *list;     /* the k-mer section as packed records */
+  u64 *first;            /* n_words first locations */
+  u64 *locs;             /* n_locations packed locations */
+  void *first_owner, *locs_owner;
+  u64 n_locations;
+  LocationBits bits;
+};
+
+static_assert (sizeof (gt4hip_location) == 16, "a location is one 16-byte store");
+
+extern "C" void gt4hip_location_index_free (gt4hip_location_index *li)
+{
+  if (!li) return;
+  gt4hip_block_free (li->first_owner);
+  gt4hip_block_free (li->locs_owner);
+  gt4hip_list_free (li->list);
+  delete li;
+}
+
+extern "C" const gt4hip_list *gt4hip_location_index_list (const gt4hip_location_index *li) { return li ? li->list : NULL; }
+extern "C" uint64_t gt4hip_location_index_n_locations (const gt4hip_location_index *li) { return li ? li->n_locations : 0; }
+
+extern "C" int gt4hip_location_index_create (gt4hip_context *ctx, const void *host_kmers, uint64_t n_words, const void *host_locations, uint64_t num_locations,
+                                             uint32_t word_length, uint32_t n_file_bits, uint32_t n_subseq_bits, uint32_t n_pos_bits, gt4hip_location_index **out)
+{
+  if (!ctx || !out || (n_words && !host_kmers) || (num_locations && !host_locations)) return GT4HIP_EINVAL;
+  *out = NULL;
+  if (word_length < 1 || word_length > 32) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_location_index_create: word length %u", word_length);
+  if (n_file_bits > 64 || n_subseq_bits > 64 || n_pos_bits > 64 || n_file_bits + n_subseq_bits + n_pos_bits + 1 > 64)
+    return gt4hip_fail (ctx, GT4HIP_EFORMAT, "gt4hip_location_index_create: a location of %u + %u + %u + 1 bits does not fit 64", n_file_bits, n_subseq_bits, n_pos_bits);
+  if (n_words > (1ull << 59) || num_locations > (1ull << 60)) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_location_index_create: %llu k-mers, %llu locations", (unsigned long long) n_words, (unsigned long long) num_locations);
+  HIPCHK (ctx, hipSetDevice (ctx->device));
+  gt4hip_location_index *li = new (std::nothrow) gt4hip_location_index ();
+  if (!li) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "host allocation failed");
+  li->ctx = ctx;
+  li->n_locations = num_locations;
+  const auto mask = [] (u32 bits) { return bits >= 64 ? ~0ull : (1ull << bits) - 1; };
+  const u32 fs = n_subseq_bits + n_pos_bits + 1;
+  li->bits.file_shift = fs < 64 ? fs : 0;
+  li->bits.file_mask = fs < 64 ? mask (n_file_bits) : 0;
+  li->bits.seq_shift = n_pos_bits + 1 < 64 ? n_pos_bits + 1 : 0;
+  li->bits.seq_mask = n_pos_bits + 1 < 64 ? mask (n_subseq_bits) : 0;
+  li->bits.pos_mask = mask (n_pos_bits);
+  /* the k-mer section goes through a device buffer of PIECE entries (and the one behind them: the end of the last count) */
+  const u64 PIECE = 1ull << 22;
+  Blocks blk;
+  u64 *tmp = NULL;
+  u32 *bad = (u32 *) ctx->scratch;
+  int rc = gt4hip_list_new (ctx, n_words, word_length, &li->list);
+  if (!rc) rc = gt4hip_block_alloc (ctx, n_words ? n_words * 8 : 16, (void **) &li->first, &li->first_owner);
+  if (!rc) rc = gt4hip_block_alloc (ctx, num_locations ? num_locations * 8 : 16, (void **) &li->locs, &li->locs_owner);
+  if (!rc) rc = blk.get (ctx, ((n_words < PIECE ? n_words : PIECE) + 1) * 16, (void **) &tmp);
+  if (!rc && hipMemsetAsync (bad, 0, 4, ctx->stream) != hipSuccess) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_location_index_create: hipMemsetAsync failed");
+  for (u64 i0 = 0; !rc && i0 < n_words; i0 += PIECE) {
+    const u64 n = n_words - i0 < PIECE ? n_words - i0 : PIECE, with_next = i0 + n < n_words ? n + 1 : n;
+    rc = gt4hip_io_upload (ctx, (const char *) host_kmers + i0 * 16, tmp, with_next * 16);
+    if (rc) break;
+    hipLaunchKernelGGL (k_index_split, dim3 (grid_for (ctx, n, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, (const u64 *) tmp, i0, n, n_words, num_locations,
+                        (u32 *) li->list->dev, li->first, bad);
+    if (hipGetLastError () != hipSuccess || hipStreamSynchronize (ctx->stream) != hipSuccess) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_location_index_create: decoding the k-mer section failed");
+  }
+  if (!rc) rc = gt4hip_read_back (ctx, ctx->scratch_host, bad, 4, "gt4hip_location_index_create: reading the check back failed");
+  if (!rc && *(const u32 *) ctx->scratch_host)
+    rc = gt4hip_fail (ctx, GT4HIP_EFORMAT, "gt4hip_location_index_create: the first locations of the k-mers descend or pass the %llu locations of the index",
+                      (unsigned long long) num_locations);
+  if (!rc && num_locations) rc = gt4hip_io_upload (ctx, host_locations, li->locs, num_locations * 8);
+  if (rc) {
+    gt4hip_location_index_free (li);
+    return rc;
+  }
+  *out = li;
+  return GT4HIP_OK;
+}
+
+extern "C" int gt4hip_query_lookup_locations (gt4hip_context *ctx, gt4hip_query_index *qi, const gt4hip_location_index *li, const uint64_t *words, uint64_t n,
+                                              const gt4hip_query_params *prm, gt4hip_query_hit *hits, uint64_t hit_capacity, uint64_t *n_hits,
+                                              gt4hip_location *locations, uint64_t loc_capacity, uint64_t *n_locations)
+{
+  if (!ctx || !qi || !li || !prm || !n_hits || !n_locations || (n && !words) || (hit_capacity && !hits) || (loc_capacity && !locations)) return GT4HIP_EINVAL;
+  if (qi->list != li->list) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_query_lookup_locations: the query index was not made of this location index's list");
+  int rc = check_params (ctx, "gt4hip_query_lookup_locations", qi, prm);
+  if (rc) return rc;
+  *n_hits = *n_locations = 0;
+  qi->last_ms = qi->gather_ms = 0;
+  if (!n) return GT4HIP_OK;
+  HIPCHK (ctx, hipSetDevice (ctx->device));
+  Blocks blk;
+  u64 *d_words = NULL;
+  if ((rc = blk.get (ctx, n * 8, (void **) &d_words))) return rc;
+  Query Q;
+  if ((rc = fill_query (ctx, "gt4hip_query_lookup_locations", qi, prm, d_words, n, &Q))) return rc;
+  const u64 tiles = Q.total / MM_TILE + (Q.total % MM_TILE != 0);
+  if (tiles > (1ull << 31))
+    return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_query_lookup_locations: %llu queries of %llu variants each are too many for one call: split the batch",
+                        (unsigned long long) n, (unsigned long long) Q.n_var);
+  u32 *tile_cnt = NULL;
+  u64 *tile_loc = NULL, *tile_off = NULL, *tile_loc_off = NULL;
+  if ((rc = blk.get (ctx, tiles * 4, (void **) &tile_cnt)) || (rc = blk.get (ctx, tiles * 8, (void **) &tile_loc)) || (rc = blk.get (ctx, tiles * 8, (void **) &tile_off)) ||
+      (rc = blk.get (ctx, tiles * 8, (void **) &tile_loc_off)))
+    return rc;
+  Timer tm, tg;
+  HIPCHK (ctx, hipEventCreate (&tm.e0));
+  HIPCHK (ctx, hipEventCreate (&tm.e1));
+  HIPCHK (ctx, hipEventCreate (&tg.e0));
+  HIPCHK (ctx, hipMemcpyAsync (d_words, words, n * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK (ctx, hipEventRecord (tm.e0, ctx->stream));
+  const int grid = grid_for (ctx, tiles, 1);
+  hipLaunchKernelGGL (k_query_loc<false>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, Q, (const u64 *) li->first, tiles, tile_cnt, tile_loc, (const u64 *) NULL,
+                      (const u64 *) NULL, (gt4hip_query_hit *) NULL, (u64 *) NULL, (u64 *) NULL);
+  hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, ctx->stream, tile_cnt, tiles, tile_off, ctx->scratch);
+  hipLaunchKernelGGL (k_tile_scan64, dim3 (1), dim3 (1024), 0, ctx->stream, (const u64 *) tile_loc, tiles, tile_loc_off, ctx->scratch + 1);
+  HIPCHK (ctx, hipGetLastError ());
+  HIPCHK (ctx, hipMemcpyAsync (ctx->scratch_host, ctx->scratch, 16, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK (ctx, hipStreamSynchronize (ctx->stream));
+  const u64 total_hits = ctx->scratch_host[0], total_locs = ctx->scratch_host[1];
+  *n_hits = total_hits;
+  *n_locations = total_locs;
+  if (total_hits && total_hits <= hit_capacity && total_locs <= loc_capacity) {
+    if (total_locs > (1ull << 59)) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_query_lookup_locations: %llu locations", (unsigned long long) total_locs);
+    gt4hip_query_hit *d_hits = NULL;
+    gt4hip_location *d_locs = NULL;
+    u64 *seg_off = NULL, *seg_src = NULL;
+    if ((rc = blk.get (ctx, total_hits * sizeof (gt4hip_query_hit), (void **) &d_hits)) || (rc = blk.get (ctx, total_hits * 8, (void **) &seg_off)) ||
+        (rc = blk.get (ctx, total_hits * 8, (void **) &seg_src)) || (rc = blk.get (ctx, total_locs * sizeof (gt4hip_location), (void **) &d_locs)))
+      return rc;
+    hipLaunchKernelGGL (k_query_loc<true>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, Q, (const u64 *) li->first, tiles, tile_cnt, tile_loc, (const u64 *) tile_off,
+                        (const u64 *) tile_loc_off, d_hits, seg_off, seg_src);
+    HIPCHK (ctx, hipGetLastError ());
+    HIPCHK (ctx, hipEventRecord (tg.e0, ctx->stream));
+    if (total_locs) {
+      const u64 g_tiles = (total_locs + GATHER_TILE - 1) / GATHER_TILE;
+      hipLaunchKernelGGL (k_gather_locations, dim3 (grid_for (ctx, g_tiles, 1)), dim3 (MM_THREADS), 0, ctx->stream, (const u64 *) seg_off, (const u64 *) seg_src, total_hits,
+                          total_locs, (const u64 *) li->locs, li->bits, d_locs);
+      HIPCHK (ctx, hipGetLastError ());
+    }
+    HIPCHK (ctx, hipEventRecord (tm.e1, ctx->stream));
+    HIPCHK (ctx, hipMemcpyAsync (hits, d_hits, total_hits * sizeof (gt4hip_query_hit), hipMemcpyDeviceToHost, ctx->stream));
+    if (total_locs * sizeof (gt4hip_location) < ((size_t) 32 << 20)) {
+      HIPCHK (ctx, hipMemcpyAsync (locations, d_locs, total_locs * sizeof (gt4hip_location), hipMemcpyDeviceToHost, ctx->stream));
+    } else { /* in pieces through the staging threads, as large lists are */
+      HIPCHK (ctx, hipStreamSynchronize (ctx->stream));
+      if ((rc = gt4hip_io_download (ctx, d_locs, locations, total_locs * sizeof (gt4hip_location)))) return rc;
+    }
+  } else {
+    HIPCHK (ctx, hipEventRecord (tg.e0, ctx->stream));
+    HIPCHK (ctx, hipEventRecord (tm.e1, ctx->stream));
+  }
+  HIPCHK (ctx, hipStreamSynchronize (ctx->stream));
+  float ms = 0;
+  if (hipEventElapsedTime (&ms, tm.e0, tm.e1) == hipSuccess) qi->last_ms = ms;
+  if (hipEventElapsedTime (&ms, tg.e0, tm.e1) == hipSuccess) qi->gather_ms = ms;
+  return GT4HIP_OK;
+}
+
+extern "C" double gt4hip_query_index_gather_ms (const gt4hip_query_index *qi) { return qi ? qi->gather_ms : 0.0; }

@@ -53,6 +53,15 @@ typedef struct {
    * index_locations (imap_get_count, src/index-map.c:129-139).  NULL / 0 for list files. */
   const unsigned char *index_kmers;
   uint64_t index_locations;
+  /* ... and what --locations, --files and --sequences read: the location section (index_locations packed 64-bit words:
+   * file << (n_subseq_bits + n_pos_bits + 1) | sequence << (n_pos_bits + 1) | position << 1 | strand) and the file block
+   * (16 bytes "F4TG", two versions, the number of files; then per file size u64, n_sequences u64, name length u16, the
+   * name with its NUL, and 28 bytes per sequence).  index_files is NULL and index_n_files 0 for an index without words,
+   * which has no file block.  gt4_indexfile_open has walked the block once: the two walkers below stay inside the file. */
+  const unsigned char *index_location_words;
+  uint32_t index_file_bits, index_subseq_bits, index_pos_bits;
+  uint32_t index_n_files;
+  const unsigned char *index_files;
 } GT4ListFile;
 
 /* struct _GT4IndexHeader, src/index-map.h:69-83: 72 bytes, little-endian, no padding */
@@ -79,7 +88,8 @@ enum {
   GT4_LISTFILE_EVERSION = 3, /* incompatible major version (src/word-map.c:185)     */
   GT4_LISTFILE_ESIZE = 4     /* file size too small (src/word-map.c:211-215) -- and headers that pass that test while
                               * the records cannot lie in the file at stride 12: list_start > size or
-                              * n_words > (size - list_start) / 12, checked by division (the reference's product wraps) */
+                              * n_words > (size - list_start) / 12, checked by division (the reference's product wraps);
+                              * for an index: any section, or any step through the file block, that leaves the file */
 };
 
 /* Reads the 4-byte tag of a file (glistcompare's format sniff, src/glistcompare.c:256-263).
@@ -95,8 +105,26 @@ void gt4_listfile_close (GT4ListFile *lf);
  * header.word_length / n_words (= num_words) / total_count (= num_locations), index_kmers and
  * index_locations; records stays NULL.  The reference checks tag and major version only
  * ("gt4_index_map_new: ..." diagnostics, reproduced); a k-mer table that does not fit in the file
- * is rejected here with GT4_LISTFILE_ESIZE instead of being read out of bounds. */
+ * is rejected here with GT4_LISTFILE_ESIZE instead of being read out of bounds.  So is everything else a reader of the
+ * index follows: locations_start > size or num_locations > (size - locations_start) / 8 (by division), bit sizes with
+ * n_file_bits + n_subseq_bits + n_pos_bits + 1 > 64, and a file block that leaves the file anywhere: its 16-byte head,
+ * a file's 16 bytes and 2-byte name length, a name (which must end in its NUL), n_sequences x 28 bytes. */
 int gt4_indexfile_open (const char *path, unsigned int major_version, GT4ListFile *out);
+
+/* File i (< index_n_files) of a mapped index (index_map_get_file, src/index-map.c:210-230) and sequence j
+ * (< n_sequences) of it (index_map_get_sequence, :232-247).  GT4_LISTFILE_OK, or GT4_LISTFILE_ESIZE for an i or j that
+ * is not there. */
+typedef struct {
+  uint64_t size, n_sequences;
+  const char *name;                /* NUL-terminated, inside the mapping */
+  const unsigned char *sequences;  /* n_sequences x 28 bytes */
+} GT4IndexFile;
+typedef struct {
+  uint64_t name_pos, seq_pos, seq_len;
+  uint32_t name_len;
+} GT4IndexSequence;
+int gt4_indexfile_file (const GT4ListFile *lf, uint32_t i, GT4IndexFile *out);
+int gt4_indexfile_sequence (const GT4IndexFile *file, uint64_t j, GT4IndexSequence *out);
 
 /* Incremental writer: placeholder header, records, back-patched header (the reference's
  * fopen/fwrite/fseek sequence, src/glistcompare.c:816-834, :907-915, or write/pwrite, :538-595). */

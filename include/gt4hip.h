@@ -44,7 +44,8 @@ enum {
   GT4HIP_ECALLBACK = 8,   /* (internal) walk stopped by the caller's callback */
   GT4HIP_EIO = 9,         /* reading or writing a file descriptor failed       */
   GT4HIP_ECOMM = 10,      /* RCCL could not be loaded / a collective failed    */
-  GT4HIP_EFORMAT = 11     /* sequence text that is neither FastA nor FastQ, or malformed FastQ */
+  GT4HIP_EFORMAT = 11     /* sequence text that is neither FastA nor FastQ, or malformed FastQ; an index whose
+                             sections contradict each other (gt4hip_location_index_create) */
 };
 
 /* enum Rules of the reference, src/glistcompare.c:45-54 (same numeric values) */
@@ -266,6 +267,45 @@ typedef struct {
  * *n_hits <= capacity -- call with capacity 0 to size a buffer, or with a guess and again when *n_hits exceeds it. */
 int gt4hip_query_lookup_all (gt4hip_context *ctx, gt4hip_query_index *qindex, const uint64_t *words, uint64_t n_queries,
                              const gt4hip_query_params *params, gt4hip_query_hit *hits, uint64_t capacity, uint64_t *n_hits);
+
+/* ---- glistquery --locations: a GT4I index resident with its location section.
+ * gt4hip_location_index_create takes the two sections of a mapped index file (include/gt4_listfile.h: index_kmers,
+ * index_location_words) and keeps on the device: the k-mer section decoded to a list (gt4hip_location_index_list: what
+ * gt4hip_query_index_create and every statistic take; it lives as long as the location index), the first location of
+ * every k-mer, the packed locations, and the three bit sizes.  Both sections are copied from host memory in pieces.
+ * The k-mer section is checked ON THE DEVICE in the same pass that decodes it: first locations that descend, or
+ * one above num_locations, are GT4HIP_EFORMAT and nothing is made -- no kernel ever reads the location array through
+ * an unchecked offset.  Bit sizes with n_file_bits + n_subseq_bits + n_pos_bits + 1 > 64 are GT4HIP_EFORMAT too.  An
+ * index that does not fit the device is GT4HIP_ENOMEM. */
+typedef struct gt4hip_location_index gt4hip_location_index;
+int gt4hip_location_index_create (gt4hip_context *ctx, const void *host_kmers, uint64_t n_words, const void *host_locations,
+                                  uint64_t num_locations, uint32_t word_length, uint32_t n_file_bits, uint32_t n_subseq_bits,
+                                  uint32_t n_pos_bits, gt4hip_location_index **lindex);
+void gt4hip_location_index_free (gt4hip_location_index *lindex);
+const gt4hip_list *gt4hip_location_index_list (const gt4hip_location_index *lindex);
+uint64_t gt4hip_location_index_n_locations (const gt4hip_location_index *lindex);
+
+/* One place a word occurs, decoded (index_map_get_location, src/index-map.c:197-208): 16 bytes. */
+typedef struct {
+  uint64_t pos_dir;   /* position << 1 | strand (1: the canonical word is the reverse complement of the text) */
+  uint32_t file;      /* number of the file ...                                                               */
+  uint32_t seq;       /* ... and of the sequence in it, each in 32 bits as the reference holds them           */
+} gt4hip_location;
+
+/* gt4hip_query_lookup_all with the locations of every hit.  `qindex` must have been made of
+ * gt4hip_location_index_list (lindex).  The hits are the same records in (query, rank) order; count is the number of
+ * locations of the word in 32 bits (the reference's n_locations).  The locations of hit h are
+ * locations[sum of the counts of the hits before h ... + its count), in the order of the index.  Two variants of a
+ * query with the same canonical word are two hits, and the word's locations are copied twice, as the reference prints
+ * them twice.  Both totals are always returned; the two HOST arrays are filled only when *n_hits <= hit_capacity AND
+ * *n_locations <= loc_capacity, and are left untouched otherwise.  The device holds 16 bytes per location for the
+ * call: a batch too large for it is GT4HIP_ENOMEM -- split it. */
+int gt4hip_query_lookup_locations (gt4hip_context *ctx, gt4hip_query_index *qindex, const gt4hip_location_index *lindex,
+                                   const uint64_t *words, uint64_t n_queries, const gt4hip_query_params *params,
+                                   gt4hip_query_hit *hits, uint64_t hit_capacity, uint64_t *n_hits,
+                                   gt4hip_location *locations, uint64_t loc_capacity, uint64_t *n_locations);
+/* Device time of the gather kernel alone in the last gt4hip_query_lookup_locations on this index (HIP events). */
+double gt4hip_query_index_gather_ms (const gt4hip_query_index *qindex);
 
 /* One streaming pass over the records each (glistquery --median, --distribution, --gc; src/glistquery.c:831-932).
  * Smallest and largest count (0xffffffff and 0 for an empty list). */
