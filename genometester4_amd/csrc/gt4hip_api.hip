@@ -174,6 +174,7 @@ extern "C" int gt4hip_set_option (gt4hip_context *ctx, const char *name, int64_t
   else if (!strcmp (name, "grid")) ctx->grid_override = value;
   else if (!strcmp (name, "scan_group")) ctx->scan_group = (int) value;
   else if (!strcmp (name, "dynamic")) ctx->dynamic = (int) value;
+  else if (!strcmp (name, "a_rows")) ctx->a_rows = (int) value;
   else if (!strcmp (name, "kway")) ctx->kway_enabled = (int) value;
   else if (!strcmp (name, "kway_max")) ctx->kway_max = value == 8 ? 8 : (value == 33 ? 33 : 32);
   else if (!strcmp (name, "kway_g")) ctx->kway_g = value;

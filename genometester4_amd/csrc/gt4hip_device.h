@@ -81,7 +81,9 @@ __device__ __forceinline__ u32 dpp_wave_sum_u32 (u32 v)
 /* Exclusive prefix of the chunk ballots' popcounts (up to 128 chunks: two per lane, packed into
  * the halves of one dword for a single scan) and the empty sentinel chunk behind them; returns the
  * tile total.  Every lane of the calling wavefront takes part. */
-template <int NCH>
+/* SENTINEL = false: the caller's streams never look behind the table (kept_before is not used on them), and entry NCH of
+ * a table scanned short is a real chunk's: it is left alone. */
+template <int NCH, bool SENTINEL = true>
 __device__ __forceinline__ u32 chunk_scan (u64 *km, u32 *cp, int lane)
 {
   static_assert (NCH <= 2 * WAVE, "two chunks per lane");
@@ -92,7 +94,7 @@ __device__ __forceinline__ u32 chunk_scan (u64 *km, u32 *cp, int lane)
   const u32 t0 = last & 0xffffu, total = t0 + (last >> 16);
   if (lane < NCH) cp[lane] = (incl & 0xffffu) - v0;
   if (NCH > WAVE && lane + WAVE < NCH) cp[lane + WAVE] = t0 + (incl >> 16) - v1;
-  if (lane == 0) {
+  if (SENTINEL && lane == 0) {
     cp[NCH] = total;
     km[NCH] = 0;
   }

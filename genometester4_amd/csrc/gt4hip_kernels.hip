@@ -254,7 +254,8 @@ __device__ __forceinline__ u32 kept_before (const u64 *km, const u32 *cp, u32 z)
   return cp[c] + (u32) __popcll (km[c] & ((1ull << (z & 63u)) - 1ull));
 }
 
-template <int S, int NT, int IPT, int OPS, int FAST, class Shared>
+/* KR: the position rows the caller ranked, the first KR of IPT (all, or IPT / 2 in the A-rows body of the A-only kernels) */
+template <int S, int NT, int IPT, int KR, int OPS, int FAST, class Shared>
 __device__ __forceinline__ void scatter_stream (Shared &sh, u32 *dst32, const PairParams &p, u32 nbs, int lane, int wid,
                                                 const u64 (&key)[IPT], const u32 (&fa)[IPT], const u32 (&fb)[IPT], const u32 (&meta)[IPT])
 {
@@ -266,7 +267,7 @@ __device__ __forceinline__ void scatter_stream (Shared &sh, u32 *dst32, const Pa
   constexpr bool A_ONLY = S == 1 || S == 2;
   const u32 pna = A_ONLY ? 0u : kept_before (sh.kmask[S], sh.cpre[S], nbs); /* nbs: tile position of the first B record */
 #pragma unroll
-  for (int k = 0; k < IPT; k++) {
+  for (int k = 0; k < KR; k++) {
     const u32 chunk = (u32) k * NW + (u32) wid;
     /* the chunk's ballot is the same in every lane: as a scalar it IS the lane mask of the kept
      * records (no per-lane bit test) and the count of kept lanes below is one mbcnt pair */
@@ -457,12 +458,23 @@ k_pair_merge (const u32 *__restrict__ A, u64 nA, const u32 *__restrict__ B, u64 
   __shared__ Shared sh;
   u32 *const lds32 = sh.raw;
 
+  /* A-rows body (single-pass A-only kernels: the intersection and the first complement do per-record work on A records only).
+   * Row k of a thread is position k * NT + tid, and the A records lie at [0, na): in a tile with na <= NT * KA, KA = IPT / 2
+   * -- the usual tile of two lists of similar density -- rows KA .. IPT - 1 hold B records and padding alone.  Such a tile is
+   * ranked, scanned and scattered by a body compiled for KA rows (one search group, no liveness test, keep masks and prefix
+   * table of KA * NW chunks); every other tile (A much denser than B there) takes the body for IPT rows.  Option "a_rows" =
+   * -1 (p.a_rows_off) always takes the latter. */
+  constexpr bool A_ROWS = (OPS == 2 || OPS == 4) && MODE == MODE_LOOKBACK;
+  constexpr int KA = IPT / 2;
   /* The general any-combination kernels sit at their register bound (128 at sixteen wavefronts per CU, 85 for the
    * count-only geometry's three workgroups): there the thread number is made opaque once per tile, so that
    * addresses and masks derived from it are recomputed where they are used (a few VALU each) instead of living in
    * registers across the whole loop, hoisted by the compiler -- which had two to six of them in scratch memory.
-   * tools/kernel_resources.py / tests/test_kernel_resources.py: no instantiation may spill a vector register. */
-  constexpr bool OPAQUE_TID = OPS == 0 && !(FAST == 1 && (OPSET == 3 || OPSET == 5) && MODE != MODE_COUNT);
+   * tools/kernel_resources.py / tests/test_kernel_resources.py: no instantiation may spill a vector register.
+   * The A_ROWS kernels take it too: with two bodies in the loop the hoisted values pushed the prefetched records into scratch
+   * memory (7 to 27 VGPRs spilled); opaque, the intersection needs 108 registers where the one body needed 120.  (Opaque
+   * for the general body alone: 127 registers, no spill at 1024 threads, and all of the A-rows body's gain gone.) */
+  constexpr bool OPAQUE_TID = A_ROWS || (OPS == 0 && !(FAST == 1 && (OPSET == 3 || OPSET == 5) && MODE != MODE_COUNT));
   int tid = threadIdx.x, lane = tid & (WAVE - 1); /* (not const: OPAQUE_TID) */
   const int wid = __builtin_amdgcn_readfirstlane (tid / WAVE); /* wave-uniform: scalar branches on it */
   static_assert (pair_variant_exists ({ NT, IPT, MODE, OPS, FAST, OPSET }), "not an instantiation the selection can return (a compile-time stream set belongs to the any-combination kernel)");
@@ -753,180 +765,196 @@ PROF (
       base_lo = (u32) t_min;
     }
     PHASE_STAMP (2); /* ring read, housekeeping issue, fetch issue */
-    /* ---- phase 1: rank, classify, predicates.  Chunks are handled two at a time so that every
-     * step of the search has two independent LDS reads in flight per lane. */
+    /* Ranking and staging exist for KR position rows per thread: all IPT of them, or -- the A-rows body of the A-only kernels
+     * (A_ROWS) -- the IPT / 2 that hold every A record of the tile.  One body each, compiled for either row count; what lies
+     * between them (the late fetch parts, barrier B1) is common code: every fetch part keeps its one place of issue. */
     u64 key[IPT];
     u32 fa[IPT], fb[IPT], meta[IPT]; /* meta: rank | kind << 16 | is_a << 18 */
-    {
-      const StreamCoef c0 = make_coef<0> (p), c1 = make_coef<1> (p), c2 = make_coef<2> (p), c3 = make_coef<3> (p);
-      static_assert (IPT % G == 0, "chunks are searched in groups");
+    auto rank_rows = [&] (auto rows) __attribute__ ((always_inline)) {
+      constexpr int KR = decltype (rows)::value;
+      constexpr bool AROWS = KR < IPT;
+      static_assert (!AROWS || (A_ROWS && DEFER), "the A-rows body belongs to the single-pass A-only kernels");
+      /* ---- phase 1: rank, classify, predicates.  Chunks are handled two at a time so that every
+       * step of the search has two independent LDS reads in flight per lane. */
+      {
+        const StreamCoef c0 = make_coef<0> (p), c1 = make_coef<1> (p), c2 = make_coef<2> (p), c3 = make_coef<3> (p);
+        static_assert (KR % G == 0, "chunks are searched in groups");
 #pragma unroll
-      for (int kk = 0; kk < IPT; kk += G) {
-        if (STAGGER && kk == G && nxt < ntl) {
+        for (int kk = 0; kk < KR; kk += G) {
+          if (STAGGER && kk == G && nxt < ntl) {
 #pragma unroll
-          for (int j = F_TOP; j < F_TOP + F_MID; j++) fetch_part (tn, j);
-        } /* staggered fetch: see fetch_part */
-        bool live[G], valid[G], any_live = false;
-        u32 is_a[G], own[G], lim[G], lo[G]; /* is_a: wave-uniform (chunks never mix the lists); lim, lo: bytes (12 per record) */
-        u32 sbase[G], sn[G];                /* wave-uniform: dword base and length of the run this chunk is ranked in */
-        u32 plim[G];                        /* wave-uniform: positions below it hold a record this call looks at */
-        u64 ky[G];
+            for (int j = F_TOP; j < F_TOP + F_MID; j++) fetch_part (tn, j);
+          } /* staggered fetch: see fetch_part */
+          bool live[G], valid[G], any_live = false;
+          u32 is_a[G], own[G], lim[G], lo[G]; /* is_a: wave-uniform (chunks never mix the lists); lim, lo: bytes (12 per record) */
+          u32 sbase[G], sn[G];                /* wave-uniform: dword base and length of the run this chunk is ranked in */
+          u32 plim[G];                        /* wave-uniform: positions below it hold a record this call looks at */
+          u64 ky[G];
 #pragma unroll
-        for (int u = 0; u < G; u++) {
-          const u32 cbeg = ((u32) (kk + u) * NW + (u32) wid) * WAVE; /* wave-uniform */
-          is_a[u] = cbeg < nbs ? 1u : 0u;
-          plim[u] = is_a[u] ? na : (need_b ? npos : 0u);
-          live[u] = cbeg < plim[u];
-          any_live |= live[u];
-        }
-        if (!any_live) {
-          /* nothing in these chunks can be kept (padding, or B records of a call that keeps none
-           * of them on their own: pairs are found from the A side): empty keep masks, no other work */
+          for (int u = 0; u < G; u++) {
+            const u32 cbeg = ((u32) (kk + u) * NW + (u32) wid) * WAVE; /* wave-uniform */
+            /* A-rows body: every row is an A row (na <= NT * KR) and is ranked without asking: a chunk past na keeps nothing by
+             * its lanes' own test (e < na), and its empty mask comes out of the same ballot as everybody's */
+            is_a[u] = AROWS ? 1u : (cbeg < nbs ? 1u : 0u);
+            plim[u] = is_a[u] ? na : (need_b ? npos : 0u);
+            live[u] = AROWS ? true : cbeg < plim[u];
+            any_live |= live[u];
+          }
+          if (!AROWS && !any_live) {
+            /* nothing in these chunks can be kept (padding, or B records of a call that keeps none
+             * of them on their own: pairs are found from the A side): empty keep masks, no other work */
+#pragma unroll
+            for (int u = 0; u < G; u++) {
+              const int k = kk + u;
+              key[k] = 0;
+              fa[k] = fb[k] = 0;
+              meta[k] = KIND_SKIP << 16;
+              {
+                const u32 chunk = (u32) k * NW + (u32) wid;
+#pragma unroll
+                for (int s = 0; s < 4; s++)
+                  if ((ops >> s) & 1u) store_lane0 (&sh.kmask[s][chunk], sh.trash, 0ull, lane);
+              }
+            }
+            continue;
+          }
+#pragma unroll
+          for (int u = 0; u < G; u++) {
+            /* one per-lane compare against a scalar limit; everything uniform stays a scalar select
+             * (mixing uniform and per-lane conditions costs the shared scalar unit a mask operation each) */
+            const u32 e = (u32) (kk + u) * NT + (u32) tid;
+            u32 at;
+            if (OPS == 2) { /* (the intersection alone measures 4 % FASTER with the condition spelled out) */
+              valid[u] = live[u] && (is_a[u] ? e < na : e < npos);
+              at = valid[u] ? (is_a[u] ? 3 * e : OB + 3 * (e - nbs)) : 0u;
+            } else {
+              valid[u] = e < plim[u]; /* (a chunk that is not live has no position below its limit) */
+              const u32 off = is_a[u] ? 0u : OB - 3 * nbs;
+              at = valid[u] ? 3 * e + off : 0u;
+            }
+            ky[u] = (u64) lds32[at] | ((u64) lds32[at + 1] << 32);
+            own[u] = lds32[at + 2];
+            sbase[u] = is_a[u] ? OB : 0u;
+            sn[u] = is_a[u] ? nb : na;
+            lim[u] = valid[u] ? 12 * sn[u] : 0u;
+            lo[u] = 0;
+          }
+          rank_group<CAP, G> (lds32, sbase, sn, ky, lo, narrow, base_lo);
 #pragma unroll
           for (int u = 0; u < G; u++) {
             const int k = kk + u;
-            key[k] = 0;
-            fa[k] = fb[k] = 0;
-            meta[k] = KIND_SKIP << 16;
-            {
-              const u32 chunk = (u32) k * NW + (u32) wid;
-#pragma unroll
-              for (int s = 0; s < 4; s++)
-                if ((ops >> s) & 1u) store_lane0 (&sh.kmask[s][chunk], sh.trash, 0ull, lane);
+            const u32 chunk = (u32) k * NW + (u32) wid;
+            const u32 r = (lo[u] * 43691u) >> 19; /* lo / 12, exact for multiples of 12 below 2^16 */
+            const bool in = lo[u] < lim[u];
+            const u32 oat = sbase[u] + (in ? lo[u] >> 2 : 0u);
+            const u64 okey = (u64) lds32[oat] | ((u64) lds32[oat + 1] << 32);
+            const u32 ocnt = lds32[oat + 2];
+            const bool matched = in & (okey == ky[u]);
+            if (FAST && (OPS == 2 || OPS == 4)) {
+              /* A-only kernels with the rule folded in: live chunks are A chunks (`in` implies a valid
+               * lane), and the kept records are decided by the match alone */
+              u32 f;
+              bool keep;
+              if (OPS == 2 && FAST == 1) {
+                f = own[u] < ocnt ? own[u] : ocnt;                  /* MIN */
+                keep = matched && f >= (p.cutoff ? p.cutoff : 1u); /* both counts >= cutoff <=> min >= cutoff; and min != 0 */
+              } else if (OPS == 2) {
+                /* FAST = 2 / 3: a step of intersect_multi's left-to-right chain (reference src/glistcompare.c:655-678): the
+                 * running minimum restarts at 0 (`if (!freq || c < freq) freq = c`, :669 = RULE_MINZ); intermediate steps
+                 * keep every shared key (FAST = 2), the last one those whose count reaches the cutoff (FAST = 3, :683) */
+                const u32 mn = own[u] < ocnt ? own[u] : ocnt;
+                f = own[u] == 0u ? ocnt : mn;
+                keep = matched && (FAST == 2 || f >= p.cutoff);
+              } else {
+                const u32 xb = matched ? ocnt : 0u;
+                f = own[u] - xb;                                   /* SUBTRACT: kept only when f1 >= cutoff > f2 */
+                keep = valid[u] && own[u] >= p.cutoff && xb < p.cutoff && f != 0u;
+              }
+              key[k] = ky[u];
+              fa[k] = f;
+              fb[k] = 0;
+              meta[k] = 0;
+              const u64 m = __builtin_amdgcn_ballot_w64 (keep);
+              store_lane0 (&sh.kmask[OPS == 2 ? 1 : 2][chunk], sh.trash, m, lane);
+              if (OPS == 2) acc_sum1 += keep ? f : 0u;
+              else acc_sum2 += keep ? f : 0u;
+              continue;
             }
-          }
-          continue;
-        }
-#pragma unroll
-        for (int u = 0; u < G; u++) {
-          /* one per-lane compare against a scalar limit; everything uniform stays a scalar select
-           * (mixing uniform and per-lane conditions costs the shared scalar unit a mask operation each) */
-          const u32 e = (u32) (kk + u) * NT + (u32) tid;
-          u32 at;
-          if (OPS == 2) { /* (the intersection alone measures 4 % FASTER with the condition spelled out) */
-            valid[u] = live[u] && (is_a[u] ? e < na : e < npos);
-            at = valid[u] ? (is_a[u] ? 3 * e : OB + 3 * (e - nbs)) : 0u;
-          } else {
-            valid[u] = e < plim[u]; /* (a chunk that is not live has no position below its limit) */
-            const u32 off = is_a[u] ? 0u : OB - 3 * nbs;
-            at = valid[u] ? 3 * e + off : 0u;
-          }
-          ky[u] = (u64) lds32[at] | ((u64) lds32[at + 1] << 32);
-          own[u] = lds32[at + 2];
-          sbase[u] = is_a[u] ? OB : 0u;
-          sn[u] = is_a[u] ? nb : na;
-          lim[u] = valid[u] ? 12 * sn[u] : 0u;
-          lo[u] = 0;
-        }
-        rank_group<CAP, G> (lds32, sbase, sn, ky, lo, narrow, base_lo);
-#pragma unroll
-        for (int u = 0; u < G; u++) {
-          const int k = kk + u;
-          const u32 chunk = (u32) k * NW + (u32) wid;
-          const u32 r = (lo[u] * 43691u) >> 19; /* lo / 12, exact for multiples of 12 below 2^16 */
-          const bool in = lo[u] < lim[u];
-          const u32 oat = sbase[u] + (in ? lo[u] >> 2 : 0u);
-          const u64 okey = (u64) lds32[oat] | ((u64) lds32[oat + 1] << 32);
-          const u32 ocnt = lds32[oat + 2];
-          const bool matched = in & (okey == ky[u]);
-          if (FAST && (OPS == 2 || OPS == 4)) {
-            /* A-only kernels with the rule folded in: live chunks are A chunks (`in` implies a valid
-             * lane), and the kept records are decided by the match alone */
-            u32 f;
-            bool keep;
-            if (OPS == 2 && FAST == 1) {
-              f = own[u] < ocnt ? own[u] : ocnt;                  /* MIN */
-              keep = matched && f >= (p.cutoff ? p.cutoff : 1u); /* both counts >= cutoff <=> min >= cutoff; and min != 0 */
-            } else if (OPS == 2) {
-              /* FAST = 2 / 3: a step of intersect_multi's left-to-right chain (reference src/glistcompare.c:655-678): the
-               * running minimum restarts at 0 (`if (!freq || c < freq) freq = c`, :669 = RULE_MINZ); intermediate steps
-               * keep every shared key (FAST = 2), the last one those whose count reaches the cutoff (FAST = 3, :683) */
-              const u32 mn = own[u] < ocnt ? own[u] : ocnt;
-              f = own[u] == 0u ? ocnt : mn;
-              keep = matched && (FAST == 2 || f >= p.cutoff);
+            if (FAST && OPS == 1) {
+              /* union with ADD folded in: an A record carries its partner's count, a B record with a
+               * partner keeps nothing; FAST == 2 (intermediate N-way level) keeps zero sums too */
+              const u32 xo = (is_a[u] && matched) ? ocnt : 0u; /* the partner's count travels with the A record */
+              const u32 f = own[u] + xo;
+              const bool keep = valid[u] && (is_a[u] || !matched) &&
+                                (FAST == 2 || (FAST == 3 ? f >= p.cutoff : ((own[u] >= p.cutoff || xo >= p.cutoff) && f != 0u)));
+              key[k] = ky[u];
+              fa[k] = f;
+              fb[k] = 0;
+              meta[k] = r | (is_a[u] << 18);
+              const u64 m = __builtin_amdgcn_ballot_w64 (keep);
+              sh.kmask[0][chunk] = m;
+              acc_sum0 += keep ? f : 0u;
+              continue;
+            }
+            u32 kind, xa, xb;
+            if (is_a[u]) {
+              kind = matched ? KIND_BOTH : KIND_A;
+              xa = own[u];
+              xb = matched ? ocnt : 0u;
             } else {
-              const u32 xb = matched ? ocnt : 0u;
-              f = own[u] - xb;                                   /* SUBTRACT: kept only when f1 >= cutoff > f2 */
-              keep = valid[u] && own[u] >= p.cutoff && xb < p.cutoff && f != 0u;
+              kind = matched ? KIND_SKIP : KIND_B;
+              xa = 0;
+              xb = own[u];
             }
+            if (!valid[u]) kind = KIND_SKIP;
             key[k] = ky[u];
-            fa[k] = f;
-            fb[k] = 0;
-            meta[k] = 0;
-            const u64 m = __builtin_amdgcn_ballot_w64 (keep);
-            store_lane0 (&sh.kmask[OPS == 2 ? 1 : 2][chunk], sh.trash, m, lane);
-            if (OPS == 2) acc_sum1 += keep ? f : 0u;
-            else acc_sum2 += keep ? f : 0u;
-            continue;
+            fa[k] = xa;
+            fb[k] = xb;
+            meta[k] = (OPS == 2 || OPS == 4) ? 0u : (r | (kind << 16) | (is_a[u] << 18)); /* A-only kernels place by the own prefix alone */
+            u32 f;
+            if (ops & 1u) {
+              const bool keep = (FAST && OPS == 0) ? eval_default<0> (kind, xa, xb, p.cutoff, f) : eval_stream<0> (kind, xa, xb, c0, f);
+              const u64 m = __builtin_amdgcn_ballot_w64 (keep);
+              sh.kmask[0][chunk] = m;
+              acc_sum0 += keep ? f : 0u;
+            }
+            if ((!FAST || OPS == 0) && (ops & 2u)) {
+              const bool keep = (FAST && OPS == 0) ? eval_default<1> (kind, xa, xb, p.cutoff, f) : eval_stream<1> (kind, xa, xb, c1, f);
+              const u64 m = __builtin_amdgcn_ballot_w64 (keep);
+              sh.kmask[1][chunk] = m;
+              acc_sum1 += keep ? f : 0u;
+            }
+            if ((!FAST || OPS == 0) && (ops & 4u)) {
+              const bool keep = (FAST && OPS == 0) ? eval_default<2> (kind, xa, xb, p.cutoff, f) : eval_stream<2> (kind, xa, xb, c2, f);
+              const u64 m = __builtin_amdgcn_ballot_w64 (keep);
+              sh.kmask[2][chunk] = m;
+              acc_sum2 += keep ? f : 0u;
+            }
+            if ((!FAST || OPS == 0) && (ops & 8u)) {
+              const bool keep = (FAST && OPS == 0) ? eval_default<3> (kind, xa, xb, p.cutoff, f) : eval_stream<3> (kind, xa, xb, c3, f);
+              const u64 m = __builtin_amdgcn_ballot_w64 (keep);
+              sh.kmask[3][chunk] = m;
+              acc_sum3 += keep ? f : 0u;
+            }
+            if (OPS != 0) fa[k] = f; /* the one stream's count: staging does not evaluate the rule again */
           }
-          if (FAST && OPS == 1) {
-            /* union with ADD folded in: an A record carries its partner's count, a B record with a
-             * partner keeps nothing; FAST == 2 (intermediate N-way level) keeps zero sums too */
-            const u32 xo = (is_a[u] && matched) ? ocnt : 0u; /* the partner's count travels with the A record */
-            const u32 f = own[u] + xo;
-            const bool keep = valid[u] && (is_a[u] || !matched) &&
-                              (FAST == 2 || (FAST == 3 ? f >= p.cutoff : ((own[u] >= p.cutoff || xo >= p.cutoff) && f != 0u)));
-            key[k] = ky[u];
-            fa[k] = f;
-            fb[k] = 0;
-            meta[k] = r | (is_a[u] << 18);
-            const u64 m = __builtin_amdgcn_ballot_w64 (keep);
-            sh.kmask[0][chunk] = m;
-            acc_sum0 += keep ? f : 0u;
-            continue;
-          }
-          u32 kind, xa, xb;
-          if (is_a[u]) {
-            kind = matched ? KIND_BOTH : KIND_A;
-            xa = own[u];
-            xb = matched ? ocnt : 0u;
-          } else {
-            kind = matched ? KIND_SKIP : KIND_B;
-            xa = 0;
-            xb = own[u];
-          }
-          if (!valid[u]) kind = KIND_SKIP;
-          key[k] = ky[u];
-          fa[k] = xa;
-          fb[k] = xb;
-          meta[k] = (OPS == 2 || OPS == 4) ? 0u : (r | (kind << 16) | (is_a[u] << 18)); /* A-only kernels place by the own prefix alone */
-          u32 f;
-          if (ops & 1u) {
-            const bool keep = (FAST && OPS == 0) ? eval_default<0> (kind, xa, xb, p.cutoff, f) : eval_stream<0> (kind, xa, xb, c0, f);
-            const u64 m = __builtin_amdgcn_ballot_w64 (keep);
-            sh.kmask[0][chunk] = m;
-            acc_sum0 += keep ? f : 0u;
-          }
-          if ((!FAST || OPS == 0) && (ops & 2u)) {
-            const bool keep = (FAST && OPS == 0) ? eval_default<1> (kind, xa, xb, p.cutoff, f) : eval_stream<1> (kind, xa, xb, c1, f);
-            const u64 m = __builtin_amdgcn_ballot_w64 (keep);
-            sh.kmask[1][chunk] = m;
-            acc_sum1 += keep ? f : 0u;
-          }
-          if ((!FAST || OPS == 0) && (ops & 4u)) {
-            const bool keep = (FAST && OPS == 0) ? eval_default<2> (kind, xa, xb, p.cutoff, f) : eval_stream<2> (kind, xa, xb, c2, f);
-            const u64 m = __builtin_amdgcn_ballot_w64 (keep);
-            sh.kmask[2][chunk] = m;
-            acc_sum2 += keep ? f : 0u;
-          }
-          if ((!FAST || OPS == 0) && (ops & 8u)) {
-            const bool keep = (FAST && OPS == 0) ? eval_default<3> (kind, xa, xb, p.cutoff, f) : eval_stream<3> (kind, xa, xb, c3, f);
-            const u64 m = __builtin_amdgcn_ballot_w64 (keep);
-            sh.kmask[3][chunk] = m;
-            acc_sum3 += keep ? f : 0u;
-          }
-          if (OPS != 0) fa[k] = f; /* the one stream's count: staging does not evaluate the rule again */
         }
       }
-    }
-    /* cut the value-numbering link between phase 1 and phase 3: without it the compiler keeps every
-     * stream's count of every record alive across phase 2 instead of recomputing it (2x the VGPRs) */
+      /* cut the value-numbering link between phase 1 and phase 3: without it the compiler keeps every
+       * stream's count of every record alive across phase 2 instead of recomputing it (2x the VGPRs) */
 #pragma unroll
-    for (int k = 0; k < IPT; k++) {
-      if (OPS == 0) asm volatile ("" : "+v"(fa[k]), "+v"(fb[k]), "+v"(meta[k]));
-      else if (OPS == 1) asm volatile ("" : "+v"(fa[k]), "+v"(meta[k]));
-      else asm volatile ("" : "+v"(fa[k]));
-    }
+      for (int k = 0; k < KR; k++) {
+        if (OPS == 0) asm volatile ("" : "+v"(fa[k]), "+v"(fb[k]), "+v"(meta[k]));
+        else if (OPS == 1) asm volatile ("" : "+v"(fa[k]), "+v"(meta[k]));
+        else asm volatile ("" : "+v"(fa[k]));
+      }
+    };
+    /* workgroup-uniform: a scalar branch per tile and body */
+    const bool a_body = A_ROWS && !p.a_rows_off && na <= (u32) (NT * KA);
+    if constexpr (A_ROWS) {
+      if (a_body) rank_rows (std::integral_constant<int, KA>{});
+      else rank_rows (std::integral_constant<int, IPT>{});
+    } else rank_rows (std::integral_constant<int, IPT>{});
     /* any-combination kernel: resolved BEFORE the rest of the fetch is issued -- the memory counter
      * retires in order, so looking at the words asked for at the top of the iteration waits for every
      * load issued before this point: only the two parts issued at the top with them */
@@ -958,69 +986,76 @@ PROF (
     PHASE_STAMP (3); /* phase 1 */
     __syncthreads (); /* B1: all input reads done */
     PHASE_STAMP (4); /* barrier B1 */
-
-    /* ---- phase 2.  Single-output (deferred) kernels: EVERY wavefront scans the chunk ballots
-     * itself and writes the same prefix table to LDS, so nobody has to wait for anybody -- no
-     * barrier between ranking and staging; wavefront 0 also publishes the tile total. */
-    u32 my_total = 0;
-    if (DEFER) {
-      my_total = chunk_scan<NCH> (sh.kmask[S0], sh.cpre[S0], lane);
-      blk_cnt += my_total; /* every lane of every wavefront holds the same sum; the kernel-total reduction reads lane 0 of wave S0 */
-      if (wid == 0 && MODE == MODE_LOOKBACK) { /* a uniform branch first: fifteen wavefronts skip the exec bookkeeping */
-        if (lane == 0) publish_u32 (&agg[(u64) S0 * n_rows * WAVE + cur], AGG_READY | my_total);
-      }
-    }
-    /* any-combination kernel: wavefront s owns stream s: chunk scan, tile total, publish */
-    if (!DEFER && wid < 4 && ((ops >> wid) & 1u)) {
-      const int s = wid;
-      const u32 total = chunk_scan<NCH> (sh.kmask[s], sh.cpre[s], lane);
-      if (lane == 0) {
-        sh.tot[s] = total;
-        blk_cnt += total;
-        if (MODE == MODE_COUNT) {
-          if (desc) desc[4 * (u64) cur + s] = total; /* pass 1 of the two-pass path: counts for the scan kernel */
-        } else if (MODE == MODE_LOOKBACK) {
-          publish_u32 (&agg[(u64) s * n_rows * WAVE + cur], AGG_READY | total);
+    auto stage_rows = [&] (auto rows) __attribute__ ((always_inline)) {
+      constexpr int KR = decltype (rows)::value;
+      constexpr bool AROWS = KR < IPT;
+      /* ---- phase 2.  Single-output (deferred) kernels: EVERY wavefront scans the chunk ballots
+       * itself and writes the same prefix table to LDS, so nobody has to wait for anybody -- no
+       * barrier between ranking and staging; wavefront 0 also publishes the tile total. */
+      u32 my_total = 0;
+      if (DEFER) {
+        my_total = chunk_scan<KR * NW, !AROWS> (sh.kmask[S0], sh.cpre[S0], lane); /* (the A-rows body wrote the masks of KR * NW chunks only) */
+        blk_cnt += my_total; /* every lane of every wavefront holds the same sum; the kernel-total reduction reads lane 0 of wave S0 */
+        if (wid == 0 && MODE == MODE_LOOKBACK) { /* a uniform branch first: fifteen wavefronts skip the exec bookkeeping */
+          if (lane == 0) publish_u32 (&agg[(u64) S0 * n_rows * WAVE + cur], AGG_READY | my_total);
         }
       }
-    }
-
-    PHASE_STAMP (5); /* phase 2 */
-    if (GDEFER) {
-      /* write the previous tile's streams out of the staging area, then (B2) stage this tile's */
-      if (it >= 1) {
-#pragma unroll
-        for (int s = 0; s < 4; s++)
-          if ((ops >> s) & 1u) write_out_fixed<NT, (3 * CAP / 4 + NT - 1) / NT> (outs.rec[s], uniform64 (sh.excl[s]), g_tot[s], sh.stage[0] + 3 * g_off[s], tid);
-      }
-      __syncthreads (); /* B2: staging area free, this tile's totals and prefix tables complete */
-      u32 run = 0;
-#pragma unroll
-      for (int s = 0; s < 4; s++) {
-        g_off[s] = run;
-        g_tot[s] = ((ops >> s) & 1u) ? uniform32 (sh.tot[s]) : 0u;
-        run += (g_tot[s] + 3u) & ~3u;
-      }
-#pragma unroll
-      for (int s = 0; s < 4; s++) {
-        if (!((ops >> s) & 1u)) continue;
-        u32 *const dst = sh.stage[0] + 3 * g_off[s];
-        switch (s) {
-          case 0: scatter_stream<0, NT, IPT, OPS, FAST> (sh, dst, p, nbs, lane, wid, key, fa, fb, meta); break;
-          case 1: scatter_stream<1, NT, IPT, OPS, FAST> (sh, dst, p, nbs, lane, wid, key, fa, fb, meta); break;
-          case 2: scatter_stream<2, NT, IPT, OPS, FAST> (sh, dst, p, nbs, lane, wid, key, fa, fb, meta); break;
-          default: scatter_stream<3, NT, IPT, OPS, FAST> (sh, dst, p, nbs, lane, wid, key, fa, fb, meta); break;
+      /* any-combination kernel: wavefront s owns stream s: chunk scan, tile total, publish */
+      if (!DEFER && wid < 4 && ((ops >> wid) & 1u)) {
+        const int s = wid;
+        const u32 total = chunk_scan<NCH> (sh.kmask[s], sh.cpre[s], lane);
+        if (lane == 0) {
+          sh.tot[s] = total;
+          blk_cnt += total;
+          if (MODE == MODE_COUNT) {
+            if (desc) desc[4 * (u64) cur + s] = total; /* pass 1 of the two-pass path: counts for the scan kernel */
+          } else if (MODE == MODE_LOOKBACK) {
+            publish_u32 (&agg[(u64) s * n_rows * WAVE + cur], AGG_READY | total);
+          }
         }
       }
-    } else if (DEFER) {
-      /* stage this tile in the slot the write-out at the top of this iteration freed */
-      u32 *const slot = sh.stage[it % LAG];
-      const u32 my_tot = my_total;
-      scatter_stream<S0, NT, IPT, OPS, FAST> (sh, slot, p, nbs, lane, wid, key, fa, fb, meta);
+
+      PHASE_STAMP (5); /* phase 2 */
+      if (GDEFER) {
+        /* write the previous tile's streams out of the staging area, then (B2) stage this tile's */
+        if (it >= 1) {
 #pragma unroll
-      for (int q = 0; q + 1 < LAG; q++) pend_tot[q] = pend_tot[q + 1];
-      pend_tot[LAG - 1] = my_tot;
-    }
+          for (int s = 0; s < 4; s++)
+            if ((ops >> s) & 1u) write_out_fixed<NT, (3 * CAP / 4 + NT - 1) / NT> (outs.rec[s], uniform64 (sh.excl[s]), g_tot[s], sh.stage[0] + 3 * g_off[s], tid);
+        }
+        __syncthreads (); /* B2: staging area free, this tile's totals and prefix tables complete */
+        u32 run = 0;
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+          g_off[s] = run;
+          g_tot[s] = ((ops >> s) & 1u) ? uniform32 (sh.tot[s]) : 0u;
+          run += (g_tot[s] + 3u) & ~3u;
+        }
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+          if (!((ops >> s) & 1u)) continue;
+          u32 *const dst = sh.stage[0] + 3 * g_off[s];
+          switch (s) {
+            case 0: scatter_stream<0, NT, IPT, KR, OPS, FAST> (sh, dst, p, nbs, lane, wid, key, fa, fb, meta); break;
+            case 1: scatter_stream<1, NT, IPT, KR, OPS, FAST> (sh, dst, p, nbs, lane, wid, key, fa, fb, meta); break;
+            case 2: scatter_stream<2, NT, IPT, KR, OPS, FAST> (sh, dst, p, nbs, lane, wid, key, fa, fb, meta); break;
+            default: scatter_stream<3, NT, IPT, KR, OPS, FAST> (sh, dst, p, nbs, lane, wid, key, fa, fb, meta); break;
+          }
+        }
+      } else if (DEFER) {
+        /* stage this tile in the slot the write-out at the top of this iteration freed */
+        u32 *const slot = sh.stage[it % LAG];
+        const u32 my_tot = my_total;
+        scatter_stream<S0, NT, IPT, KR, OPS, FAST> (sh, slot, p, nbs, lane, wid, key, fa, fb, meta);
+#pragma unroll
+        for (int q = 0; q + 1 < LAG; q++) pend_tot[q] = pend_tot[q + 1];
+        pend_tot[LAG - 1] = my_tot;
+      }
+    };
+    if constexpr (A_ROWS) {
+      if (a_body) stage_rows (std::integral_constant<int, KA>{});
+      else stage_rows (std::integral_constant<int, IPT>{});
+    } else stage_rows (std::integral_constant<int, IPT>{});
     PHASE_STAMP (6); /* (any-combination kernel: previous tile's write-out, B2) staging scatter */
     if (tid == 0) {
       sh.tile_id[s_nn] = hk_tile;

@@ -52,6 +52,7 @@ int gt4hip_run_pair (gt4hip_context *ctx, const uint32_t *A, uint64_t nA, const 
   }
   PairParams p = p_in;
   p.spin_limit = ctx->spin_limit;
+  p.a_rows_off = ctx->a_rows < 0 ? 1u : 0u;
   memset (run, 0, sizeof *run);
   const uint64_t total = nA + nB;
   if (!total || !p.ops) return GT4HIP_OK;

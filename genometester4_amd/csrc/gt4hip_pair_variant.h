@@ -30,6 +30,7 @@ struct PairParams {
   uint32_t spin_limit;     /* bound of every inter-workgroup wait (0: the default, ~seconds); tests set it low */
   uint32_t scan_group;     /* 0: one scanner wavefront per stream; 1: summers + chainer (launches with many rows) */
   uint32_t dynamic;        /* 0: tiles dealt round-robin; 1: by a ticket counter (ctl->ticket), three tiles ahead */
+  uint32_t a_rows_off;     /* A-only kernels: 0: a tile whose A records fit half the position rows takes the A-rows body; 1: never */
 };
 
 enum MergeMode : int {

@@ -611,6 +611,9 @@ int gt4hip_synchronize (gt4hip_context *ctx);
  *   "dynamic" = 1 / -1 tiles of the single-pass kernel always / never dealt by a ticket counter
  *                      (0: automatic -- the record-writing kernels except a complement alone)
  *   "scan_group" = 1 / -1  the scanner as a group of wavefronts always / never (0: by launch size)
+ *   "a_rows" = 0 / -1  single-pass intersection and first complement: a tile whose first-list records fit half
+ *                      of the workgroup's position rows is ranked by the body compiled for those rows alone /
+ *                      every tile by the general body (experiments, tests)
  *   "geom0" / "geom1"  force the 512- / 1024-thread geometry (experiments). */
 int gt4hip_set_option (gt4hip_context *ctx, const char *name, int64_t value);
 /* Diagnostic counters of a context.  "single_pass_fallbacks": calls whose single-pass merge gave up a

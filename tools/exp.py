@@ -23,7 +23,7 @@ drivers.)
   exp.py table [--n N]
         count tables of six lists by the N-way tile kernel (kway 1) and by merges (kway 0)
 
-Environment: SCAN_GROUP, DYNAMIC, SPIN_LIMIT, KWAY_G, KWAY_VT, GRID, GEOM0, GEOM1, TWO_PASS set the library's options;
+Environment: SCAN_GROUP, DYNAMIC, SPIN_LIMIT, KWAY_G, KWAY_VT, GRID, GEOM0, GEOM1, TWO_PASS, A_ROWS set the library's options;
 GT4HIP_LIB selects another build of the library (e.g. `make -C genometester4_amd/csrc prof`: libgt4hip_prof.so).
 """
 import argparse
@@ -35,7 +35,7 @@ from genometester4_amd import capi, synth  # noqa: E402
 
 
 def _opts(ctx):
-    for opt in ("scan_group", "dynamic", "spin_limit", "kway_g", "kway_vt", "grid", "geom0", "geom1", "two_pass"):
+    for opt in ("scan_group", "dynamic", "spin_limit", "kway_g", "kway_vt", "grid", "geom0", "geom1", "two_pass", "a_rows"):
         if os.environ.get(opt.upper()):
             ctx.set_option(opt, int(os.environ[opt.upper()]))
 
