@@ -33,6 +33,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 namespace gt4 {
 
 namespace {
@@ -73,6 +75,19 @@ struct RadixPlan {
   u32 shift[RADIX_MAX_PASSES];
   u32 bits[RADIX_MAX_PASSES];
 };
+
+/* The control words in front of a chained scan's tile states, cleared with them: a ticket per launch that takes its
+ * tiles by ticket (one scatter pass each; the fold has one), then the word that a wait which gives up raises. */
+struct ScanControl {
+  u32 ticket[15];
+  u32 err;
+};
+/* the sort's workspace: this, then RADIX_MAX_DIGITS state words per tile */
+struct RadixHead {
+  u64 bases[RADIX_MAX_PASSES][RADIX_MAX_DIGITS]; /* k_radix_hist: words of each digit; k_radix_bases: where they start */
+  ScanControl ctl;
+};
+static_assert (sizeof (ScanControl) == 64 && RADIX_MAX_PASSES <= 15 && sizeof (RadixHead) % 8 == 0, "a ticket per pass; the states are 64-bit words");
 
 /* all passes' digit counts in one read of the words: LDS counters per block, flushed by global atomics */
 __global__ __launch_bounds__ (HIST_NT) void k_radix_hist (const u64 *__restrict__ in, u64 n, RadixPlan plan, u64 *__restrict__ ghist)
@@ -116,6 +131,66 @@ __global__ __launch_bounds__ (RADIX_MAX_DIGITS) void k_radix_bases (u64 *__restr
   row[threadIdx.x] = before + incl - v;
 }
 
+/* A tile's words as a wavefront takes them, 64 consecutive ones per round: word r of a lane is word (wid * ITEMS + r) * 64 + lane
+ * of the tile.  A range-checked descriptor over the tile's nv words: no per-lane bounds, no addresses in registers; words
+ * behind the end read as 0. */
+template <int ITEMS>
+__device__ __forceinline__ void load_tile (const u64 *__restrict__ tile_words, u32 nv, int lane, int wid, u64 (&word)[ITEMS])
+{
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc ((void *) tile_words, 0, (int) (8 * nv), 0x00020000);
+#pragma unroll
+  for (int r = 0; r < ITEMS; r++) {
+    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64 (rs, 8 * lane, 8 * WAVE * (wid * ITEMS + r), 0);
+    word[r] = (u64) v.x | ((u64) v.y << 32);
+  }
+}
+
+/* sixteen bits per round, two rounds to a register */
+__device__ __forceinline__ u32 half_of (const u32 (&a)[RADIX_ITEMS / 2], int r) { return (a[r / 2] >> (16 * (r & 1))) & 0xffffu; }
+
+/* What the tiles before `tile` hold of digit d in this pass, from their state words (ND per tile).  RADIX_LOOK earlier
+ * tiles per round trip: the states are asked for together and summed in order up to the first PREFIX (a serial walk
+ * meets ~20 AGG states per tile: 20 dependent round trips). */
+template <int ND>
+__device__ __forceinline__ u64 radix_look_back (u64 *__restrict__ state, u64 tile, u32 pass, int d, u32 *__restrict__ err, u32 spin_limit)
+{
+  const u64 mine = radix_tag (pass) >> 56;
+  auto ready = [&] (u64 v) { return (v >> 62) != 0 && ((v >> 56) & 63u) == mine; };
+  u64 excl = 0;
+  bool done = false;
+  for (u64 j = tile; !done; j -= RADIX_LOOK) {
+    u64 v[RADIX_LOOK];
+#pragma unroll
+    for (int i = 0; i < RADIX_LOOK; i++)
+      v[i] = j >= (u64) (1 + i) ? __hip_atomic_load (&state[(j - 1 - i) * ND + d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (RADIX_PREFIX | radix_tag (pass));
+#pragma unroll
+    for (int i = 0; i < RADIX_LOOK; i++) {
+      if (done) continue;
+      /* bounded: a predecessor that never publishes (a fault, a device shared with a stuck process) must
+       * not hang the sort.  The wait that gives up raises *err (the host returns GT4HIP_EHIP; the output
+       * is garbage) and goes on as if it had met a PREFIX, so its own PREFIX lets the successors drain;
+       * every other wait notices the flag at its next look. */
+      for (u32 spins = 0; !ready (v[i]);) {
+        if (++spins >= spin_limit || ((spins & 255u) == 0 && peek_u32 (err))) {
+          atomicOr (err, 1u);
+          v[i] = RADIX_PREFIX | radix_tag (pass);
+          break;
+        }
+        v[i] = __hip_atomic_load (&state[(j - 1 - i) * ND + d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      excl += v[i] & RADIX_VALUE;
+      done = (v[i] & RADIX_PREFIX) != 0;
+    }
+  }
+  return excl;
+}
+
+struct RadixTile {
+  u64 base;                   /* the tile's first word in `in` */
+  u32 nv;                     /* words in the tile */
+  u32 place[RADIX_ITEMS / 2]; /* (KEEP_PLACE) where in the sorted tile each word this lane read went: half_of (place, r) */
+};
+
 /* One pass over a digit of B = 8 or 9 bits: tile t's words go behind everything the earlier tiles hold of
  * the same digit, in the order they came (stable).  Tiles are taken by ticket, so a tile's predecessors have
  * all STARTED (a wait may only point at workgroups that run: the last workgroups of a launch are not
@@ -126,22 +201,21 @@ __global__ __launch_bounds__ (RADIX_MAX_DIGITS) void k_radix_bases (u64 *__restr
  *      counters (LDS, 16 bits) give every word its rank among the wavefront's words of that digit;
  *   3. prefix over wavefronts and digits = every word's place in the tile sorted by digit; the words go
  *      there (LDS);
- *   4. one thread per digit looks back over the earlier tiles' states (RADIX_LOOK per round trip) until it
- *      meets a PREFIX; the tile's own PREFIX is published;
- *   5. the tile leaves LDS in digit order: runs of one digit go to consecutive addresses. */
+ *   4. one thread per digit looks back over the earlier tiles' states until it meets a PREFIX; the tile's own
+ *      PREFIX is published;
+ *   5. the tile leaves LDS in digit order: runs of one digit go to consecutive addresses.
+ * radix_tile_sort is steps 1 to 4 of both scatter kernels, up to the barrier behind them: `keys` then holds the tile
+ * sorted by digit and gofs[d] the address of the tile's first word of digit d in `out`, minus its place in the sorted
+ * tile.  Only the pair kernel asks for the words' places (KEEP_PLACE): it sends the values the same way. */
 /* (cache-policy switches of the words' streaming load and scattered store, as in gt4hip_device.h) */
-/* k_radix_scatter_pairs below repeats steps 1 to 5 line by line: a change to the ranks, the look-back or its bounded
- * wait goes into both. */
-template <int B>
-__global__ __launch_bounds__ (RADIX_NT, GT4_RADIX_WAVES) void k_radix_scatter (const u64 *__restrict__ in, u64 *__restrict__ out, u64 n, u32 pass, u32 shift, const u64 *__restrict__ gbase,
-                                                                              u64 *__restrict__ state, u32 *__restrict__ ticket, u32 *__restrict__ err, u32 spin_limit)
+template <int B, bool KEEP_PLACE>
+__device__ __forceinline__ RadixTile radix_tile_sort (const u64 *__restrict__ in, u64 n, u32 pass, u32 shift, const u64 *__restrict__ gbase, u64 *__restrict__ state, u32 *__restrict__ ticket,
+                                                     u32 *__restrict__ err, u32 spin_limit, u64 (&keys)[RADIX_TILE], u64 (&gofs)[1 << B])
 {
   constexpr int ND = 1 << B, NDW = ND / WAVE; /* digits; wavefronts that own one digit per lane */
   static_assert (ND <= RADIX_NT && ND <= RADIX_MAX_DIGITS && RADIX_TILE <= 65535, "a digit per thread; 16-bit places");
-  __shared__ u64 keys[RADIX_TILE];
   __shared__ unsigned short wcnt[RADIX_NW][ND]; /* per wavefront: words of each digit so far; later: where the wavefront's words of the digit start in the sorted tile */
   __shared__ u32 hcnt[ND];          /* words of each digit in the tile */
-  __shared__ u64 gofs[ND];          /* address of the tile's first word of each digit in `out`, minus its place in the sorted tile */
   __shared__ u32 wtot[NDW];
   __shared__ u32 tile_s;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -150,18 +224,12 @@ __global__ __launch_bounds__ (RADIX_NT, GT4_RADIX_WAVES) void k_radix_scatter (c
   if (tid < ND) hcnt[tid] = 0;
   __syncthreads ();
   const u64 tile = tile_s;
-  const u64 base = tile * RADIX_TILE;
-  const u32 nv = n - base < (u64) RADIX_TILE ? (u32) (n - base) : (u32) RADIX_TILE;
+  RadixTile t;
+  t.base = tile * RADIX_TILE;
+  t.nv = n - t.base < (u64) RADIX_TILE ? (u32) (n - t.base) : (u32) RADIX_TILE;
+  const u32 nv = t.nv;
   u64 key[RADIX_ITEMS];
-  {
-    /* a range-checked descriptor over the tile: no per-lane bounds, no addresses in registers */
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc ((void *) (in + base), 0, (int) (8 * nv), 0x00020000);
-#pragma unroll
-    for (int r = 0; r < RADIX_ITEMS; r++) {
-      const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64 (rs, 8 * lane, 8 * WAVE * (wid * RADIX_ITEMS + r), 0);
-      key[r] = (u64) v.x | ((u64) v.y << 32);
-    }
-  }
+  load_tile (in + t.base, nv, lane, wid, key);
   /* what the tile holds of every digit, as early as it can be known (the stable ranks below take several
    * times as long): the later tiles look back for it */
 #pragma unroll
@@ -218,220 +286,84 @@ __global__ __launch_bounds__ (RADIX_NT, GT4_RADIX_WAVES) void k_radix_scatter (c
   for (int r = 0; r < RADIX_ITEMS; r++) {
     const u32 q = (u32) (wid * RADIX_ITEMS + r) * WAVE + (u32) lane;
     const u32 d = (u32) (key[r] >> shift) & (u32) (ND - 1);
-    if (q < nv) keys[(u32) wcnt[wid][d] + ((rk[r / 2] >> (16 * (r & 1))) & 0xffffu)] = key[r];
+    const u32 at = (u32) wcnt[wid][d] + half_of (rk, r);
+    if (q < nv) keys[at] = key[r];
+    if constexpr (KEEP_PLACE) t.place[r / 2] = (r & 1) ? t.place[r / 2] | (at << 16) : at;
   }
   /* look back: what the earlier tiles hold of digit tid */
   if (tid < ND) {
     u64 excl = 0;
     if (tile > 0) {
-      /* RADIX_LOOK earlier tiles per round trip: the states are asked for together and summed in order
-       * up to the first PREFIX (a serial walk meets ~20 AGG states per tile: 20 dependent round trips) */
-      const u64 mine = radix_tag (pass) >> 56;
-      auto ready = [&] (u64 v) { return (v >> 62) != 0 && ((v >> 56) & 63u) == mine; };
-      bool done = false;
-      for (u64 j = tile; !done; j -= RADIX_LOOK) {
-        u64 v[RADIX_LOOK];
-#pragma unroll
-        for (int i = 0; i < RADIX_LOOK; i++)
-          v[i] = j >= (u64) (1 + i) ? __hip_atomic_load (&state[(j - 1 - i) * ND + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (RADIX_PREFIX | radix_tag (pass));
-#pragma unroll
-        for (int i = 0; i < RADIX_LOOK; i++) {
-          if (done) continue;
-          /* bounded: a predecessor that never publishes (a fault, a device shared with a stuck process) must
-           * not hang the sort.  The wait that gives up raises *err (the host returns GT4HIP_EHIP; the output
-           * is garbage) and goes on as if it had met a PREFIX, so its own PREFIX lets the successors drain;
-           * every other wait notices the flag at its next look. */
-          for (u32 spins = 0; !ready (v[i]);) {
-            if (++spins >= spin_limit || ((spins & 255u) == 0 && peek_u32 (err))) {
-              atomicOr (err, 1u);
-              v[i] = RADIX_PREFIX | radix_tag (pass);
-              break;
-            }
-            v[i] = __hip_atomic_load (&state[(j - 1 - i) * ND + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-          excl += v[i] & RADIX_VALUE;
-          done = (v[i] & RADIX_PREFIX) != 0;
-        }
-      }
+      excl = radix_look_back<ND> (state, tile, pass, tid, err, spin_limit);
       __hip_atomic_store (&state[tile * ND + tid], RADIX_PREFIX | radix_tag (pass) | (excl + cnt_d), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     gofs[tid] = gbase[pass * RADIX_MAX_DIGITS + tid] + excl - ls;
   }
   __syncthreads ();
+  return t;
+}
+
+/* step 5 for word q of the sorted tile; returns the word's digit */
+template <int B>
+__device__ __forceinline__ u32 radix_word_out (const u64 (&keys)[RADIX_TILE], const u64 (&gofs)[1 << B], u64 *__restrict__ out, u32 q, u32 shift)
+{
+  const u64 k = keys[q];
+  const u32 d = (u32) (k >> shift) & (u32) ((1 << B) - 1);
+  out[gofs[d] + q] = k; /* (plain: non-temporal scattered stores measured slower, profiles/round5/r5_cache_policy.log) */
+  return d;
+}
+
+template <int B>
+__global__ __launch_bounds__ (RADIX_NT, GT4_RADIX_WAVES) void k_radix_scatter (const u64 *__restrict__ in, u64 *__restrict__ out, u64 n, u32 pass, u32 shift, const u64 *__restrict__ gbase,
+                                                                              u64 *__restrict__ state, u32 *__restrict__ ticket, u32 *__restrict__ err, u32 spin_limit)
+{
+  __shared__ u64 keys[RADIX_TILE];
+  __shared__ u64 gofs[1 << B];
+  const RadixTile t = radix_tile_sort<B, false> (in, n, pass, shift, gbase, state, ticket, err, spin_limit, keys, gofs);
 #pragma unroll
   for (int r = 0; r < RADIX_ITEMS; r++) {
-    const u32 q = (u32) r * RADIX_NT + (u32) tid;
-    if (q < nv) {
-      const u64 k = keys[q];
-      out[gofs[(u32) (k >> shift) & (u32) (ND - 1)] + q] = k; /* (plain: non-temporal scattered stores measured slower, profiles/round5/r5_cache_policy.log) */
-    }
+    const u32 q = (u32) r * RADIX_NT + threadIdx.x;
+    if (q < t.nv) radix_word_out<B> (keys, gofs, out, q, shift);
   }
 }
 
-/* The same pass over (word, value) pairs: 32 bytes moved per pair.  A sibling of k_radix_scatter and not an instantiation
- * of a shared body: with the body shared the keys-only kernel came out with other registers, and its code is to stay as
- * it is; steps 1 to 5 are the same, line by line.  The values are fetched only when the words have left LDS and take the
- * same way through the same 64 KB of it, so the kernel keeps its two workgroups per CU: what stays in registers between
- * the two rounds is each word's place in the sorted tile (16 bits, where its rank was) and the digit of the word each
- * thread wrote out (16 bits). */
+/* The same pass over (word, value) pairs: 32 bytes moved per pair.  The values are fetched only when the words have left
+ * LDS and take the same way through the same 64 KB of it, so the kernel keeps its two workgroups per CU: what stays in
+ * registers between the two rounds is each word's place in the sorted tile (16 bits, where its rank was) and the digit of
+ * the word each thread wrote out (16 bits). */
 template <int B>
 __global__ __launch_bounds__ (RADIX_NT, GT4_RADIX_WAVES) void k_radix_scatter_pairs (const u64 *__restrict__ in, u64 *__restrict__ out, const u64 *__restrict__ vin, u64 *__restrict__ vout, u64 n,
                                                                                     u32 pass, u32 shift, const u64 *__restrict__ gbase, u64 *__restrict__ state, u32 *__restrict__ ticket,
                                                                                     u32 *__restrict__ err, u32 spin_limit)
 {
-  constexpr int ND = 1 << B, NDW = ND / WAVE; /* digits; wavefronts that own one digit per lane */
-  static_assert (ND <= RADIX_NT && ND <= RADIX_MAX_DIGITS && RADIX_TILE <= 65535, "a digit per thread; 16-bit places");
   __shared__ u64 keys[RADIX_TILE];
-  __shared__ unsigned short wcnt[RADIX_NW][ND]; /* per wavefront: words of each digit so far; later: where the wavefront's words of the digit start in the sorted tile */
-  __shared__ u32 hcnt[ND];          /* words of each digit in the tile */
-  __shared__ u64 gofs[ND];          /* address of the tile's first word of each digit in `out`, minus its place in the sorted tile */
-  __shared__ u32 wtot[NDW];
-  __shared__ u32 tile_s;
+  __shared__ u64 gofs[1 << B];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  if (tid == 0) tile_s = atomicAdd (ticket, 1u);
-  for (int i = tid; i < RADIX_NW * ND / 2; i += RADIX_NT) reinterpret_cast<u32 *> (&wcnt[0][0])[i] = 0;
-  if (tid < ND) hcnt[tid] = 0;
-  __syncthreads ();
-  const u64 tile = tile_s;
-  const u64 base = tile * RADIX_TILE;
-  const u32 nv = n - base < (u64) RADIX_TILE ? (u32) (n - base) : (u32) RADIX_TILE;
-  u64 key[RADIX_ITEMS];
-  {
-    /* a range-checked descriptor over the tile: no per-lane bounds, no addresses in registers */
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc ((void *) (in + base), 0, (int) (8 * nv), 0x00020000);
-#pragma unroll
-    for (int r = 0; r < RADIX_ITEMS; r++) {
-      const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64 (rs, 8 * lane, 8 * WAVE * (wid * RADIX_ITEMS + r), 0);
-      key[r] = (u64) v.x | ((u64) v.y << 32);
-    }
-  }
-  /* what the tile holds of every digit, as early as it can be known (the stable ranks below take several
-   * times as long): the later tiles look back for it */
-#pragma unroll
-  for (int r = 0; r < RADIX_ITEMS; r++) {
-    const u32 q = (u32) (wid * RADIX_ITEMS + r) * WAVE + (u32) lane;
-    if (q < nv) atomicAdd (&hcnt[(u32) (key[r] >> shift) & (u32) (ND - 1)], 1u);
-  }
-  __syncthreads ();
-  u32 cnt_d = 0;
-  if (tid < ND) {
-    cnt_d = hcnt[tid];
-    __hip_atomic_store (&state[tile * ND + tid], (tile == 0 ? RADIX_PREFIX : RADIX_AGG) | radix_tag (pass) | (u64) cnt_d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  u32 rk[RADIX_ITEMS / 2]; /* 16 bits each */
-#pragma unroll
-  for (int r = 0; r < RADIX_ITEMS; r++) {
-    const u32 q = (u32) (wid * RADIX_ITEMS + r) * WAVE + (u32) lane;
-    const bool valid = q < nv;
-    const u32 d = (u32) (key[r] >> shift) & (u32) (ND - 1);
-    u64 m = __builtin_amdgcn_ballot_w64 (valid);
-#pragma unroll
-    for (int b = 0; b < B; b++) {
-      const u64 bal = __builtin_amdgcn_ballot_w64 ((d >> b) & 1u);
-      m &= ((d >> b) & 1u) ? bal : ~bal;
-    }
-    const u32 below = __builtin_amdgcn_mbcnt_hi ((u32) (m >> 32), __builtin_amdgcn_mbcnt_lo ((u32) m, 0u));
-    /* every lane of the group reads the counter, then its first lane adds the group (LDS executes a
-     * wavefront's accesses in order) */
-    const u32 old = valid ? wcnt[wid][d] : 0u;
-    if (valid && below == 0) wcnt[wid][d] = (unsigned short) (old + (u32) __popcll (m));
-    rk[r / 2] = (r & 1) ? rk[r / 2] | ((old + below) << 16) : old + below;
-  }
-  /* digit d = tid: its first place in the sorted tile */
-  u32 ls = 0;
-  if (tid < ND) {
-    const u32 incl = dpp_inclusive_scan_u32 (cnt_d);
-    if (lane == 63) wtot[wid] = incl;
-    ls = incl - cnt_d;
-  }
-  __syncthreads ();
-  if (tid < ND) {
-    for (int w = 0; w < wid; w++) ls += wtot[w];
-    u32 run = ls;
-#pragma unroll
-    for (int w = 0; w < RADIX_NW; w++) { /* -> where wavefront w's words of the digit start */
-      const u32 c = wcnt[w][tid];
-      wcnt[w][tid] = (unsigned short) run;
-      run += c;
-    }
-  }
-  __syncthreads ();
-  /* the tile sorted by digit, in LDS */
-#pragma unroll
-  for (int r = 0; r < RADIX_ITEMS; r++) {
-    const u32 q = (u32) (wid * RADIX_ITEMS + r) * WAVE + (u32) lane;
-    const u32 d = (u32) (key[r] >> shift) & (u32) (ND - 1);
-    const u32 place = (u32) wcnt[wid][d] + ((rk[r / 2] >> (16 * (r & 1))) & 0xffffu);
-    if (q < nv) keys[place] = key[r];
-    rk[r / 2] = (r & 1) ? (rk[r / 2] & 0xffffu) | (place << 16) : (rk[r / 2] & 0xffff0000u) | place;
-  }
-  /* look back: what the earlier tiles hold of digit tid */
-  if (tid < ND) {
-    u64 excl = 0;
-    if (tile > 0) {
-      /* RADIX_LOOK earlier tiles per round trip: the states are asked for together and summed in order
-       * up to the first PREFIX (a serial walk meets ~20 AGG states per tile: 20 dependent round trips) */
-      const u64 mine = radix_tag (pass) >> 56;
-      auto ready = [&] (u64 v) { return (v >> 62) != 0 && ((v >> 56) & 63u) == mine; };
-      bool done = false;
-      for (u64 j = tile; !done; j -= RADIX_LOOK) {
-        u64 v[RADIX_LOOK];
-#pragma unroll
-        for (int i = 0; i < RADIX_LOOK; i++)
-          v[i] = j >= (u64) (1 + i) ? __hip_atomic_load (&state[(j - 1 - i) * ND + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (RADIX_PREFIX | radix_tag (pass));
-#pragma unroll
-        for (int i = 0; i < RADIX_LOOK; i++) {
-          if (done) continue;
-          /* bounded: a predecessor that never publishes (a fault, a device shared with a stuck process) must
-           * not hang the sort.  The wait that gives up raises *err (the host returns GT4HIP_EHIP; the output
-           * is garbage) and goes on as if it had met a PREFIX, so its own PREFIX lets the successors drain;
-           * every other wait notices the flag at its next look. */
-          for (u32 spins = 0; !ready (v[i]);) {
-            if (++spins >= spin_limit || ((spins & 255u) == 0 && peek_u32 (err))) {
-              atomicOr (err, 1u);
-              v[i] = RADIX_PREFIX | radix_tag (pass);
-              break;
-            }
-            v[i] = __hip_atomic_load (&state[(j - 1 - i) * ND + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-          excl += v[i] & RADIX_VALUE;
-          done = (v[i] & RADIX_PREFIX) != 0;
-        }
-      }
-      __hip_atomic_store (&state[tile * ND + tid], RADIX_PREFIX | radix_tag (pass) | (excl + cnt_d), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    gofs[tid] = gbase[pass * RADIX_MAX_DIGITS + tid] + excl - ls;
-  }
-  __syncthreads ();
+  const RadixTile t = radix_tile_sort<B, true> (in, n, pass, shift, gbase, state, ticket, err, spin_limit, keys, gofs);
   u32 dg[RADIX_ITEMS / 2]; /* the digits of the words this thread writes out, 16 bits each */
 #pragma unroll
   for (int r = 0; r < RADIX_ITEMS; r++) {
     const u32 q = (u32) r * RADIX_NT + (u32) tid;
     if (!(r & 1)) dg[r / 2] = 0;
-    if (q < nv) {
-      const u64 k = keys[q];
-      out[gofs[(u32) (k >> shift) & (u32) (ND - 1)] + q] = k; /* (plain: non-temporal scattered stores measured slower, profiles/round5/r5_cache_policy.log) */
-      dg[r / 2] = (r & 1) ? dg[r / 2] | (((u32) (k >> shift) & (u32) (ND - 1)) << 16) : (u32) (k >> shift) & (u32) (ND - 1);
+    if (q < t.nv) {
+      const u32 d = radix_word_out<B> (keys, gofs, out, q, shift);
+      dg[r / 2] = (r & 1) ? dg[r / 2] | (d << 16) : d;
     }
   }
   /* the values: read as the words were, to the words' places in LDS, out behind the words' digits */
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc ((void *) (vin + base), 0, (int) (8 * nv), 0x00020000);
-#pragma unroll
-  for (int r = 0; r < RADIX_ITEMS; r++) {
-    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64 (rs, 8 * lane, 8 * WAVE * (wid * RADIX_ITEMS + r), 0);
-    key[r] = (u64) v.x | ((u64) v.y << 32);
-  }
+  u64 val[RADIX_ITEMS];
+  load_tile (vin + t.base, t.nv, lane, wid, val);
   __syncthreads (); /* (every word has been read out of LDS) */
 #pragma unroll
   for (int r = 0; r < RADIX_ITEMS; r++) {
     const u32 q = (u32) (wid * RADIX_ITEMS + r) * WAVE + (u32) lane;
-    if (q < nv) keys[(rk[r / 2] >> (16 * (r & 1))) & 0xffffu] = key[r];
+    if (q < t.nv) keys[half_of (t.place, r)] = val[r];
   }
   __syncthreads ();
 #pragma unroll
   for (int r = 0; r < RADIX_ITEMS; r++) {
     const u32 q = (u32) r * RADIX_NT + (u32) tid;
-    if (q < nv) vout[gofs[(dg[r / 2] >> (16 * (r & 1))) & 0xffffu] + q] = keys[q];
+    if (q < t.nv) vout[gofs[half_of (dg, r)] + q] = keys[q];
   }
 }
 
@@ -449,12 +381,7 @@ constexpr int FOLD_STRETCH = FOLD_ITEMS * WAVE; /* consecutive words of one wave
  * in memory before it; word 0 of all starts a run). */
 __device__ __forceinline__ u32 fold_heads (const u64 *__restrict__ w, u64 n, u64 base, u32 nv, int lane, int wid, u64 (&word)[FOLD_ITEMS])
 {
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc ((void *) (w + base), 0, (int) (8 * nv), 0x00020000);
-#pragma unroll
-  for (int r = 0; r < FOLD_ITEMS; r++) {
-    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64 (rs, 8 * lane, 8 * WAVE * (wid * FOLD_ITEMS + r), 0);
-    word[r] = (u64) v.x | ((u64) v.y << 32);
-  }
+  load_tile (w + base, nv, lane, wid, word);
   const u64 first = base + (u64) wid * FOLD_STRETCH;
   u64 before = 0; /* (uniform) */
   if (first > 0 && first < n) before = w[first - 1];
@@ -692,8 +619,8 @@ using namespace gt4;
 /* Sorts n 64-bit words in device memory ascending; `tmp` holds n more.  The sorted words end up in
  * `words` or in `tmp` (odd number of passes): *result says where.  `who` names the entry point in the messages.  With `vals` (and `vtmp`, n more) every word takes
  * its value along, stably: values of equal words stay in the order they came; *vresult says where they end up. */
-static int radix_sort_device (gt4hip_context *ctx, u64 *words, u64 *tmp, uint64_t n, uint32_t word_length, u64 **result, const char *who = "gt4hip_sort_words",
-                              u64 *vals = NULL, u64 *vtmp = NULL, u64 **vresult = NULL)
+static int radix_sort_device (gt4hip_context *ctx, const char *who, u64 *words, u64 *tmp, uint64_t n, uint32_t word_length, u64 **result, u64 *vals = NULL, u64 *vtmp = NULL,
+                              u64 **vresult = NULL)
 {
   *result = words;
   if (vresult) *vresult = vals;
@@ -717,37 +644,33 @@ static int radix_sort_device (gt4hip_context *ctx, u64 *words, u64 *tmp, uint64_
   const uint32_t passes = plan.passes;
   const uint64_t tiles = (n + RADIX_TILE - 1) / RADIX_TILE;
   if (tiles >= (1ull << 32)) return gt4hip_fail (ctx, GT4HIP_EINVAL, "%s: %llu words", who, (unsigned long long) n);
-  /* workspace: digit bases of every pass, a ticket per pass, the tile states */
-  const size_t head = (size_t) RADIX_MAX_PASSES * RADIX_MAX_DIGITS * 8 + 64;
-  const size_t state_bytes = (size_t) tiles * RADIX_MAX_DIGITS * 8;
-  char *ws = NULL;
+  const size_t ws_bytes = sizeof (RadixHead) + (size_t) tiles * RADIX_MAX_DIGITS * 8;
+  RadixHead *ws = NULL;
   void *ws_owner = NULL;
-  if (gt4hip_block_alloc (ctx, head + state_bytes, (void **) &ws, &ws_owner))
-    return gt4hip_fail (ctx, GT4HIP_ENOMEM, "%s: workspace of %llu bytes", who, (unsigned long long) (head + state_bytes));
-  u64 *ghist = (u64 *) ws;
-  u32 *tickets = (u32 *) (ws + (size_t) RADIX_MAX_PASSES * RADIX_MAX_DIGITS * 8);
-  u32 *err = tickets + 15; /* (the 64 bytes behind the digit bases: a ticket per pass, then the error word) */
+  if (gt4hip_block_alloc (ctx, ws_bytes, (void **) &ws, &ws_owner)) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "%s: workspace of %llu bytes", who, (unsigned long long) ws_bytes);
+  u64 *ghist = &ws->bases[0][0], *state = (u64 *) (ws + 1);
+  u32 *err = &ws->ctl.err;
   const u32 spin_limit = ctx->spin_limit ? ctx->spin_limit : SPIN_LIMIT;
-  u64 *state = (u64 *) (ws + head);
   hipStream_t st = ctx->stream;
-  hipError_t e = hipMemsetAsync (ws, 0, head + state_bytes, st);
+  hipError_t e = hipMemsetAsync (ws, 0, ws_bytes, st);
   u64 hb = (n + (u64) HIST_NT * HIST_ITEMS - 1) / ((u64) HIST_NT * HIST_ITEMS);
   if (hb > (u64) ctx->n_cus * 8) hb = (u64) ctx->n_cus * 8;
   hipLaunchKernelGGL (k_radix_hist, dim3 ((unsigned) hb), dim3 (HIST_NT), 0, st, words, n, plan, ghist);
   hipLaunchKernelGGL (k_radix_bases, dim3 (passes), dim3 (RADIX_MAX_DIGITS), 0, st, ghist);
   u64 *src = words, *dst = tmp, *vsrc = vals, *vdst = vtmp;
   for (uint32_t p = 0; p < passes; p++) {
-    if (vals) {
-      if (plan.bits[p] == 9)
-        hipLaunchKernelGGL (k_radix_scatter_pairs<9>, dim3 ((unsigned) tiles), dim3 (RADIX_NT), 0, st, src, dst, vsrc, vdst, n, p, plan.shift[p], ghist, state, tickets + p, err, spin_limit);
-      else
-        hipLaunchKernelGGL (k_radix_scatter_pairs<8>, dim3 ((unsigned) tiles), dim3 (RADIX_NT), 0, st, src, dst, vsrc, vdst, n, p, plan.shift[p], ghist, state, tickets + p, err, spin_limit);
-      std::swap (vsrc, vdst);
-    } else if (plan.bits[p] == 9) hipLaunchKernelGGL (k_radix_scatter<9>, dim3 ((unsigned) tiles), dim3 (RADIX_NT), 0, st, src, dst, n, p, plan.shift[p], ghist, state, tickets + p, err, spin_limit);
-    else hipLaunchKernelGGL (k_radix_scatter<8>, dim3 ((unsigned) tiles), dim3 (RADIX_NT), 0, st, src, dst, n, p, plan.shift[p], ghist, state, tickets + p, err, spin_limit);
-    u64 *const t = src;
-    src = dst;
-    dst = t;
+    /* one pass: the kernel for its digit width, with or without the values */
+    auto scatter = [&] (auto width) {
+      constexpr int B = decltype (width)::value;
+      const dim3 grid ((unsigned) tiles), block (RADIX_NT);
+      u32 *ticket = &ws->ctl.ticket[p];
+      if (vals) hipLaunchKernelGGL (k_radix_scatter_pairs<B>, grid, block, 0, st, src, dst, vsrc, vdst, n, p, plan.shift[p], ghist, state, ticket, err, spin_limit);
+      else hipLaunchKernelGGL (k_radix_scatter<B>, grid, block, 0, st, src, dst, n, p, plan.shift[p], ghist, state, ticket, err, spin_limit);
+    };
+    if (plan.bits[p] == 9) scatter (std::integral_constant<int, 9> ());
+    else scatter (std::integral_constant<int, 8> ());
+    std::swap (src, dst);
+    std::swap (vsrc, vdst);
   }
   if (e == hipSuccess) e = hipGetLastError ();
   if (e == hipSuccess) e = hipMemcpyAsync (ctx->scratch_host, err, 4, hipMemcpyDeviceToHost, st);
@@ -760,23 +683,46 @@ static int radix_sort_device (gt4hip_context *ctx, u64 *words, u64 *tmp, uint64_
   return GT4HIP_OK;
 }
 
+/* gt4hip_sort_words, and with `device_values` gt4hip_sort_pairs: the sort in place.  The scratch holds what the passes
+ * alternate with; after an odd number of passes the result lies there and is copied back.  The pair sort reports its time
+ * without that copy (ctx->sort_ms); the word sort reports none and leaves the events alone: they cost a call of 3.3 ms
+ * (1e8 words) 17 us. */
+static int sort_in_place (gt4hip_context *ctx, const char *who, void *device_words, void *device_values, uint64_t n, uint32_t word_length)
+{
+  HIPCHK (ctx, hipSetDevice (ctx->device));
+  if (n < 2) return GT4HIP_OK;
+  const size_t stream_bytes = (size_t) n * 8, scratch_bytes = device_values ? 2 * stream_bytes : stream_bytes;
+  u64 *tmp = NULL;
+  void *tmp_owner = NULL;
+  if (gt4hip_block_alloc (ctx, scratch_bytes, (void **) &tmp, &tmp_owner)) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "%s: %llu bytes of scratch", who, (unsigned long long) scratch_bytes);
+  u64 *res = NULL, *vres = NULL;
+  if (device_values) hipEventRecord (ctx->ev[0], ctx->stream);
+  int rc = radix_sort_device (ctx, who, (u64 *) device_words, tmp, n, word_length, &res, (u64 *) device_values, device_values ? tmp + n : NULL, &vres);
+  if (device_values) hipEventRecord (ctx->ev[1], ctx->stream);
+  if (!rc && res != (u64 *) device_words) {
+    hipError_t e = hipMemcpyAsync (device_words, res, stream_bytes, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess && device_values) e = hipMemcpyAsync (device_values, vres, stream_bytes, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e != hipSuccess) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "%s: %s", who, hipGetErrorString (e));
+  }
+  hipError_t e = hipStreamSynchronize (ctx->stream);
+  if (!rc && e != hipSuccess) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "%s: %s", who, hipGetErrorString (e));
+  float ms = 0;
+  if (device_values && hipEventElapsedTime (&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->sort_ms = ms;
+  gt4hip_block_free (tmp_owner);
+  return rc;
+}
+
 extern "C" int gt4hip_sort_words (gt4hip_context *ctx, void *device_words, uint64_t n_words, uint32_t word_length)
 {
   if (!ctx || (n_words && !device_words) || !word_length || word_length > 32) return GT4HIP_EINVAL;
-  HIPCHK (ctx, hipSetDevice (ctx->device));
-  if (n_words < 2) return GT4HIP_OK;
-  u64 *tmp = NULL;
-  void *tmp_owner = NULL;
-  if (gt4hip_block_alloc (ctx, (size_t) n_words * 8, (void **) &tmp, &tmp_owner)) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_sort_words: %llu bytes of scratch", (unsigned long long) n_words * 8);
-  u64 *res = NULL;
-  int rc = radix_sort_device (ctx, (u64 *) device_words, tmp, n_words, word_length, &res);
-  if (!rc && res != (u64 *) device_words) {
-    hipError_t e = hipMemcpyAsync (device_words, res, (size_t) n_words * 8, hipMemcpyDeviceToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize (ctx->stream);
-    if (e != hipSuccess) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_sort_words: %s", hipGetErrorString (e));
-  }
-  gt4hip_block_free (tmp_owner);
-  return rc;
+  return sort_in_place (ctx, "gt4hip_sort_words", device_words, NULL, n_words, word_length);
+}
+
+/* (word, value) pairs: glistmaker --index */
+extern "C" int gt4hip_sort_pairs (gt4hip_context *ctx, void *device_words, void *device_values, uint64_t n_pairs, uint32_t word_length)
+{
+  if (!ctx || (n_pairs && (!device_words || !device_values)) || !word_length || word_length > 32) return GT4HIP_EINVAL;
+  return sort_in_place (ctx, "gt4hip_sort_pairs", device_words, device_values, n_pairs, word_length);
 }
 
 /* sorted device words -> list of (word, occurrences) */
@@ -788,17 +734,17 @@ static int fold_sorted_words (gt4hip_context *ctx, const u64 *words, uint64_t n_
   hipError_t e;
   const uint64_t tiles = (n_words + FOLD_TILE - 1) / FOLD_TILE;
   if (tiles >= (1ull << 32)) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_words_to_list: %llu words", (unsigned long long) n_words);
-  /* workspace: ticket, tile states, runs before every tile (+ the total) */
-  char *ws = NULL;
+  /* workspace: control words, tile states, runs before every tile (+ the total) */
+  ScanControl *ws = NULL;
   void *ws_owner = NULL;
-  const size_t bytes = 64 + (size_t) tiles * 8 + (size_t) (tiles + 1) * 8;
+  const size_t cleared = sizeof (ScanControl) + (size_t) tiles * 8, bytes = cleared + (size_t) (tiles + 1) * 8;
   if (gt4hip_block_alloc (ctx, bytes, (void **) &ws, &ws_owner)) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_words_to_list: workspace");
-  u64 *state = (u64 *) (ws + 64), *tile_excl = state + tiles;
-  e = hipMemsetAsync (ws, 0, 64 + (size_t) tiles * 8, st);
-  hipLaunchKernelGGL (k_fold_count, dim3 ((unsigned) tiles), dim3 (FOLD_NT), 0, st, words, n_words, state, tile_excl, tiles, (u32 *) ws, ctx->scratch, (u32 *) ws + 15,
+  u64 *state = (u64 *) (ws + 1), *tile_excl = state + tiles;
+  e = hipMemsetAsync (ws, 0, cleared, st);
+  hipLaunchKernelGGL (k_fold_count, dim3 ((unsigned) tiles), dim3 (FOLD_NT), 0, st, words, n_words, state, tile_excl, tiles, &ws->ticket[0], ctx->scratch, &ws->err,
                       ctx->spin_limit ? ctx->spin_limit : SPIN_LIMIT);
   if (e == hipSuccess) e = hipMemcpyAsync (ctx->scratch_host, ctx->scratch, 8, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync (ctx->scratch_host + 1, (u32 *) ws + 15, 4, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync (ctx->scratch_host + 1, &ws->err, 4, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize (st);
   if (e != hipSuccess) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_words_to_list: %s", hipGetErrorString (e));
   else if ((u32) ctx->scratch_host[1]) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_words_to_list: a chained-scan wait gave up (device shared with a stuck workgroup?)");
@@ -834,7 +780,7 @@ extern "C" int gt4hip_device_words_to_list (gt4hip_context *ctx, void *device_wo
     return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_device_words_to_list: %llu bytes of scratch", (unsigned long long) n_words * 8);
   hipEventRecord (ctx->ev[0], ctx->stream);
   u64 *res = NULL;
-  int rc = radix_sort_device (ctx, (u64 *) device_words, tmp, n_words, word_length, &res);
+  int rc = radix_sort_device (ctx, "gt4hip_sort_words", (u64 *) device_words, tmp, n_words, word_length, &res);
   hipEventRecord (ctx->ev[1], ctx->stream);
   /* (the words are the caller's scratch from here on: sorted in place or not, they are folded from wherever the last pass left them) */
   if (!rc) rc = fold_sorted_words (ctx, res, n_words, word_length, out);
@@ -863,33 +809,7 @@ extern "C" int gt4hip_words_to_list (gt4hip_context *ctx, const uint64_t *host_w
   return rc;
 }
 
-/* ---- (word, value) pairs: glistmaker --index */
-
-extern "C" int gt4hip_sort_pairs (gt4hip_context *ctx, void *device_words, void *device_values, uint64_t n_pairs, uint32_t word_length)
-{
-  if (!ctx || (n_pairs && (!device_words || !device_values)) || !word_length || word_length > 32) return GT4HIP_EINVAL;
-  HIPCHK (ctx, hipSetDevice (ctx->device));
-  if (n_pairs < 2) return GT4HIP_OK;
-  u64 *tmp = NULL;
-  void *tmp_owner = NULL;
-  if (gt4hip_block_alloc (ctx, (size_t) n_pairs * 16, (void **) &tmp, &tmp_owner))
-    return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_sort_pairs: %llu bytes of scratch", (unsigned long long) n_pairs * 16);
-  u64 *res = NULL, *vres = NULL;
-  hipEventRecord (ctx->ev[0], ctx->stream);
-  int rc = radix_sort_device (ctx, (u64 *) device_words, tmp, n_pairs, word_length, &res, "gt4hip_sort_pairs", (u64 *) device_values, tmp + n_pairs, &vres);
-  hipEventRecord (ctx->ev[1], ctx->stream);
-  if (!rc && res != (u64 *) device_words) { /* (an odd number of passes: both streams lie in the scratch) */
-    hipError_t e = hipMemcpyAsync (device_words, res, (size_t) n_pairs * 8, hipMemcpyDeviceToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync (device_values, vres, (size_t) n_pairs * 8, hipMemcpyDeviceToDevice, ctx->stream);
-    if (e != hipSuccess) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_sort_pairs: %s", hipGetErrorString (e));
-  }
-  hipError_t e = hipStreamSynchronize (ctx->stream);
-  if (!rc && e != hipSuccess) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_sort_pairs: %s", hipGetErrorString (e));
-  float ms = 0;
-  if (hipEventElapsedTime (&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->sort_ms = ms;
-  gt4hip_block_free (tmp_owner);
-  return rc;
-}
+/* ---- the table step of a location index: glistmaker --index */
 
 /* The k-mer section of an index is a pooled block that the context owns, as the words of gt4hip_text_to_words are: one at a time. */
 extern "C" void gt4hip_index_free (gt4hip_context *ctx)

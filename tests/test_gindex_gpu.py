@@ -3,7 +3,8 @@
 GT4I file, reference src/glistmaker.c:425-574), against numpy and against the reference's own index files.
 
 Sizes: 20,001 pairs are two full 8192-pair tiles of the scatter kernel and a partial third, so the chained scan over
-tiles and the bounds of the last tile both take part; the fold's tiles are 8192 words, the index kernels' 1024 records.
+tiles and the bounds of the last tile both take part; 8192 and 16,384 end with a full tile (one tile: no look-back at
+all); the fold's tiles are 8192 words, the index kernels' 1024 records.
 Word lengths: ceil (2k / 9) passes, so k = 2, 11 end in the scratch buffers (1 and 3 passes: copied back) and k = 9, 25,
 32 in place (2, 6, 8 passes); k = 25 and 32 take 9-bit digits, k = 32 every bit of the word."""
 import hashlib
@@ -50,15 +51,16 @@ def spread_keys(k, n_distinct, rng):
     return keys
 
 
-@pytest.mark.parametrize("k", [2, 9, 11, 25, 32])
-def test_pair_sort_is_stable_with_sixteen_keys(ctx, k):
+@pytest.mark.parametrize("k,n", [pytest.param(k, N, id=str(k)) for k in (2, 9, 11, 25, 32)]
+                         + [pytest.param(k, n, id="%d-%d" % (k, n)) for k in (9, 11) for n in (8192, 16384)])  # full last tiles: in place, copied back
+def test_pair_sort_is_stable_with_sixteen_keys(ctx, k, n):
     """value = where the pair stood in the input: after a stable sort the values ascend within every word, and together
     with the words they are exactly numpy's stable argsort"""
     rng = np.random.default_rng(k)
-    words = spread_keys(k, 16, rng)[rng.integers(0, 16, size=N)]
-    values = np.arange(N, dtype=np.uint64)
+    words = spread_keys(k, 16, rng)[rng.integers(0, 16, size=n)]
+    values = np.arange(n, dtype=np.uint64)
     w, v = on_device(words), on_device(values)
-    ctx.sort_pairs(w.data_ptr(), v.data_ptr(), N, k)
+    ctx.sort_pairs(w.data_ptr(), v.data_ptr(), n, k)
     order = np.argsort(words, kind="stable")
     assert back(w).tolist() == words[order].tolist()
     assert back(v).tolist() == order.tolist()
@@ -83,6 +85,17 @@ def test_pair_sort_of_nothing_and_of_one(ctx, n):
     assert back(w).tolist() == [7] * max(n, 1) and back(v).tolist() == [9] * max(n, 1)
     kmers, n_locations, locs = ctx.pairs_to_index(w.data_ptr(), v.data_ptr(), n, 16)
     assert kmers.tolist() == [[7, 0]] * n and n_locations == n and locs.tolist() == [9] * n
+
+
+@pytest.mark.parametrize("n,k", [(N, 2), (N, 11), (N, 9), (0, 16), (1, 16)])
+def test_word_sort_against_numpy(ctx, n, k):
+    """gt4hip_sort_words sorts in place: after 1 and 3 passes (k = 2, 11) the words come back from the scratch, after 2
+    (k = 9) they lie in place; nothing and one word are left as they are"""
+    rng = np.random.default_rng(200 + k)
+    words = rng.integers(0, 1 << (2 * k), size=max(n, 1), dtype=np.uint64)
+    w = on_device(words)
+    ctx.sort_words(w.data_ptr(), n, k)
+    assert back(w).tolist() == (np.sort(words) if n else words).tolist()
 
 
 def expected_index(words, values, lo, hi):
