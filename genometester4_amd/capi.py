@@ -84,6 +84,13 @@ class IndexArrays(C.Structure):
                 ("d_kmers", C.c_void_p), ("d_locations", C.c_void_p)]
 
 
+class SubsetParams(C.Structure):
+    _fields_ = [("method", C.c_uint32), ("size", C.c_uint64), ("state48", C.c_uint64)]
+
+
+SUBSET_RAND, SUBSET_RAND_UNIQUE, SUBSET_RAND_WEIGHTED_UNIQUE = 0, 1, 2
+
+
 class MultiResult(C.Structure):
     _fields_ = [("n_words", C.c_uint64), ("total_count", C.c_uint64), ("out", C.c_void_p), ("device_ms", C.c_double),
                 ("records_read", C.c_uint64), ("records_written", C.c_uint64)]
@@ -114,6 +121,7 @@ SYMBOLS = [
     "gt4hip_query_lookup_locations", "gt4hip_query_index_gather_ms",
     "gt4hip_text_to_words", "gt4hip_words_free", "gt4hip_words_download", "gt4hip_text_to_list",
     "gt4hip_sort_pairs", "gt4hip_pairs_to_index", "gt4hip_index_free",
+    "gt4hip_list_subset", "gt4hip_subset_state_at",
     "gt4hip_text_to_locations", "gt4hip_locations_free", "gt4hip_pack_locations", "gt4hip_pairs_reserve", "gt4hip_pairs_release",
 ]
 
@@ -224,6 +232,8 @@ def lib():
             "gt4hip_pack_locations": (C.c_int, [vp, vp, u64, u64, C.c_uint, C.c_uint]),
             "gt4hip_pairs_reserve": (C.c_int, [vp, u64, C.POINTER(vp), C.POINTER(vp)]),
             "gt4hip_pairs_release": (None, [vp]),
+            "gt4hip_list_subset": (C.c_int, [vp, vp, C.POINTER(SubsetParams), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]),
+            "gt4hip_subset_state_at": (u64, [u64, u64]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -340,6 +350,11 @@ class DeviceList:
             self.free()
         except Exception:
             pass
+
+
+def subset_state_at(state48, position) -> int:
+    """drand48's state `position` steps behind `state48` by the library's jump-ahead table (no device needed)."""
+    return lib().gt4hip_subset_state_at(state48, position)
 
 
 def query_variants(word_length, n_mm, pm_3=0) -> int:
@@ -738,6 +753,12 @@ class Context:
                       level_ms=[st.level_ms[i] for i in range(n)], level_words=[st.level_words[i] for i in range(n)],
                       level_probes=[st.level_probes[i] for i in range(n)], probes=st.probes)
         return stats, lists, timing
+
+    def subset(self, lst: DeviceList, method, size, state48):
+        """glistcompare --subset on a resident list: (n_words, total_count, DeviceList) (gt4hip_list_subset)."""
+        prm, h, n, t = SubsetParams(method, size, state48), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        self._chk(lib().gt4hip_list_subset(self.h, lst.h, C.byref(prm), C.byref(h), C.byref(n), C.byref(t)))
+        return n.value, t.value, DeviceList(self, h)
 
     def _multi(self, fn, lists, cutoff, rule, count_override, count_only, out=None):
         arr = (C.c_void_p * len(lists))(*[l.h for l in lists])

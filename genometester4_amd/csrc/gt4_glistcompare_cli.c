@@ -7,8 +7,13 @@
  * as the reference's main() (reference src/glistcompare.c:84-429, naming :814-834, :907-953).
  * Deliberate differences, all loud:
  *   - a file that cannot be opened is an error message + exit 1 (the reference dereferences NULL);
- *   - --subset is outside the GPU path: error + exit 1 (GT4I index inputs are read as the sorted
- *     k-mer lists they contain, as in the reference);
+ *   - --subset METHOD SIZE (gt4hip_list_subset: the reference's serial selection solved as a fixed point on the GPU, the
+ *     same list for the same --seed) runs on one GPU with the list resident, like -mm: --gpus N > 1 or GT4HIP_HBM_LIMIT
+ *     are an error + exit 1.  Where fewer than SIZE items are selected behind the last one (rand with SIZE above the sum
+ *     of the counts, a rand_weighted_unique walk that falls short) the reference does not terminate: here that is
+ *     "Error: ..." with the method, SIZE and the number reached, exit 1 and no output file.  A rename that fails is
+ *     exit 1 (the reference reports it and exits 0).  GT4I index inputs are read as the sorted k-mer lists they
+ *     contain, as in the reference;
  *   - -mm N (difference up to N mismatches, gt4hip_compare_mismatch) runs on one GPU with both lists
  *     resident: with --gpus N > 1 or GT4HIP_HBM_LIMIT it is an error + exit 1, and inputs that do not fit
  *     the device memory are an out-of-memory error, not a chunked run.  An empty lookup list holds no
@@ -39,6 +44,7 @@
 #include <string.h>
 #include <sys/stat.h>
 #include <sys/time.h>
+#include <time.h>
 #include <unistd.h>
 
 #include "gt4_cli.h"
@@ -49,9 +55,10 @@
 #define MAX_FILES 1024
 
 /* Weak: the product links libgt4hip.so, which defines both; the host-only sanitizer build of this file
- * (tests/harness, a CPU stand-in for the device layer) has no -mm path and leaves them NULL. */
+ * (tests/harness, a CPU stand-in for the device layer) has no -mm and no --subset path and leaves them NULL. */
 #pragma weak gt4hip_compare_mismatch
 #pragma weak gt4hip_mismatch_stats_get
+#pragma weak gt4hip_list_subset
 
 enum { OPT_PLAIN, OPT_VERSION, OPT_HELP, OPT_OUT, OPT_CUTOFF, OPT_MM, OPT_UNION, OPT_INTRSEC, OPT_DIFF, OPT_DDIFF, OPT_DU,
        OPT_COUNT_ONLY, OPT_RULE, OPT_SUBSET, OPT_SEED, OPT_PRINT_OP, OPT_NOSCOUTS, OPT_STREAM, OPT_DEBUG, OPT_GPUS };
@@ -113,6 +120,10 @@ typedef struct {
   int rule;
   unsigned int cutoff, nmm, count_override;
   int find_union, find_intrsec, find_diff, find_ddiff, find_subset, subtraction, countonly, print_operation, debug;
+  const char *subset_method_name;
+  uint32_t subset_method;         /* GT4HIP_SUBSET_* */
+  unsigned long long subset_size; /* as the reference holds it: strtoll into an unsigned long long */
+  long seed;                      /* --seed; -1 (also when given): the start time */
   const char *outputname;
   /* environment */
   int n_gpus;         /* GT4HIP_GPUS, or --gpus N */
@@ -143,6 +154,7 @@ static void parse_argv (int argc, const char *argv[], Options *o)
   o->cutoff = 1;
   o->count_override = 1;
   o->outputname = "out";
+  o->seed = -1;
   for (int i = 1; i < argc; i++) {
     const char *arg = argv[i];
     if (arg[0] != '-') {
@@ -222,10 +234,14 @@ static void parse_argv (int argc, const char *argv[], Options *o)
         o->find_subset = 1;
         i += 1;
         if (i >= argc) print_help (1);
-        if (strcmp (argv[i], "rand") && strcmp (argv[i], "rand_unique") && strcmp (argv[i], "rand_weighted_unique")) print_help (1);
+        if (!strcmp (argv[i], "rand")) o->subset_method = GT4HIP_SUBSET_RAND;
+        else if (!strcmp (argv[i], "rand_unique")) o->subset_method = GT4HIP_SUBSET_RAND_UNIQUE;
+        else if (!strcmp (argv[i], "rand_weighted_unique")) o->subset_method = GT4HIP_SUBSET_RAND_WEIGHTED_UNIQUE;
+        else print_help (1);
+        o->subset_method_name = argv[i];
         i += 1;
         if (i >= argc) print_help (1);
-        (void) strtoll (argv[i], &end, 10);
+        o->subset_size = (unsigned long long) strtoll (argv[i], &end, 10);
         if (*end != 0) {
           fprintf (stderr, "Error: Invalid subset size: %s! Must be an integer.\n", argv[i]);
           print_help (1);
@@ -234,7 +250,8 @@ static void parse_argv (int argc, const char *argv[], Options *o)
       case OPT_SEED:
         i += 1;
         if (i >= argc) print_help (1);
-        break; /* only --subset draws random numbers */
+        o->seed = (long) strtoll (argv[i], &end, 10); /* only --subset draws random numbers */
+        break;
       case OPT_PRINT_OP: o->print_operation = 1; break;
       case OPT_NOSCOUTS: break;
       case OPT_STREAM: stream = 1; break;
@@ -301,10 +318,6 @@ static unsigned int open_inputs (const Options *o, GT4ListFile *files)
 /* validity checks, in the reference's order (:317-352) */
 static void validate (Options *o)
 {
-  if (o->find_subset) {
-    fprintf (stderr, "Error: --subset is not part of the GPU set-operation path\n");
-    exit (1);
-  }
   if (o->nfiles < 2) {
     fprintf (stderr, "Error: At least 2 list/index files are needed\n");
     exit (1);
@@ -534,7 +547,56 @@ static int run_multi (const Options *o, const GT4ListFile *files, unsigned int w
   return v;
 }
 
-/* ---- the three execution paths */
+/* ---- the execution paths */
+
+/* X0 of drand48's generator behind the reference's srand48 (reference :237-241; glibc: the low 32 bits of the seed above
+ * 0x330E); no --seed, or --seed -1: the start time */
+static uint64_t subset_state48 (long seed)
+{
+  const uint32_t low = seed == -1 ? (uint32_t) (unsigned int) time (NULL) : (uint32_t) (unsigned long) seed;
+  return ((uint64_t) low << 16) | 0x330Eull;
+}
+
+/* subset (reference :292-315, :719-787): one list, SIZE of its records or occurrences selected at random */
+static int run_subset (const Options *o, GT4ListFile *files, unsigned int wlen)
+{
+  if (o->nfiles != 1) {
+    fprintf (stderr, "Error: Subsetting multiple files is not supported\n");
+    exit (1);
+  }
+  const unsigned long long num_words = files[0].header.n_words;
+  if (o->subset_method != GT4HIP_SUBSET_RAND && o->subset_size > num_words) {
+    fprintf (stderr, "Error: Unique subset size (%llu) is bigger than number of unique kmers (%llu)\n", o->subset_size, num_words);
+    exit (1);
+  }
+  if (o->n_gpus > 1 || o->hbm_limit) {
+    fprintf (stderr, "Error: --subset needs the list resident on one GPU: it cannot be combined with %s\n",
+             o->n_gpus > 1 ? "--gpus N > 1 (GT4HIP_GPUS)" : "GT4HIP_HBM_LIMIT");
+    return 1;
+  }
+  if (!gt4hip_list_subset) {
+    fprintf (stderr, "Error: this build has no --subset path\n");
+    return 1;
+  }
+  gt4hip_context *ctx = create_context (o);
+  gt4hip_list *lists[1];
+  upload_inputs (o, ctx, files, wlen, lists);
+  const gt4hip_subset_params prm = { .method = o->subset_method, .size = o->subset_size, .state48 = subset_state48 (o->seed) };
+  gt4hip_list *result = NULL;
+  uint64_t n_words = 0, total_count = 0;
+  if (gt4hip_list_subset (ctx, lists[0], &prm, &result, &n_words, &total_count)) {
+    fprintf (stderr, "Error: %s\n", gt4hip_last_error (ctx));
+    release (o, files, lists, ctx);
+    return 1;
+  }
+  char name[2048];
+  snprintf (name, sizeof name, "%s_subset_%u.list", o->outputname, wlen);
+  /* fopen (.., "w") in the reference: mode 0666 minus umask */
+  const int bad = gt4_cli_write_list_file (ctx, result, wlen, n_words, total_count, name, 0666, "Error: ");
+  gt4hip_list_free (result);
+  release (o, files, lists, ctx);
+  return bad ? 1 : 0;
+}
 
 /* compare_wordmaps_mm (reference :958-1093): two lists, diff1 and / or diff2 up to nmm mismatches */
 static int run_mismatch (const Options *o, GT4ListFile *files, unsigned int wlen)
@@ -702,6 +764,7 @@ int main (int argc, const char *argv[])
   read_environment (&o);
   parse_argv (argc, argv, &o); /* --gpus N overrides GT4HIP_GPUS */
   const unsigned int wlen = open_inputs (&o, files);
+  if (o.find_subset) return run_subset (&o, files, wlen); /* before the two-file checks, as in the reference (:292-315) */
   validate (&o);
   if (o.nmm) return run_mismatch (&o, files, wlen);
   gt4hip_context *ctx = resident_context (&o, files); /* run_resident owns it from here and destroys it */

@@ -207,6 +207,9 @@ extern "C" int gt4hip_get_counter (gt4hip_context *ctx, const char *name, uint64
   else if (!strcmp (name, "query_wide")) *value = ctx->query_wide;
   else if (!strcmp (name, "mm_wide_levels")) *value = ctx->mm_wide_levels;
   else if (!strcmp (name, "mm_unskipped_levels")) *value = ctx->mm_unskipped_levels;
+  else if (!strcmp (name, "subset_passes")) *value = ctx->subset_passes;
+  else if (!strcmp (name, "subset_tile")) *value = GT4HIP_SUBSET_TILE;
+  else if (!strcmp (name, "subset_us")) *value = (uint64_t) (ctx->subset_ms * 1000.0);
   else return gt4hip_fail (ctx, GT4HIP_EINVAL, "unknown counter %s", name);
   return GT4HIP_OK;
 }

@@ -78,6 +78,8 @@ struct gt4hip_context {
   uint64_t mm_wide_levels;      /* counter "mm_wide_levels": its levels, both sides added, that ran the 64-bit unranking (k_level<true>) */
   uint64_t mm_unskipped_levels; /* counter "mm_unskipped_levels": ... that ran without the early exit (early == 0) */
   uint64_t query_wide;          /* counter "query_wide": the last gt4hip_query_lookup launched k_query<true> */
+  uint64_t subset_passes;       /* counter "subset_passes": passes of the last gt4hip_list_subset (gt4hip_subset.hip) */
+  double subset_ms;             /* counter "subset_us": its kernels (HIP events) */
   char err[512];
   char info[256];
 };
@@ -175,6 +177,8 @@ void *gt4hip_table_padded_bases (gt4hip_count_table *table);
 void gt4hip_io_destroy (gt4hip_context *ctx);
 /* bytes of text, and codes, per tile of gt4hip_maker.hip's kernels (counters "maker_text_tile", "maker_code_tile") */
 #define GT4HIP_MAKER_TILE 4096u
+/* items per tile of gt4hip_subset.hip's decision kernels (counter "subset_tile") */
+#define GT4HIP_SUBSET_TILE 4096u
 int gt4hip_io_download (gt4hip_context *ctx, const void *dev, void *host, size_t bytes);
 /* host memory (a file mapping, say) -> device memory, waited for: large extents in pieces through the staging threads */
 int gt4hip_io_upload (gt4hip_context *ctx, const void *host, void *dev, size_t bytes);

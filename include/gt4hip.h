@@ -317,6 +317,35 @@ int gt4hip_list_count_histogram (gt4hip_context *ctx, const gt4hip_list *list, u
 /* Sum over the records of count x (G and C bases of the word). */
 int gt4hip_list_gc (gt4hip_context *ctx, const gt4hip_list *list, uint64_t *weighted_gc_bases);
 
+/* ---------------------------------------------------------------- (ii d) glistcompare --subset: random subsets */
+
+/* The three methods of subset () (src/glistcompare.c:719-787).  The ITEMS the reference walks are the records of the
+ * list (rand_unique, rand_weighted_unique) or their occurrences (rand: record i is count_i items). */
+enum { GT4HIP_SUBSET_RAND = 0, GT4HIP_SUBSET_RAND_UNIQUE = 1, GT4HIP_SUBSET_RAND_WEIGHTED_UNIQUE = 2 };
+typedef struct {
+  uint32_t method;    /* GT4HIP_SUBSET_*                                                                        */
+  uint64_t size;      /* SIZE: items to select                                                                  */
+  uint64_t state48;   /* X0 of drand48's generator: srand48 (seed) sets ((uint32_t) seed << 16) | 0x330E        */
+} gt4hip_subset_params;
+
+/* The list the reference writes for the same list, method, SIZE and generator state, record for record: item i is
+ * selected iff fewer than SIZE items were selected before it and draw i of drand48 is <= (double) out / in
+ * (rand_weighted_unique: (double) count * out / in), evaluated in IEEE double as the C expression stands.  The serial
+ * walk is solved as a fixed point on the device; the input is only read.  *out is a new list (the
+ * caller's, gt4hip_list_free) with *n_words records whose counts add up to *total_count; for rand a record carries the
+ * number of its selected occurrences.  SIZE 0 or an empty list give an empty list.  Where fewer than SIZE items are
+ * selected behind the last item (rand with SIZE above the sum of the counts, the unique methods with SIZE above the
+ * number of records, a rand_weighted_unique walk that falls short) the reference does not terminate or writes the last
+ * record twice: here that is GT4HIP_EINVAL, the message names the method, SIZE and the number reached, and no list is
+ * made.  Device memory, all sized from the call: 8 bytes per record (not for rand_unique), 24 bytes per tile of
+ * "subset_tile" items, for rand 12 more bytes per record; GT4HIP_ENOMEM when that does not fit -- nothing is chunked.
+ * Counters: "subset_passes", "subset_tile", "subset_us". */
+int gt4hip_list_subset (gt4hip_context *ctx, const gt4hip_list *list, const gt4hip_subset_params *params,
+                        gt4hip_list **out, uint64_t *n_words, uint64_t *total_count);
+/* The generator's state `position` steps behind state48, by the jump-ahead table the kernels' threads start from
+ * (48 affine maps, one per power of two; host code, no device needed).  Draw i of drand48 is (the state at position i + 1) / 2^48. */
+uint64_t gt4hip_subset_state_at (uint64_t state48, uint64_t position);
+
 /* ---------------------------------------------------------------- (iii) N-way operations */
 
 typedef struct {
@@ -629,7 +658,10 @@ int gt4hip_set_option (gt4hip_context *ctx, const char *name, int64_t value);
  * "maker_code_tile": bytes of text, and codes (one per text byte >= ' '), per tile of that call's kernels;
  * "query_wide": 1 when the context's last gt4hip_query_lookup ran the kernel with 64-bit variant ranks, else 0;
  * "mm_wide_levels": levels of the last gt4hip_compare_mismatch, both tables added, run with 64-bit variant ranks;
- * "mm_unskipped_levels": levels of it run without the early exit of decided words (more than 2^32 - 1 variants a word, no subtract). */
+ * "mm_unskipped_levels": levels of it run without the early exit of decided words (more than 2^32 - 1 variants a word, no subtract);
+ * "subset_passes": passes of the last gt4hip_list_subset until a scan changed no tile's carry-in (0: it had nothing to walk);
+ * "subset_tile": items per tile of its kernels; "subset_us": its device time (HIP events around the kernels, the one
+ * word read back per pass included). */
 int gt4hip_get_counter (gt4hip_context *ctx, const char *name, uint64_t *value);
 
 #ifdef __cplusplus
