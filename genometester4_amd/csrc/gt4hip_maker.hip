@@ -23,6 +23,10 @@
  *   k_mk_emit<1>     the words (forward word masked to 2k bits, reverse complement rolled as :233-234, the smaller of the
  *                    two unless FORWARD_ONLY), staged in LDS and written out in order
  *
+ * What sibling kernels share is written once, as inline functions: tile_head (the reader's state at a thread's first byte:
+ * k_mk_codes, k_mk_events), load_word_ends and for_each_word (where words end, and the walk over them: k_mk_emit,
+ * k_mk_emit_loc), block_scan (all of them and k_mk_summary).  The host half is one MakerCall handed through stages.
+ *
  * k_tile_count of gt4hip_index.h is not used: it counts a 4-byte flag per item, which would cost more traffic than
  * the text itself; the counts here come out of the classification.  Algorithmic bytes per text byte: 1 + 1 read, 1
  * written (codes), 1 read (emit, twice: count and write) and 8 written per word. */
@@ -100,6 +104,54 @@ __device__ __forceinline__ void wave_line_state (u64 m_nl, u64 m_tail, u32 *has,
   *tail = m_nl ? (m_tail >> (63 - __builtin_clzll (m_nl))) != 0 : m_tail != 0;
 }
 
+/* v summed over the workgroup's threads in front of this one, and over all of them; s_sum: MK_THREADS / WAVE words of LDS
+ * that are free again at the caller's next barrier */
+struct BlockScan { u32 before, total; };
+__device__ __forceinline__ BlockScan block_scan (u32 v, u32 *s_sum)
+{
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  const u32 incl = dpp_inclusive_scan_u32 (v);
+  if (lane == WAVE - 1) s_sum[wv] = incl;
+  __syncthreads ();
+  BlockScan r = { incl - v, 0 };
+  for (int i = 0; i < MK_THREADS / WAVE; i++) {
+    if (i < wv) r.before += s_sum[i];
+    r.total += s_sum[i];
+  }
+  return r;
+}
+
+/* The state of the reader (src/fasta.c's machine) at a thread's first byte of tile t, from the thread's bytes, the
+ * workgroup's and the tile's carries: what k_mk_codes and k_mk_events start their byte loops from. */
+struct TileHead {
+  u32 w[4];               /* the thread's 16 bytes, 0 at n_eff and behind */
+  u32 rank, n_codes;      /* bytes >= ' ' of the tile in front of the thread, and of the whole tile */
+  u32 phase, name;        /* lines so far mod 4; in a name */
+};
+__device__ __forceinline__ TileHead tile_head (const unsigned char *__restrict__ text, u64 n_eff, u64 off, const u32 *tile_state, u32 *s_sum, u32 *s_has, u32 *s_tail)
+{
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  TileHead h;
+  u32 kept, nl, tail;
+  load16 (text, n_eff, off, h.w);
+  scan16 (h.w, &kept, &nl, &tail);
+  const u64 m_nl = __builtin_amdgcn_ballot_w64 (nl != 0), m_tail = __builtin_amdgcn_ballot_w64 (tail != 0);
+  u32 has, wt;
+  wave_line_state (m_nl, m_tail, &has, &wt);
+  if (lane == 0) s_has[wv] = has, s_tail[wv] = wt;
+  const BlockScan sc = block_scan (kept | (nl << 16), s_sum); /* both at most 4096 per tile */
+  const u32 st = *tile_state;
+  h.name = st & 1u;
+  for (int i = 0; i < MK_THREADS / WAVE; i++)
+    if (i < wv) h.name = s_has[i] ? s_tail[i] : (h.name | s_tail[i]);
+  const u64 below = ((u64) 1 << lane) - 1, b_nl = m_nl & below, b_tail = m_tail & below;
+  h.name = b_nl ? (b_tail >> (63 - __builtin_clzll (b_nl))) != 0 : (h.name | (b_tail != 0));
+  h.rank = sc.before & 0xffffu;
+  h.phase = ((st >> 1) + (sc.before >> 16)) & 3u;
+  h.n_codes = sc.total & 0xffffu;
+  return h;
+}
+
 __global__ __launch_bounds__ (MK_THREADS) void k_mk_summary (const unsigned char *__restrict__ text, u64 n, u64 n_tiles, u32 *tile_cnt, u32 *tile_info,
                                                              MakerInfo *info)
 {
@@ -115,17 +167,13 @@ __global__ __launch_bounds__ (MK_THREADS) void k_mk_summary (const unsigned char
     for (int j = MK_PER - 1; j >= 0; j--)
       if (MK_BYTE (w, j) == 0 && off + j < n) z = j;
     if (z < MK_PER) atomicMin (&info->nul_pos, off + (u64) z);
-    const u32 sum = dpp_wave_sum_u32 (kept | (nl << 16)); /* both at most 4096 per tile */
     u32 has, wt;
     wave_line_state (__builtin_amdgcn_ballot_w64 (nl != 0), __builtin_amdgcn_ballot_w64 (tail != 0), &has, &wt);
-    if (lane == 0) s_sum[wv] = sum, s_has[wv] = has, s_tail[wv] = wt;
-    __syncthreads ();
+    if (lane == 0) s_has[wv] = has, s_tail[wv] = wt;
+    const u32 s = block_scan (kept | (nl << 16), s_sum).total; /* both at most 4096 per tile */
     if (threadIdx.x == 0) {
-      u32 s = 0, tl = 0;
-      for (int i = 0; i < MK_THREADS / WAVE; i++) {
-        s += s_sum[i];
-        tl = s_has[i] ? s_tail[i] : (tl | s_tail[i]);
-      }
+      u32 tl = 0;
+      for (int i = 0; i < MK_THREADS / WAVE; i++) tl = s_has[i] ? s_tail[i] : (tl | s_tail[i]);
       tile_cnt[t] = s & 0xffffu;
       tile_info[t] = (s >> 16) | (tl << 31);
     }
@@ -174,42 +222,17 @@ __global__ __launch_bounds__ (MK_THREADS) void k_mk_codes (const unsigned char *
 {
   __shared__ unsigned char out[MK_TILE];
   __shared__ u32 s_sum[MK_THREADS / WAVE], s_has[MK_THREADS / WAVE], s_tail[MK_THREADS / WAVE];
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
   const u64 nul = info->nul_pos, n_eff = nul < n ? nul : n;
   for (u64 t = blockIdx.x; t < n_tiles; t += gridDim.x) {
     if (t * MK_TILE >= n_eff) break; /* (uniform: every later tile of this workgroup lies behind the end as well) */
     const u64 off = t * MK_TILE + (u64) threadIdx.x * MK_PER;
-    u32 w[4], kept, nl, tail;
-    load16 (text, n_eff, off, w);
-    scan16 (w, &kept, &nl, &tail);
-    const u32 incl = dpp_inclusive_scan_u32 (kept | (nl << 16));
-    const u64 m_nl = __builtin_amdgcn_ballot_w64 (nl != 0), m_tail = __builtin_amdgcn_ballot_w64 (tail != 0);
-    u32 has, wt;
-    wave_line_state (m_nl, m_tail, &has, &wt);
-    if (lane == WAVE - 1) s_sum[wv] = incl;
-    if (lane == 0) s_has[wv] = has, s_tail[wv] = wt;
-    __syncthreads ();
-    const u32 st = tile_state[t];
-    u32 before = 0, total = 0, name = st & 1u;
-    for (int i = 0; i < MK_THREADS / WAVE; i++) {
-      if (i < wv) {
-        before += s_sum[i];
-        name = s_has[i] ? s_tail[i] : (name | s_tail[i]);
-      }
-      total += s_sum[i];
-    }
-    const u32 excl = before + incl - (kept | (nl << 16));
-    u32 rank = excl & 0xffffu;
-    u32 phase = ((st >> 1) + (excl >> 16)) & 3u;
-    {
-      const u64 below = ((u64) 1 << lane) - 1, b_nl = m_nl & below, b_tail = m_tail & below;
-      name = b_nl ? (b_tail >> (63 - __builtin_clzll (b_nl))) != 0 : (name | (b_tail != 0));
-    }
+    const TileHead h = tile_head (text, n_eff, off, tile_state + t, s_sum, s_has, s_tail);
+    u32 rank = h.rank, phase = h.phase, name = h.name;
     u32 pnl = 0;
     if (FASTQ && off < n_eff) pnl = off ? text[off - 1] == '\n' : at_line_start0;
 #pragma unroll
     for (int j = 0; j < MK_PER; j++) {
-      const u32 c = MK_BYTE (w, j);
+      const u32 c = MK_BYTE (h.w, j);
       const u64 p = off + j;
       if (p < n_eff) {
         u32 code;
@@ -235,7 +258,7 @@ __global__ __launch_bounds__ (MK_THREADS) void k_mk_codes (const unsigned char *
     }
     __syncthreads ();
     /* the tile's codes to their place: single bytes up to a dword boundary, dwords, single bytes */
-    const u32 m = total & 0xffffu;
+    const u32 m = h.n_codes;
     unsigned char *dst = codes + tile_off[t];
     u32 head = (u32) (4u - ((size_t) dst & 3u)) & 3u;
     if (head > m) head = m;
@@ -250,64 +273,66 @@ __global__ __launch_bounds__ (MK_THREADS) void k_mk_codes (const unsigned char *
   }
 }
 
-/* `buf`: the halo's MK_HALO codes, then the text's (16-byte aligned).  WRITE = false: tile_cnt[t] = words that end in tile t. */
+/* `buf`: the halo's MK_HALO codes, then the text's (16-byte aligned).  w = the thread's 16 codes from j0 on and the MK_HALO
+ * in front of them (all 4 where the thread has none); returns bit i set iff a word ends at code j0 + i, that is iff
+ * codes j0 + i - k + 1 .. j0 + i are bases. */
+__device__ __forceinline__ u32 load_word_ends (const unsigned char *__restrict__ buf, u64 j0, u64 n_codes, u32 k, u32 w[12])
+{
+  if (j0 < n_codes) {
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+      const u32x4 v = *(const u32x4 *) (buf + j0 + 16 * q);
+      w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < 12; q++) w[q] = 0x04040404u;
+  }
+  u32 len = 0, ends = 0;
+#pragma unroll
+  for (int i = 0; i < MK_HALO + MK_PER; i++) {
+    len = MK_BYTE (w, i) < 4u ? len + 1u : 0u;
+    if (i >= MK_HALO && j0 + (u64) (i - MK_HALO) < n_codes && len >= k) ends |= 1u << (i - MK_HALO);
+  }
+  return ends;
+}
+
+/* f (j, forward word masked to 2k bits, reverse complement) for every word of `ends`, j the index of its last code, in order */
+template <typename F>
+__device__ __forceinline__ void for_each_word (const u32 w[12], u32 ends, u64 j0, u32 k, F f)
+{
+  const u64 mask = k >= 32 ? ~0ull : (1ull << (2 * k)) - 1;
+  u64 fw = 0, rv = 0;
+#pragma unroll
+  for (int i = 0; i < MK_HALO + MK_PER; i++) {
+    const u32 c = MK_BYTE (w, i);
+    fw = (fw << 2) | (c & 3u);
+    rv = (rv >> 2) | ((u64) (~c & 3u) << (2 * (k - 1)));
+    if (i >= MK_HALO && (ends >> (i - MK_HALO) & 1u)) f (j0 + (u64) (i - MK_HALO), fw & mask, rv);
+  }
+}
+
+/* WRITE = false: tile_cnt[t] = words that end in tile t. */
 template <bool WRITE>
 __global__ __launch_bounds__ (MK_THREADS) void k_mk_emit (const unsigned char *__restrict__ buf, const MakerInfo *info, u64 n_tiles, u32 k, u32 forward_only,
                                                           u32 *tile_cnt, const u64 *tile_off, u64 *words)
 {
   __shared__ u64 stage[WRITE ? MK_TILE : 1];
   __shared__ u32 s_sum[MK_THREADS / WAVE];
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
   const u64 n_codes = info->n_codes;
-  const u64 mask = k >= 32 ? ~0ull : (1ull << (2 * k)) - 1;
   for (u64 t = blockIdx.x; t < n_tiles; t += gridDim.x) {
     const u64 j0 = t * MK_TILE + (u64) threadIdx.x * MK_PER;
     u32 w[12];
-    if (j0 < n_codes) {
-#pragma unroll
-      for (int q = 0; q < 3; q++) {
-        const u32x4 v = *(const u32x4 *) (buf + j0 + 16 * q);
-        w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < 12; q++) w[q] = 0x04040404u;
-    }
-    u32 len = 0, cnt = 0;
-#pragma unroll
-    for (int i = 0; i < MK_HALO + MK_PER; i++) {
-      const u32 c = MK_BYTE (w, i);
-      len = c < 4u ? len + 1u : 0u;
-      if (i >= MK_HALO && j0 + (u64) (i - MK_HALO) < n_codes && len >= k) cnt++;
-    }
-    const u32 incl = dpp_inclusive_scan_u32 (cnt);
-    if (lane == WAVE - 1) s_sum[wv] = incl;
-    __syncthreads ();
-    u32 before = 0, total = 0;
-    for (int i = 0; i < MK_THREADS / WAVE; i++) {
-      if (i < wv) before += s_sum[i];
-      total += s_sum[i];
-    }
+    const u32 ends = load_word_ends (buf, j0, n_codes, k, w), cnt = (u32) __popc (ends);
+    const BlockScan sc = block_scan (cnt, s_sum);
     if (!WRITE) {
-      if (threadIdx.x == 0) tile_cnt[t] = total;
+      if (threadIdx.x == 0) tile_cnt[t] = sc.total;
     } else {
-      u32 rank = before + incl - cnt;
-      u64 fw = 0, rv = 0;
-      len = 0;
-#pragma unroll
-      for (int i = 0; i < MK_HALO + MK_PER; i++) {
-        const u32 c = MK_BYTE (w, i);
-        fw = (fw << 2) | (c & 3u);
-        rv = (rv >> 2) | ((u64) (~c & 3u) << (2 * (k - 1)));
-        len = c < 4u ? len + 1u : 0u;
-        if (i >= MK_HALO && j0 + (u64) (i - MK_HALO) < n_codes && len >= k) {
-          const u64 f = fw & mask;
-          stage[rank++] = forward_only || f < rv ? f : rv;
-        }
-      }
+      u32 rank = sc.before;
+      for_each_word (w, ends, j0, k, [&] (u64, u64 f, u64 rv) { stage[rank++] = forward_only || f < rv ? f : rv; });
       __syncthreads ();
       u64 *dst = words + tile_off[t];
-      for (u32 j = threadIdx.x; j < total; j += MK_THREADS) dst[j] = stage[j];
+      for (u32 j = threadIdx.x; j < sc.total; j += MK_THREADS) dst[j] = stage[j];
     }
     __syncthreads ();
   }
@@ -340,7 +365,6 @@ __global__ __launch_bounds__ (MK_THREADS) void k_mk_events (const unsigned char 
                                                             u32 *ev_cnt, const u64 *ev_off, u64 *ev, const MakerInfo *info)
 {
   __shared__ u32 s_sum[MK_THREADS / WAVE], s_has[MK_THREADS / WAVE], s_tail[MK_THREADS / WAVE], s_ev[MK_THREADS / WAVE];
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
   const u64 nul = info->nul_pos, n_eff = nul < n ? nul : n;
   for (u64 t = blockIdx.x; t < n_tiles; t += gridDim.x) {
     if (t * MK_TILE >= n_eff) { /* (uniform) */
@@ -348,36 +372,15 @@ __global__ __launch_bounds__ (MK_THREADS) void k_mk_events (const unsigned char 
       continue;
     }
     const u64 off = t * MK_TILE + (u64) threadIdx.x * MK_PER;
-    u32 w[4], kept, nl, tail;
-    load16 (text, n_eff, off, w);
-    scan16 (w, &kept, &nl, &tail);
-    const u32 incl = dpp_inclusive_scan_u32 (kept | (nl << 16));
-    const u64 m_nl = __builtin_amdgcn_ballot_w64 (nl != 0), m_tail = __builtin_amdgcn_ballot_w64 (tail != 0);
-    u32 has, wt;
-    wave_line_state (m_nl, m_tail, &has, &wt);
-    if (lane == WAVE - 1) s_sum[wv] = incl;
-    if (lane == 0) s_has[wv] = has, s_tail[wv] = wt;
-    __syncthreads ();
-    const u32 st = tile_state[t];
-    u32 before = 0, name = st & 1u;
-    for (int i = 0; i < wv; i++) {
-      before += s_sum[i];
-      name = s_has[i] ? s_tail[i] : (name | s_tail[i]);
-    }
-    const u32 excl = before + incl - (kept | (nl << 16));
-    u32 rank = excl & 0xffffu;
-    u32 phase = ((st >> 1) + (excl >> 16)) & 3u;
-    {
-      const u64 below = ((u64) 1 << lane) - 1, b_nl = m_nl & below, b_tail = m_tail & below;
-      name = b_nl ? (b_tail >> (63 - __builtin_clzll (b_nl))) != 0 : (name | (b_tail != 0));
-    }
+    const TileHead h = tile_head (text, n_eff, off, tile_state + t, s_sum, s_has, s_tail);
+    u32 rank = h.rank, phase = h.phase, name = h.name;
     /* this thread's events */
     u32 ne = 0;
     {
       u32 nm = name, ph = phase;
 #pragma unroll
       for (int j = 0; j < MK_PER; j++) { /* (load16 gives 0 for the bytes behind n_eff: no event there) */
-        const u32 c = MK_BYTE (w, j), is_nl = IS_BYTE (c, '\n'), is_gt = IS_BYTE (c, '>');
+        const u32 c = MK_BYTE (h.w, j), is_nl = IS_BYTE (c, '\n'), is_gt = IS_BYTE (c, '>');
         if (FASTQ) {
           ne += is_nl & (ph != 2u);
           ph = (ph + is_nl) & 3u;
@@ -387,22 +390,15 @@ __global__ __launch_bounds__ (MK_THREADS) void k_mk_events (const unsigned char 
         }
       }
     }
-    const u32 einc = dpp_inclusive_scan_u32 (ne);
-    if (lane == WAVE - 1) s_ev[wv] = einc;
-    __syncthreads ();
-    u32 ebefore = 0, etotal = 0;
-    for (int i = 0; i < MK_THREADS / WAVE; i++) {
-      if (i < wv) ebefore += s_ev[i];
-      etotal += s_ev[i];
-    }
+    const BlockScan es = block_scan (ne, s_ev);
     if (!WRITE) {
-      if (threadIdx.x == 0) ev_cnt[t] = etotal;
+      if (threadIdx.x == 0) ev_cnt[t] = es.total;
     } else if (ne) {
-      u64 slot = ev_off[t] + ebefore + einc - ne;
+      u64 slot = ev_off[t] + es.before;
       const u64 code0 = tile_off[t];
 #pragma unroll
       for (int j = 0; j < MK_PER; j++) {
-        const u32 c = MK_BYTE (w, j), is_nl = IS_BYTE (c, '\n'), is_gt = IS_BYTE (c, '>');
+        const u32 c = MK_BYTE (h.w, j), is_nl = IS_BYTE (c, '\n'), is_gt = IS_BYTE (c, '>');
         u32 kind, is_ev;
         if (FASTQ) {
           kind = (phase + 1u) & 3u; /* name line 1, sequence line 2, '+' line none, quality line 0 */
@@ -433,39 +429,17 @@ __global__ __launch_bounds__ (MK_THREADS) void k_mk_emit_loc (const unsigned cha
 {
   __shared__ u32 s_sum[MK_THREADS / WAVE];
   __shared__ unsigned long long s_max, s_over;
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
   const u64 n_codes = info->n_codes;
-  const u64 mask = k >= 32 ? ~0ull : (1ull << (2 * k)) - 1;
   for (u64 t = blockIdx.x; t < n_tiles; t += gridDim.x) {
     const u64 j0 = t * MK_TILE + (u64) threadIdx.x * MK_PER;
     if (threadIdx.x == 0) s_max = 0, s_over = 0;
     u32 w[12];
-    if (j0 < n_codes) {
-#pragma unroll
-      for (int q = 0; q < 3; q++) {
-        const u32x4 v = *(const u32x4 *) (buf + j0 + 16 * q);
-        w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < 12; q++) w[q] = 0x04040404u;
-    }
-    u32 len = 0, cnt = 0;
-#pragma unroll
-    for (int i = 0; i < MK_HALO + MK_PER; i++) {
-      const u32 c = MK_BYTE (w, i);
-      len = c < 4u ? len + 1u : 0u;
-      if (i >= MK_HALO && j0 + (u64) (i - MK_HALO) < n_codes && len >= k) cnt++;
-    }
-    const u32 incl = dpp_inclusive_scan_u32 (cnt);
-    if (lane == WAVE - 1) s_sum[wv] = incl;
-    __syncthreads ();
-    u32 before = 0;
-    for (int i = 0; i < wv; i++) before += s_sum[i];
+    const u32 ends = load_word_ends (buf, j0, n_codes, k, w), cnt = (u32) __popc (ends);
+    const BlockScan sc = block_scan (cnt, s_sum);
     if (cnt) {
       /* a thread's words and locations lie together (up to 128 bytes each), written from the thread: not staged in LDS as
        * k_mk_emit<true> stages the words, which would take the two streams through it one after the other */
-      u64 at = tile_off[t] + before + incl - cnt;
+      u64 at = tile_off[t] + sc.before;
       /* events whose code index is <= j0: the last of them is where the sequence of code j0 starts */
       u64 lo = 0, hi = n_ev;
       while (lo < hi) {
@@ -473,27 +447,17 @@ __global__ __launch_bounds__ (MK_THREADS) void k_mk_emit_loc (const unsigned cha
         if (ev[2 * mid + 1] <= j0) lo = mid + 1;
         else hi = mid;
       }
-      u64 fw = 0, rv = 0, pmax = 0, over = 0;
-      len = 0;
-#pragma unroll
-      for (int i = 0; i < MK_HALO + MK_PER; i++) {
-        const u32 c = MK_BYTE (w, i);
-        fw = (fw << 2) | (c & 3u);
-        rv = (rv >> 2) | ((u64) (~c & 3u) << (2 * (k - 1)));
-        len = c < 4u ? len + 1u : 0u;
-        if (i >= MK_HALO && j0 + (u64) (i - MK_HALO) < n_codes && len >= k) {
-          const u64 j = j0 + (u64) (i - MK_HALO);
-          while (lo < n_ev && ev[2 * lo + 1] <= j) lo++;
-          const u64 ord = lo ? (g0 + lo - 1) / PERIOD : ord0;
-          const u64 pos = (lo ? j - ev[2 * lo - 1] : j + codes0) + 1 - k;
-          const u64 f = fw & mask;
-          words[at] = f < rv ? f : rv;
-          raw[at] = (ord << 33) | ((pos & 0xffffffffull) << 1) | (u64) (rv < f);
-          at++;
-          pmax = pos > pmax ? pos : pmax;
-          over |= (ord >> 31) | (pos >> 32);
-        }
-      }
+      u64 pmax = 0, over = 0;
+      for_each_word (w, ends, j0, k, [&] (u64 j, u64 f, u64 rv) {
+        while (lo < n_ev && ev[2 * lo + 1] <= j) lo++;
+        const u64 ord = lo ? (g0 + lo - 1) / PERIOD : ord0;
+        const u64 pos = (lo ? j - ev[2 * lo - 1] : j + codes0) + 1 - k;
+        words[at] = f < rv ? f : rv;
+        raw[at] = (ord << 33) | ((pos & 0xffffffffull) << 1) | (u64) (rv < f);
+        at++;
+        pmax = pos > pmax ? pos : pmax;
+        over |= (ord >> 31) | (pos >> 32);
+      });
       atomicMax (&s_max, (unsigned long long) pmax);
       if (over) s_over = 1;
     }
@@ -574,179 +538,6 @@ struct LocCall {
   gt4hip_locations_carry *out;
 };
 
-int finish_locations (gt4hip_context *ctx, LocCall *loc, const gt4hip_maker_carry *reader, const u64 *d_ev, uint64_t n_ev, uint64_t n_codes, uint64_t end_offset, uint64_t max_pos);
-
-/* gt4hip_text_to_words; with `loc`, gt4hip_text_to_locations: the same kernels up to the words' count, then the events and
- * k_mk_emit_loc into the caller's arrays instead of k_mk_emit<true> into a block of the context */
-int text_to_words (gt4hip_context *ctx, const void *text, size_t n_bytes, unsigned word_length, unsigned flags, const gt4hip_maker_carry *in,
-                   gt4hip_maker_carry *out, uint64_t **d_words, uint64_t *n_words, uint64_t *error_offset, LocCall *loc)
-{
-  if (!ctx || !d_words || !n_words || (n_bytes && !text) || !word_length || word_length > 32 ||
-      (flags & ~(unsigned) (GT4HIP_MAKER_FORWARD_ONLY | GT4HIP_MAKER_TEXT_ON_DEVICE)))
-    return GT4HIP_EINVAL;
-  if ((flags & GT4HIP_MAKER_TEXT_ON_DEVICE) && ((size_t) text & 15)) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_text_to_words: device text must be 16-byte aligned");
-  if (in && (in->file_type > GT4HIP_MAKER_FASTQ || in->line_phase > 3)) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_text_to_words: carry not from this library");
-  HIPCHK (ctx, hipSetDevice (ctx->device));
-  if (!loc) gt4hip_words_free (ctx, NULL); /* (the words of the call before, if the caller still left them) */
-  *d_words = NULL;
-  *n_words = 0;
-  if (error_offset) *error_offset = 0;
-  gt4hip_maker_carry c;
-  if (in) {
-    c = *in;
-  } else {
-    memset (&c, 0, sizeof c);
-    memset (c.codes, 4, sizeof c.codes);
-    c.at_line_start = 1;
-  }
-  c.error = 0;
-  gt4hip_maker_carry dummy;
-  if (!out) out = &dummy;
-  *out = c;
-  if (!n_bytes || c.ended) return loc ? finish_locations (ctx, loc, out, NULL, 0, 0, loc->in ? loc->in->offset : 0, 0) : GT4HIP_OK;
-  hipStream_t st = ctx->stream;
-  Blocks blk;
-  int rc;
-  /* the text */
-  const unsigned char *d_text = (const unsigned char *) text;
-  if (!(flags & GT4HIP_MAKER_TEXT_ON_DEVICE)) {
-    void *p = NULL;
-    if ((rc = blk.get (ctx, n_bytes, &p))) return rc;
-    HIPCHK (ctx, hipMemcpyAsync (p, text, n_bytes, hipMemcpyHostToDevice, st));
-    d_text = (const unsigned char *) p;
-  }
-  /* the first byte of a file decides its type (:128-138); a NUL there is an empty file */
-  if (!c.file_type) {
-    unsigned char first = 0;
-    if (flags & GT4HIP_MAKER_TEXT_ON_DEVICE) {
-      if ((rc = gt4hip_read_back (ctx, &first, d_text, 1, "reading the first byte of the text failed"))) return rc;
-    } else {
-      first = *(const unsigned char *) text;
-    }
-    if (!first) {
-      hipStreamSynchronize (st); /* (the upload reads the caller's text) */
-      out->ended = 1;
-      return loc ? finish_locations (ctx, loc, out, NULL, 0, 0, loc->in ? loc->in->offset : 0, 0) : GT4HIP_OK;
-    }
-    if (first != '>' && first != '@') {
-      hipStreamSynchronize (st);
-      return format_error (ctx, out, GT4HIP_MAKER_ERR_START, 0, error_offset);
-    }
-    c.file_type = first == '>' ? GT4HIP_MAKER_FASTA : GT4HIP_MAKER_FASTQ;
-  }
-  const uint64_t tiles = (n_bytes + MK_TILE - 1) / MK_TILE;
-  if (tiles >= (1ull << 32)) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_text_to_words: %zu bytes in one piece", n_bytes);
-  MakerInfo *info = NULL;
-  u32 *tile_cnt = NULL, *tile_info = NULL, *tile_state = NULL;
-  u64 *tile_off = NULL;
-  unsigned char *buf = NULL;
-  if ((rc = blk.get (ctx, sizeof (MakerInfo), (void **) &info))) return rc;
-  if ((rc = blk.get (ctx, tiles * 4, (void **) &tile_cnt))) return rc;
-  if ((rc = blk.get (ctx, tiles * 4, (void **) &tile_info))) return rc;
-  if ((rc = blk.get (ctx, tiles * 4, (void **) &tile_state))) return rc;
-  if ((rc = blk.get (ctx, tiles * 8, (void **) &tile_off))) return rc;
-  if ((rc = blk.get (ctx, tiles * MK_TILE + MK_HALO + 64, (void **) &buf))) return rc;
-  /* with locations the codes' offsets are still read after the words are counted: the emit stage gets arrays of its own */
-  u32 *emit_cnt = tile_cnt, *ev_cnt = NULL;
-  u64 *emit_off = tile_off, *ev_off = NULL;
-  if (loc) {
-    if ((rc = blk.get (ctx, tiles * 4, (void **) &emit_cnt))) return rc;
-    if ((rc = blk.get (ctx, tiles * 8, (void **) &emit_off))) return rc;
-    if ((rc = blk.get (ctx, tiles * 4, (void **) &ev_cnt))) return rc;
-    if ((rc = blk.get (ctx, tiles * 8, (void **) &ev_off))) return rc;
-  }
-  const bool fastq = c.file_type == GT4HIP_MAKER_FASTQ;
-  const u64 file_off = loc && loc->in ? loc->in->offset : 0;
-  MakerInfo h;
-  memset (&h, 0, sizeof h);
-  h.nul_pos = n_bytes;
-  h.err = ~0ull;
-  h.in_name = c.in_name, h.phase = c.line_phase, h.at_line_start = c.at_line_start;
-  HIPCHK (ctx, hipMemcpyAsync (info, &h, sizeof h, hipMemcpyHostToDevice, st));
-  HIPCHK (ctx, hipMemcpyAsync (buf, c.codes, MK_HALO, hipMemcpyHostToDevice, st));
-  const int grid = grid_for (ctx, tiles, 1);
-  hipEventRecord (ctx->ev[0], st);
-  hipLaunchKernelGGL (k_mk_summary, dim3 (grid), dim3 (MK_THREADS), 0, st, d_text, (u64) n_bytes, (u64) tiles, tile_cnt, tile_info, info);
-  hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, st, tile_cnt, (u64) tiles, tile_off, &info->n_words);
-  hipLaunchKernelGGL (k_mk_state_scan, dim3 (1), dim3 (1024), 0, st, tile_info, (u64) tiles, c.in_name, c.line_phase, tile_state);
-  if (c.file_type == GT4HIP_MAKER_FASTQ)
-    hipLaunchKernelGGL (k_mk_codes<true>, dim3 (grid), dim3 (MK_THREADS), 0, st, d_text, (u64) n_bytes, (u64) tiles, tile_off, tile_state, c.at_line_start, buf + MK_HALO, info);
-  else
-    hipLaunchKernelGGL (k_mk_codes<false>, dim3 (grid), dim3 (MK_THREADS), 0, st, d_text, (u64) n_bytes, (u64) tiles, tile_off, tile_state, c.at_line_start, buf + MK_HALO, info);
-  /* (tile_cnt and tile_off now serve the emit stage: at most as many codes as bytes, so at most as many tiles) */
-  hipLaunchKernelGGL (k_mk_emit<false>, dim3 (grid), dim3 (MK_THREADS), 0, st, buf, info, (u64) tiles, word_length, 0u, emit_cnt, emit_off, (u64 *) NULL);
-  hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, st, emit_cnt, (u64) tiles, emit_off, &info->n_words);
-  if (loc) {
-    if (fastq)
-      hipLaunchKernelGGL ((k_mk_events<true, false>), dim3 (grid), dim3 (MK_THREADS), 0, st, d_text, (u64) n_bytes, (u64) tiles, tile_off, tile_state, file_off, ev_cnt, ev_off, (u64 *) NULL, info);
-    else
-      hipLaunchKernelGGL ((k_mk_events<false, false>), dim3 (grid), dim3 (MK_THREADS), 0, st, d_text, (u64) n_bytes, (u64) tiles, tile_off, tile_state, file_off, ev_cnt, ev_off, (u64 *) NULL, info);
-    hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, st, ev_cnt, (u64) tiles, ev_off, &info->n_events);
-  }
-  hipEventRecord (ctx->ev[1], st);
-  HIPCHK (ctx, hipGetLastError ());
-  if ((rc = gt4hip_read_back (ctx, &h, info, sizeof h, "reading the extraction's totals back failed"))) return rc;
-  /* what the next piece starts from */
-  out->file_type = c.file_type;
-  out->in_name = h.in_name, out->line_phase = h.phase, out->at_line_start = h.at_line_start;
-  out->ended = h.nul_pos < n_bytes;
-  HIPCHK (ctx, hipMemcpyAsync (out->codes, buf + h.n_codes, MK_HALO, hipMemcpyDeviceToHost, st)); /* the last 32 codes, halo included */
-  HIPCHK (ctx, hipStreamSynchronize (st));
-  if (h.err != ~0ull) return format_error (ctx, out, (uint32_t) (h.err & 7u), h.err >> 3, error_offset);
-  if (out->ended && end_error (out)) return format_error (ctx, out, end_error (out), h.nul_pos, error_offset);
-  if (loc) {
-    if (h.n_words > loc->capacity)
-      return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_text_to_locations: %llu words, room for %llu", (unsigned long long) h.n_words, (unsigned long long) loc->capacity);
-    u64 *ev = NULL;
-    if ((rc = blk.get (ctx, (size_t) h.n_events * 16, (void **) &ev))) return rc;
-    hipEventRecord (ctx->ev[2], st);
-    if (h.n_events) {
-      if (fastq)
-        hipLaunchKernelGGL ((k_mk_events<true, true>), dim3 (grid), dim3 (MK_THREADS), 0, st, d_text, (u64) n_bytes, (u64) tiles, tile_off, tile_state, file_off, ev_cnt, ev_off, ev, info);
-      else
-        hipLaunchKernelGGL ((k_mk_events<false, true>), dim3 (grid), dim3 (MK_THREADS), 0, st, d_text, (u64) n_bytes, (u64) tiles, tile_off, tile_state, file_off, ev_cnt, ev_off, ev, info);
-    }
-    if (h.n_words) {
-      const u64 g0 = loc->in ? loc->in->n_events : 0, ord0 = loc->in && loc->in->n_subseqs ? loc->in->n_subseqs - 1 : 0, codes0 = loc->in ? loc->in->seq_codes : 0;
-      if (fastq)
-        hipLaunchKernelGGL (k_mk_emit_loc<3>, dim3 (grid), dim3 (MK_THREADS), 0, st, buf, info, (u64) tiles, word_length, emit_off, loc->dst_words, loc->dst_raw, ev, h.n_events, g0, ord0, codes0);
-      else
-        hipLaunchKernelGGL (k_mk_emit_loc<2>, dim3 (grid), dim3 (MK_THREADS), 0, st, buf, info, (u64) tiles, word_length, emit_off, loc->dst_words, loc->dst_raw, ev, h.n_events, g0, ord0, codes0);
-    }
-    hipEventRecord (ctx->ev[3], st);
-    HIPCHK (ctx, hipGetLastError ());
-    if ((rc = gt4hip_read_back (ctx, &h, info, sizeof h, "reading the locations' totals back failed"))) return rc;
-    float ms = 0, ms2 = 0;
-    if (hipEventElapsedTime (&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess && hipEventElapsedTime (&ms2, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->extract_ms = ms + ms2;
-    if (h.overflow) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_text_to_locations: a sequence ordinal of 2^31 or a position of 2^32 or more does not fit a raw location");
-    if (h.n_words) *d_words = (uint64_t *) loc->dst_words;
-    *n_words = h.n_words;
-    return finish_locations (ctx, loc, out, ev, h.n_events, h.n_codes, file_off + (out->ended ? h.nul_pos : n_bytes), h.max_pos);
-  }
-  if (h.n_words) {
-    void *w = NULL, *owner = NULL;
-    if (gt4hip_block_alloc (ctx, (size_t) h.n_words * 8, &w, &owner))
-      return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_text_to_words: %llu words", (unsigned long long) h.n_words);
-    ctx->maker_words = (gt4hip_list *) owner;
-    hipEventRecord (ctx->ev[2], st);
-    hipLaunchKernelGGL (k_mk_emit<true>, dim3 (grid), dim3 (MK_THREADS), 0, st, buf, info, (u64) tiles, word_length, (u32) ((flags & GT4HIP_MAKER_FORWARD_ONLY) != 0),
-                        tile_cnt, tile_off, (u64 *) w);
-    hipError_t e = hipGetLastError ();
-    hipEventRecord (ctx->ev[3], st);
-    if (e == hipSuccess) e = hipStreamSynchronize (st);
-    if (e != hipSuccess) {
-      gt4hip_words_free (ctx, (uint64_t *) w);
-      return gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_text_to_words: %s", hipGetErrorString (e));
-    }
-    /* the kernels alone: neither the read-back of the totals nor the allocation of the words between the two spans */
-    float ms = 0, ms2 = 0;
-    if (hipEventElapsedTime (&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess && hipEventElapsedTime (&ms2, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->extract_ms = ms + ms2;
-    *d_words = (uint64_t *) w;
-    *n_words = h.n_words;
-  }
-  return GT4HIP_OK;
-}
-
 /* the piece's events -> its subsequence records and the carry behind it (reference start_sequence_index / end_sequence_index,
  * src/glistmaker.c:1031-1052); `reader`: the reader's carry behind the piece, end_offset: where the piece (or the text) ends */
 int finish_locations (gt4hip_context *ctx, LocCall *loc, const gt4hip_maker_carry *reader, const u64 *d_ev, uint64_t n_ev, uint64_t n_codes, uint64_t end_offset, uint64_t max_pos)
@@ -809,6 +600,213 @@ int finish_locations (gt4hip_context *ctx, LocCall *loc, const gt4hip_maker_carr
   pc->subseqs = recs;
   if (loc->out) *loc->out = c;
   return GT4HIP_OK;
+}
+
+struct TypeKernels {
+  decltype (&k_mk_codes<false>) codes;
+  decltype (&k_mk_events<false, false>) count_events, write_events;
+  decltype (&k_mk_emit_loc<2>) emit_loc;
+};
+
+/* One call of the reader: its arguments and what the stages hand on.  A stage returns GT4HIP_OK, an error, or MK_DONE. */
+struct MakerCall {
+  gt4hip_context *ctx;
+  const void *text;
+  size_t n_bytes;
+  unsigned k, flags;
+  gt4hip_maker_carry *out;
+  uint64_t **d_words, *n_words, *error_offset;
+  LocCall *loc;            /* NULL: gt4hip_text_to_words */
+  gt4hip_maker_carry c;    /* what the piece starts from */
+  Blocks blk;
+  const unsigned char *d_text;
+  const TypeKernels *kern;
+  u64 file_off, tiles;     /* where the piece starts in its file (locations); its tiles of text */
+  int grid;
+  MakerInfo *info, h;      /* on the device, and as last read back */
+  u64 *tile_off, *emit_off, *ev_off, *ev;
+  u32 *tile_cnt, *tile_info, *tile_state, *emit_cnt, *ev_cnt;
+  unsigned char *buf;      /* the halo, then the codes */
+};
+constexpr int MK_DONE = -1; /* not an error: there is no text to read (no bytes, behind a NUL, or a NUL first) */
+
+/* the kernels that are instantiated by file type, [0] for FastA and [1] for FastQ: the one place that names both */
+const TypeKernels MK_KERNELS[2] = { { k_mk_codes<false>, k_mk_events<false, false>, k_mk_events<false, true>, k_mk_emit_loc<2> },
+                                    { k_mk_codes<true>, k_mk_events<true, false>, k_mk_events<true, true>, k_mk_emit_loc<3> } };
+
+/* arguments, the carry in and its copy out, the text on the device, the file's type */
+int maker_begin (MakerCall &m, const gt4hip_maker_carry *in)
+{
+  gt4hip_context *const ctx = m.ctx;
+  if (!ctx || !m.d_words || !m.n_words || (m.n_bytes && !m.text) || !m.k || m.k > 32 || (m.flags & ~(unsigned) (GT4HIP_MAKER_FORWARD_ONLY | GT4HIP_MAKER_TEXT_ON_DEVICE)))
+    return GT4HIP_EINVAL;
+  if ((m.flags & GT4HIP_MAKER_TEXT_ON_DEVICE) && ((size_t) m.text & 15)) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_text_to_words: device text must be 16-byte aligned");
+  if (in && (in->file_type > GT4HIP_MAKER_FASTQ || in->line_phase > 3)) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_text_to_words: carry not from this library");
+  HIPCHK (ctx, hipSetDevice (ctx->device));
+  if (!m.loc) gt4hip_words_free (ctx, NULL); /* (the words of the call before, if the caller still left them) */
+  *m.d_words = NULL;
+  *m.n_words = 0;
+  if (m.error_offset) *m.error_offset = 0;
+  if (in) {
+    m.c = *in;
+  } else {
+    memset (&m.c, 0, sizeof m.c);
+    memset (m.c.codes, 4, sizeof m.c.codes);
+    m.c.at_line_start = 1;
+  }
+  m.c.error = 0;
+  *m.out = m.c;
+  if (!m.n_bytes || m.c.ended) return MK_DONE;
+  m.d_text = (const unsigned char *) m.text;
+  if (!(m.flags & GT4HIP_MAKER_TEXT_ON_DEVICE)) {
+    const int rc = m.blk.get (ctx, m.n_bytes, (void **) &m.d_text);
+    if (rc) return rc;
+    HIPCHK (ctx, hipMemcpyAsync ((void *) m.d_text, m.text, m.n_bytes, hipMemcpyHostToDevice, ctx->stream));
+  }
+  /* the first byte of a file decides its type (:128-138); a NUL there is an empty file */
+  if (!m.c.file_type) {
+    const bool on_device = (m.flags & GT4HIP_MAKER_TEXT_ON_DEVICE) != 0;
+    unsigned char first = on_device ? 0 : *(const unsigned char *) m.text;
+    const int rc = on_device ? gt4hip_read_back (ctx, &first, m.d_text, 1, "reading the first byte of the text failed") : GT4HIP_OK;
+    if (rc) return rc;
+    if (first != '>' && first != '@') {
+      hipStreamSynchronize (ctx->stream); /* (the upload reads the caller's text) */
+      if (first) return format_error (ctx, m.out, GT4HIP_MAKER_ERR_START, 0, m.error_offset);
+      m.out->ended = 1;
+      return MK_DONE;
+    }
+    m.c.file_type = first == '>' ? GT4HIP_MAKER_FASTA : GT4HIP_MAKER_FASTQ;
+  }
+  m.kern = &MK_KERNELS[m.c.file_type == GT4HIP_MAKER_FASTQ];
+  m.file_off = m.loc && m.loc->in ? m.loc->in->offset : 0;
+  return GT4HIP_OK;
+}
+
+/* The first span of the extraction.  The call's device arrays; classify: text -> codes by summary, the two scans and k_mk_codes */
+int maker_classify_count (MakerCall &m)
+{
+  gt4hip_context *const ctx = m.ctx;
+  hipStream_t st = ctx->stream;
+  const u64 tiles = m.tiles = (m.n_bytes + MK_TILE - 1) / MK_TILE;
+  if (tiles >= (1ull << 32)) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_text_to_words: %zu bytes in one piece", m.n_bytes);
+  /* per tile three offsets and five counts.  The emit stage has arrays of its own (tiles of codes: at most as many as tiles
+   * of text): with locations tile_off is still read after the words are counted. */
+  int rc;
+  if ((rc = m.blk.get (ctx, sizeof (MakerInfo), (void **) &m.info))) return rc;
+  if ((rc = m.blk.get (ctx, tiles * (3 * 8 + 5 * 4), (void **) &m.tile_off))) return rc;
+  if ((rc = m.blk.get (ctx, tiles * MK_TILE + MK_HALO + 64, (void **) &m.buf))) return rc;
+  m.emit_off = m.tile_off + tiles, m.ev_off = m.emit_off + tiles, m.tile_cnt = (u32 *) (m.ev_off + tiles);
+  m.tile_info = m.tile_cnt + tiles, m.tile_state = m.tile_info + tiles, m.emit_cnt = m.tile_state + tiles, m.ev_cnt = m.emit_cnt + tiles;
+  m.h = MakerInfo { m.n_bytes, ~0ull, 0, 0, m.c.in_name, m.c.line_phase, m.c.at_line_start }; /* (the rest 0) */
+  HIPCHK (ctx, hipMemcpyAsync (m.info, &m.h, sizeof m.h, hipMemcpyHostToDevice, st));
+  HIPCHK (ctx, hipMemcpyAsync (m.buf, m.c.codes, MK_HALO, hipMemcpyHostToDevice, st));
+  m.grid = grid_for (ctx, tiles, 1);
+  hipEventRecord (ctx->ev[0], st);
+  hipLaunchKernelGGL (k_mk_summary, dim3 (m.grid), dim3 (MK_THREADS), 0, st, m.d_text, (u64) m.n_bytes, tiles, m.tile_cnt, m.tile_info, m.info);
+  hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, st, m.tile_cnt, tiles, m.tile_off, &m.info->n_words);
+  hipLaunchKernelGGL (k_mk_state_scan, dim3 (1), dim3 (1024), 0, st, m.tile_info, tiles, m.c.in_name, m.c.line_phase, m.tile_state);
+  hipLaunchKernelGGL (m.kern->codes, dim3 (m.grid), dim3 (MK_THREADS), 0, st, m.d_text, (u64) m.n_bytes, tiles, m.tile_off, m.tile_state, m.c.at_line_start, m.buf + MK_HALO, m.info);
+  /* count: words per tile of codes and where each tile's go; with locations the same for the events of each tile of text */
+  hipLaunchKernelGGL (k_mk_emit<false>, dim3 (m.grid), dim3 (MK_THREADS), 0, st, m.buf, m.info, m.tiles, m.k, 0u, m.emit_cnt, m.emit_off, (u64 *) NULL);
+  hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, st, m.emit_cnt, m.tiles, m.emit_off, &m.info->n_words);
+  if (m.loc) {
+    hipLaunchKernelGGL (m.kern->count_events, dim3 (m.grid), dim3 (MK_THREADS), 0, st, m.d_text, (u64) m.n_bytes, m.tiles, m.tile_off, m.tile_state, m.file_off, m.ev_cnt, m.ev_off, m.ev, m.info);
+    hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, st, m.ev_cnt, m.tiles, m.ev_off, &m.info->n_events);
+  }
+  hipEventRecord (ctx->ev[1], st);
+  return GT4HIP_OK;
+}
+
+/* the one read-back of the totals, what the next piece starts from, and the text's format errors */
+int maker_totals (MakerCall &m)
+{
+  gt4hip_context *const ctx = m.ctx;
+  gt4hip_maker_carry *const out = m.out;
+  const MakerInfo &h = m.h;
+  HIPCHK (ctx, hipGetLastError ());
+  const int rc = gt4hip_read_back (ctx, &m.h, m.info, sizeof h, "reading the extraction's totals back failed");
+  if (rc) return rc;
+  out->file_type = m.c.file_type;
+  out->in_name = h.in_name, out->line_phase = h.phase, out->at_line_start = h.at_line_start;
+  out->ended = h.nul_pos < m.n_bytes;
+  HIPCHK (ctx, hipMemcpyAsync (out->codes, m.buf + h.n_codes, MK_HALO, hipMemcpyDeviceToHost, ctx->stream)); /* the last 32 codes, halo included */
+  HIPCHK (ctx, hipStreamSynchronize (ctx->stream));
+  if (h.err != ~0ull) return format_error (ctx, out, (uint32_t) (h.err & 7u), h.err >> 3, m.error_offset);
+  if (out->ended && end_error (out)) return format_error (ctx, out, end_error (out), h.nul_pos, m.error_offset);
+  return GT4HIP_OK;
+}
+
+/* the kernels alone: events 0 to 1 and 2 to 3, neither the read-back of the totals nor the allocation of the words between them */
+void record_extract_ms (gt4hip_context *ctx)
+{
+  float ms = 0, ms2 = 0;
+  if (hipEventElapsedTime (&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess && hipEventElapsedTime (&ms2, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->extract_ms = ms + ms2;
+}
+
+/* the words into a block of the context */
+int maker_emit_words (MakerCall &m)
+{
+  gt4hip_context *const ctx = m.ctx;
+  hipStream_t st = ctx->stream;
+  if (!m.h.n_words) return GT4HIP_OK;
+  void *w = NULL, *owner = NULL;
+  if (gt4hip_block_alloc (ctx, (size_t) m.h.n_words * 8, &w, &owner))
+    return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_text_to_words: %llu words", (unsigned long long) m.h.n_words);
+  ctx->maker_words = (gt4hip_list *) owner;
+  hipEventRecord (ctx->ev[2], st);
+  hipLaunchKernelGGL (k_mk_emit<true>, dim3 (m.grid), dim3 (MK_THREADS), 0, st, m.buf, m.info, m.tiles, m.k, (u32) ((m.flags & GT4HIP_MAKER_FORWARD_ONLY) != 0), m.emit_cnt, m.emit_off, (u64 *) w);
+  hipError_t e = hipGetLastError ();
+  hipEventRecord (ctx->ev[3], st);
+  if (e == hipSuccess) e = hipStreamSynchronize (st);
+  if (e != hipSuccess) {
+    gt4hip_words_free (ctx, (uint64_t *) w);
+    return gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_text_to_words: %s", hipGetErrorString (e));
+  }
+  record_extract_ms (ctx);
+  *m.d_words = (uint64_t *) w;
+  *m.n_words = m.h.n_words;
+  return GT4HIP_OK;
+}
+
+/* the events, then the words and their raw locations into the caller's arrays, then the records of the file block */
+int maker_emit_locations (MakerCall &m)
+{
+  gt4hip_context *const ctx = m.ctx;
+  hipStream_t st = ctx->stream;
+  LocCall *const loc = m.loc;
+  MakerInfo &h = m.h;
+  if (h.n_words > loc->capacity)
+    return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_text_to_locations: %llu words, room for %llu", (unsigned long long) h.n_words, (unsigned long long) loc->capacity);
+  int rc;
+  if ((rc = m.blk.get (ctx, (size_t) h.n_events * 16, (void **) &m.ev))) return rc;
+  hipEventRecord (ctx->ev[2], st);
+  if (h.n_events)
+    hipLaunchKernelGGL (m.kern->write_events, dim3 (m.grid), dim3 (MK_THREADS), 0, st, m.d_text, (u64) m.n_bytes, m.tiles, m.tile_off, m.tile_state, m.file_off, m.ev_cnt, m.ev_off, m.ev, m.info);
+  if (h.n_words) {
+    const u64 g0 = loc->in ? loc->in->n_events : 0, ord0 = loc->in && loc->in->n_subseqs ? loc->in->n_subseqs - 1 : 0, codes0 = loc->in ? loc->in->seq_codes : 0;
+    hipLaunchKernelGGL (m.kern->emit_loc, dim3 (m.grid), dim3 (MK_THREADS), 0, st, m.buf, m.info, m.tiles, m.k, m.emit_off, loc->dst_words, loc->dst_raw, m.ev, h.n_events, g0, ord0, codes0);
+  }
+  hipEventRecord (ctx->ev[3], st);
+  HIPCHK (ctx, hipGetLastError ());
+  if ((rc = gt4hip_read_back (ctx, &h, m.info, sizeof h, "reading the locations' totals back failed"))) return rc;
+  record_extract_ms (ctx);
+  if (h.overflow) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_text_to_locations: a sequence ordinal of 2^31 or a position of 2^32 or more does not fit a raw location");
+  if (h.n_words) *m.d_words = (uint64_t *) loc->dst_words;
+  *m.n_words = h.n_words;
+  return finish_locations (ctx, loc, m.out, m.ev, h.n_events, h.n_codes, m.file_off + (m.out->ended ? h.nul_pos : m.n_bytes), h.max_pos);
+}
+
+/* gt4hip_text_to_words; with `loc`, gt4hip_text_to_locations: the same stages up to the words' count, then the events and
+ * k_mk_emit_loc into the caller's arrays instead of k_mk_emit<true> into a block of the context */
+int text_to_words (gt4hip_context *ctx, const void *text, size_t n_bytes, unsigned word_length, unsigned flags, const gt4hip_maker_carry *in,
+                   gt4hip_maker_carry *out, uint64_t **d_words, uint64_t *n_words, uint64_t *error_offset, LocCall *loc)
+{
+  gt4hip_maker_carry dummy;
+  MakerCall m = { ctx, text, n_bytes, word_length, flags, out ? out : &dummy, d_words, n_words, error_offset, loc };
+  int rc = maker_begin (m, in);
+  if (rc == MK_DONE) return loc ? finish_locations (ctx, loc, m.out, NULL, 0, 0, loc->in ? loc->in->offset : 0, 0) : GT4HIP_OK;
+  if (rc || (rc = maker_classify_count (m)) || (rc = maker_totals (m))) return rc;
+  return loc ? maker_emit_locations (m) : maker_emit_words (m);
 }
 
 }  // namespace
