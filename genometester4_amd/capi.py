@@ -123,6 +123,7 @@ SYMBOLS = [
     "gt4hip_sort_pairs", "gt4hip_pairs_to_index", "gt4hip_index_free",
     "gt4hip_list_subset", "gt4hip_subset_state_at",
     "gt4hip_text_to_locations", "gt4hip_locations_free", "gt4hip_pack_locations", "gt4hip_pairs_reserve", "gt4hip_pairs_release",
+    "gt4hip_pair_partition",
 ]
 
 _lib = None
@@ -234,6 +235,7 @@ def lib():
             "gt4hip_pairs_release": (None, [vp]),
             "gt4hip_list_subset": (C.c_int, [vp, vp, C.POINTER(SubsetParams), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]),
             "gt4hip_subset_state_at": (u64, [u64, u64]),
+            "gt4hip_pair_partition": (C.c_int, [vp, vp, vp, u64, vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -515,6 +517,13 @@ class Context:
 
     def synchronize(self):
         self._chk(lib().gt4hip_synchronize(self.h))
+
+    def pair_partition(self, a: "DeviceList", b: "DeviceList", tile_records):
+        """The partition launch of a pair merge alone (diagnostic): uint64 array [tiles + 1, 2], the records of a and of b before every tile."""
+        tiles = (a.n_words + b.n_words + tile_records - 1) // tile_records
+        part = np.empty((tiles + 1, 2), dtype=np.uint64)
+        self._chk(lib().gt4hip_pair_partition(self.h, a.h, b.h, tile_records, part.ctypes.data))
+        return part
 
     def shard_cuts(self, lists, n_shards):
         """First key of every key-range shard, from samples of the lists themselves (gt4hip_shard_cuts)."""

@@ -175,6 +175,7 @@ extern "C" int gt4hip_set_option (gt4hip_context *ctx, const char *name, int64_t
   else if (!strcmp (name, "scan_group")) ctx->scan_group = (int) value;
   else if (!strcmp (name, "dynamic")) ctx->dynamic = (int) value;
   else if (!strcmp (name, "a_rows")) ctx->a_rows = (int) value;
+  else if (!strcmp (name, "part_guided")) ctx->part_guided = (int) value;
   else if (!strcmp (name, "kway")) ctx->kway_enabled = (int) value;
   else if (!strcmp (name, "kway_max")) ctx->kway_max = value == 8 ? 8 : (value == 33 ? 33 : 32);
   else if (!strcmp (name, "kway_g")) ctx->kway_g = value;
@@ -190,6 +191,7 @@ extern "C" int gt4hip_get_counter (gt4hip_context *ctx, const char *name, uint64
 {
   if (!ctx || !name || !value) return GT4HIP_EINVAL;
   if (!strcmp (name, "single_pass_fallbacks")) *value = ctx->single_pass_fallbacks;
+  else if (!strcmp (name, "partition_us")) *value = (uint64_t) (ctx->partition_ms * 1000.0);
   else if (!strcmp (name, "kway_calls")) *value = ctx->kway_calls;
   else if (!strcmp (name, "kway_overflows")) *value = ctx->kway_overflows;
   else if (!strcmp (name, "kway_declined")) *value = ctx->kway_declined;

@@ -23,6 +23,8 @@ struct gt4hip_context {
   int64_t grid_override;
   uint32_t spin_limit;       /* option "spin_limit": bound of the single-pass kernel's waits (0 = default) */
   int a_rows;      /* option "a_rows": A-only single-pass kernels: 0 the A-rows body for every tile whose A records fit half the position rows, -1 never */
+  int part_guided; /* option "part_guided": the pair partition's co-rank searches: 0 guided by the coarse neighbours (gt4hip_corank.h), -1 plain bisection */
+  double partition_ms; /* counter "partition_us": the partition launch of the last pair call (HIP events 0 -> 1 of gt4hip_run_pair) */
   int dynamic;     /* option "dynamic": tiles of the single-pass kernels dealt by a ticket counter: 0 automatic, 1 always, -1 never (round-robin) */
   int scan_group;  /* option "scan_group": 0 automatic, 1 always the scanner group, -1 always one wavefront per stream */
   int force_geom; /* options "geom1" / "geom0": force the large / small geometry for every call (experiments); 0 = automatic */

@@ -34,8 +34,21 @@ struct PairControl {
   unsigned long long resolve_stats[8]; /* diagnostic builds: sampled resolve calls, spins, -, agg/carry not ready at first look; scanner rounds, rows retired on the first look, rows */ /* diagnostic builds (-DGT4_PROFILE_PHASES): shader cycles per phase, summed over workgroups */
 };
 
+/* What the partition launch zeroes for the merge launch behind it, in 16-byte chunks: ctl_chunks of the control block, and
+ * for every stream in `ops` the words of the chained scan as k_pair_merge lays them out in desc for `rows` rows of 64
+ * tiles: agg u32[4][rows * 64], carry u64[4][rows + 1], rowsum u64[4][rows] (a stream's carries and row sums widened to
+ * whole chunks, into a neighbour stream's words: the merge either finds those zeroed too or never reads them).
+ * ctl_chunks 0 and ops 0: nothing. */
+struct PartZero {
+  void *ctl;
+  uint32_t ctl_chunks, ops;
+  unsigned long long *desc;
+  uint64_t rows;
+};
+
+/* guided: the co-rank searches place their probes from the coarse neighbours (gt4hip_corank.h); false: plain bisection */
 hipError_t launch_partition (hipStream_t s, const uint32_t *A, uint64_t nA, const uint32_t *B, uint64_t nB,
-                             uint64_t num_tiles, uint64_t tile_records, uint64_t *part);
+                             uint64_t num_tiles, uint64_t tile_records, uint64_t *part, bool guided, const PartZero &zero);
 hipError_t launch_pair_merge (hipStream_t s, const PairVariant &v, int grid, const uint32_t *A, uint64_t nA,
                               const uint32_t *B, uint64_t nB, const uint64_t *part, uint64_t num_tiles,
                               const PairParams &p, const PairOutputs &o, unsigned long long *desc,

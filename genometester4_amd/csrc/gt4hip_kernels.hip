@@ -24,6 +24,7 @@
  */
 #define GT4_RESOLVE_LOOKBACK 3
 #include "gt4hip_device.h"
+#include "gt4hip_corank.h"
 
 #include <type_traits>
 
@@ -124,52 +125,67 @@ __device__ __forceinline__ bool eval_default (u32 kind, u32 fa, u32 fb, u32 cuto
 
 /* ------------------------------------------------------------------ K1: partition */
 
-/* Number of A records among the first `diag` records of merge(A, B) with A first on ties,
- * searched inside [lo, hi] (the caller's bracket must contain the answer). */
-__device__ __forceinline__ u64 merge_path (const u32 *__restrict__ A, u64 nA, const u32 *__restrict__ B, u64 nB, u64 diag, u64 lo, u64 hi)
-{
-  const u64 lo0 = diag > nB ? diag - nB : 0, hi0 = diag < nA ? diag : nA;
-  if (lo < lo0) lo = lo0;
-  if (hi > hi0) hi = hi0;
-  while (lo < hi) {
-    const u64 mid = (lo + hi) >> 1;
-    if (load_key (A, mid) <= load_key (B, diag - 1 - mid)) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-constexpr u64 PART_COARSE = 64; /* tiles per coarse partition interval */
+/* The co-rank search itself is gt4hip_corank.h's (plain C++, shared with the CPU model of the tests); here it reads its
+ * keys from the packed lists. */
+struct KeyOf {
+  const u32 *rec;
+  __device__ __forceinline__ u64 operator() (u64 i) const { return load_key (rec, i); }
+};
 
 /* level 1: the co-rank of every PART_COARSE-th tile boundary, full-range search (few threads) */
-__global__ void k_partition_coarse (const u32 *__restrict__ A, u64 nA, const u32 *__restrict__ B, u64 nB, u64 num_tiles, u64 tile_records, u64 *__restrict__ coarse)
+__global__ void k_partition_coarse (const u32 *__restrict__ A, u64 nA, const u32 *__restrict__ B, u64 nB, u64 num_tiles, u64 tile_records, u64 *__restrict__ coarse,
+                                    int guided)
 {
   const u64 c = (u64) blockIdx.x * blockDim.x + threadIdx.x;
   const u64 n_coarse = (num_tiles + PART_COARSE - 1) / PART_COARSE;
   if (c > n_coarse) return;
-  const u64 total = nA + nB;
-  u64 diag = c * PART_COARSE * tile_records;
-  if (diag > total) diag = total;
-  coarse[c] = merge_path (A, nA, B, nB, diag, 0, nA);
+  coarse[c] = corank_coarse_boundary (KeyOf{ A }, nA, KeyOf{ B }, nB, tile_records, c, guided != 0);
+}
+
+/* 16-byte chunk j of a launch's zeroing job (PartZero, gt4hip_internal.h), nullptr behind its last one */
+__device__ __forceinline__ u32x4 *zero_chunk (const PartZero &z, u64 j)
+{
+  if (j < z.ctl_chunks) return reinterpret_cast<u32x4 *> (z.ctl) + j;
+  j -= z.ctl_chunks;
+  /* in chunks: agg 4 x rows x 16, carry 4 x (rows + 1) / 2, rowsum 4 x rows / 2 */
+  u32x4 *const agg = reinterpret_cast<u32x4 *> (z.desc), *const carry = agg + z.rows * 64, *const rowsum = carry + 2 * (z.rows + 1);
+#pragma unroll
+  for (u32 s = 0; s < 4; s++) {
+    if (!((z.ops >> s) & 1u)) continue;
+    const u64 n_agg = z.rows * 16;
+    if (j < n_agg) return agg + s * n_agg + j;
+    j -= n_agg;
+    const u64 c0 = (s * (z.rows + 1)) >> 1, c1 = ((s + 1) * (z.rows + 1) + 1) >> 1;
+    if (j < c1 - c0) return carry + c0 + j;
+    j -= c1 - c0;
+    const u64 r0 = (s * z.rows) >> 1, r1 = ((s + 1) * z.rows + 1) >> 1;
+    if (j < r1 - r0) return rowsum + r0 + j;
+    j -= r1 - r0;
+  }
+  return nullptr;
 }
 
 /* level 2: every tile boundary, searched only between its two coarse neighbours (the co-rank
- * is monotone in the diagonal): ~17 dependent reads instead of ~31, and the threads of one
- * coarse interval probe the same few cache lines */
+ * is monotone in the diagonal), guided by them (gt4hip_corank.h): on independent keys about 8 dependent reads per
+ * boundary of 6080-record tiles where bisection makes 16 (the CPU model's counts, profiles/round8/README.md); the
+ * threads of one coarse interval are one wavefront.  The launch also zeroes what the merge launch behind it expects zeroed (PartZero): 16-byte stores dealt
+ * over all its threads, complete before the merge kernel starts (stream order). */
 __global__ void k_partition (const u32 *__restrict__ A, u64 nA, const u32 *__restrict__ B, u64 nB,
-                             u64 num_tiles, u64 tile_records, const u64 *__restrict__ coarse, u64 *__restrict__ part)
+                             u64 num_tiles, u64 tile_records, const u64 *__restrict__ coarse, u64 *__restrict__ part, int guided, PartZero z)
 {
   const u64 t = (u64) blockIdx.x * blockDim.x + threadIdx.x;
+  const u64 threads = (u64) gridDim.x * blockDim.x;
+  for (u64 i = t;; i += threads) { /* (about one chunk per thread and requested stream) */
+    u32x4 *const chunk = zero_chunk (z, i);
+    if (!chunk) break;
+    *chunk = u32x4{ 0u, 0u, 0u, 0u };
+  }
   if (t > num_tiles) return;
-  const u64 total = nA + nB;
-  u64 diag = t * tile_records;
-  if (diag > total) diag = total;
   const u64 c = t / PART_COARSE;
-  u64 a = (t % PART_COARSE) ? merge_path (A, nA, B, nB, diag, coarse[c], coarse[c + 1]) : coarse[c], b = diag - a;
-  /* keys are unique inside a list, so a key present in both lists sits as an adjacent (A, B)
-   * pair in the merged order; if the diagonal falls between them pull the B record back into
-   * the earlier tile so that one tile owns the pair. */
-  if (a > 0 && b < nB && load_key (A, a - 1) == load_key (B, b)) b += 1;
+  uint64_t a, b;
+  /* (the coarse boundary behind the last tile boundary is not written when that one is itself a coarse boundary) */
+  const u64 c_lo = coarse[c], c_hi = (t % PART_COARSE) ? coarse[c + 1] : c_lo;
+  corank_tile_boundary (KeyOf{ A }, nA, KeyOf{ B }, nB, tile_records, t, c_lo, c_hi, guided != 0, &a, &b);
   part[2 * t] = a;
   part[2 * t + 1] = b;
 }
@@ -483,7 +499,10 @@ k_pair_merge (const u32 *__restrict__ A, u64 nA, const u32 *__restrict__ B, u64 
    * where a B-only key can be kept (union, diff2) */
   const bool need_b = (ops & 9u) != 0;
 
-  /* single pass: agg u32[4][rows * 64] then carry u64[4][rows + 1] inside desc (zeroed by the host) */
+  /* single pass: agg u32[4][rows * 64], then carry u64[4][rows + 1], then rowsum u64[4][rows] inside desc.  The partition
+   * launch in front of this one zeroes them (k_partition, PartZero) for the streams in p.ops alone: every read and
+   * every publish below -- scanner, summers and chainer, the speculative loads, resolve_offset -- is of a requested
+   * stream's words and of no other's */
   const u64 n_rows = (num_tiles + WAVE - 1) / WAVE;
   const u32 spin_limit = p.spin_limit ? p.spin_limit : SPIN_LIMIT;
   u32 *const agg = reinterpret_cast<u32 *> (desc);
@@ -1283,15 +1302,16 @@ inline int grid_for (u64 n, int block, int cap)
 /* ------------------------------------------------------------------ host launchers */
 
 hipError_t launch_partition (hipStream_t s, const uint32_t *A, uint64_t nA, const uint32_t *B, uint64_t nB,
-                             uint64_t num_tiles, uint64_t tile_records, uint64_t *part)
+                             uint64_t num_tiles, uint64_t tile_records, uint64_t *part, bool guided, const PartZero &zero)
 {
   /* the coarse table lives behind the (num_tiles + 1) tile ranges in the same workspace */
   u64 *const coarse = (u64 *) part + 2 * (num_tiles + 1);
   const u64 n_coarse = (num_tiles + PART_COARSE - 1) / PART_COARSE + 1;
-  hipLaunchKernelGGL (k_partition_coarse, dim3 ((unsigned) ((n_coarse + 255) / 256)), dim3 (256), 0, s, A, nA, B, nB, num_tiles, tile_records, coarse);
+  hipLaunchKernelGGL (k_partition_coarse, dim3 ((unsigned) ((n_coarse + 255) / 256)), dim3 (256), 0, s, A, nA, B, nB, num_tiles, tile_records, coarse,
+                      guided ? 1 : 0);
   const u64 threads = num_tiles + 1;
   hipLaunchKernelGGL (k_partition, dim3 ((unsigned) ((threads + 255) / 256)), dim3 (256), 0, s, A, nA, B, nB, num_tiles, tile_records,
-                      (const u64 *) coarse, (u64 *) part);
+                      (const u64 *) coarse, (u64 *) part, guided ? 1 : 0, zero);
   return hipGetLastError ();
 }
 

@@ -24,6 +24,23 @@ static size_t desc_bytes_for (uint64_t tiles)
   return std::max (gt4hip_lookback_desc_bytes (tiles), two);
 }
 
+/* What the partition launch of a pair call zeroes for its merge launch (PartZero): the control block, and with `desc` (the
+ * single-pass path) the chained scan's words of the streams in `ops` alone, not of all four. */
+static PartZero pair_zero (gt4hip_context *ctx, uint64_t tiles, uint32_t ops, bool desc)
+{
+  static_assert (sizeof (PairControl) % 16 == 0, "the control block is zeroed in 16-byte chunks");
+  PartZero z;
+  memset (&z, 0, sizeof z);
+  z.ctl = ctx->ctl;
+  z.ctl_chunks = (uint32_t) (sizeof (PairControl) / 16);
+  if (desc) {
+    z.ops = ops;
+    z.desc = ctx->desc;
+    z.rows = (tiles + 63) / 64;
+  }
+  return z;
+}
+
 int gt4hip_run_pair (gt4hip_context *ctx, const uint32_t *A, uint64_t nA, const uint32_t *B, uint64_t nB, const PairParams &p_in,
                      bool count_only, uint32_t *const dst[4], PairRun *run, bool force_two_pass)
 {
@@ -96,9 +113,8 @@ int gt4hip_run_pair (gt4hip_context *ctx, const uint32_t *A, uint64_t nA, const 
 
   hipStream_t st = ctx->stream;
   HIPCHK (ctx, hipEventRecord (ctx->ev[0], st));
-  HIPCHK (ctx, hipMemsetAsync (ctx->ctl, 0, sizeof (PairControl), st));
-  if (need_desc && !two_pass) HIPCHK (ctx, hipMemsetAsync (ctx->desc, 0, desc_bytes_for (tiles), st));
-  HIPCHK (ctx, launch_partition (st, A, nA, B, nB, tiles, tile_records, ctx->part));
+  /* (no fill launches: the partition launch zeroes the control block and the descriptor words this call reads) */
+  HIPCHK (ctx, launch_partition (st, A, nA, B, nB, tiles, tile_records, ctx->part, ctx->part_guided >= 0, pair_zero (ctx, tiles, p.ops, need_desc && !two_pass)));
   HIPCHK (ctx, hipEventRecord (ctx->ev[1], st));
   if (count_only) {
     HIPCHK (ctx, launch_pair_merge (st, v1, grid, A, nA, B, nB, ctx->part, tiles, p, outs, NULL, ctx->ctl));
@@ -117,6 +133,7 @@ int gt4hip_run_pair (gt4hip_context *ctx, const uint32_t *A, uint64_t nA, const 
   float ms = 0;
   if (hipEventElapsedTime (&ms, ctx->ev[1], ctx->ev[2]) == hipSuccess) run->merge_ms = ms;
   if (hipEventElapsedTime (&ms, ctx->ev[0], ctx->ev[3]) == hipSuccess) run->device_ms = ms;
+  if (hipEventElapsedTime (&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->partition_ms = ms;
 PROF (
   {
     static const char *names[8] = { "p0 wait+lds", "B0", "ring+fetch issue", "p1 rank", "B1", "p2 scan/publish", "B2+out+B3+scatter", "housekeeping" };
@@ -144,6 +161,22 @@ PROF (
     run->total_count[s] = ctx->ctl_host->total_count[s];
   }
   return GT4HIP_OK;
+}
+
+extern "C" int gt4hip_pair_partition (gt4hip_context *ctx, const gt4hip_list *a, const gt4hip_list *b, uint64_t tile_records, uint64_t *host_part)
+{
+  if (!ctx || !a || !b || !host_part || !tile_records) return GT4HIP_EINVAL;
+  if (a->word_length != b->word_length) return gt4hip_fail (ctx, GT4HIP_EWORDLEN, "word lengths differ (%u != %u)", b->word_length, a->word_length);
+  HIPCHK (ctx, hipSetDevice (ctx->device));
+  const uint64_t tiles = (a->n_words + b->n_words + tile_records - 1) / tile_records;
+  if (tiles >= 0xffffffffull) return gt4hip_fail (ctx, GT4HIP_EINVAL, "lists too long: %llu merge tiles", (unsigned long long) tiles);
+  int rc;
+  if ((rc = gt4hip_grow (ctx, (void **) &ctx->part, &ctx->part_bytes, (size_t) (tiles + 1) * 16 + (size_t) (tiles / 64 + 3) * 8))) return rc;
+  PartZero none;
+  memset (&none, 0, sizeof none);
+  HIPCHK (ctx, launch_partition (ctx->stream, (const uint32_t *) a->dev, a->n_words, (const uint32_t *) b->dev, b->n_words, tiles, tile_records, ctx->part,
+                                 ctx->part_guided >= 0, none));
+  return gt4hip_read_back (ctx, host_part, ctx->part, (size_t) (tiles + 1) * 16, "gt4hip_pair_partition: reading the tile ranges back failed");
 }
 
 static uint64_t worst_case (int s, uint64_t nA, uint64_t nB)

@@ -643,10 +643,15 @@ int gt4hip_synchronize (gt4hip_context *ctx);
  *   "a_rows" = 0 / -1  single-pass intersection and first complement: a tile whose first-list records fit half
  *                      of the workgroup's position rows is ranked by the body compiled for those rows alone /
  *                      every tile by the general body (experiments, tests)
+ *   "part_guided" = 0 / -1  the pair partition's co-rank searches place their first probes from the coarse
+ *                      neighbours' ranks and the probed keys (gt4hip_corank.h: fewer scattered reads on keys that
+ *                      are locally uniform, never more than bisection's and four) / plain bisection; the tile
+ *                      ranges are the same either way
  *   "geom0" / "geom1"  force the 512- / 1024-thread geometry (experiments). */
 int gt4hip_set_option (gt4hip_context *ctx, const char *name, int64_t value);
 /* Diagnostic counters of a context.  "single_pass_fallbacks": calls whose single-pass merge gave up a
  * bounded wait (a worker not resident: shared device) and were rerun on the two-pass path;
+ * "partition_us": the partition launch of the context's last pair merge (HIP events around it; it also zeroes the merge's workspace);
  * "kway_declined": N-way unions handed to the pairwise tree because their keys are clustered;
  * "kway_calls" / "kway_overflows": N-way unions (and count tables) done by the one-pass tile kernel /
  * partitions repeated with fewer samples per tile because a tile would not have fit LDS;
@@ -663,6 +668,11 @@ int gt4hip_set_option (gt4hip_context *ctx, const char *name, int64_t value);
  * "subset_tile": items per tile of its kernels; "subset_us": its device time (HIP events around the kernels, the one
  * word read back per pass included). */
 int gt4hip_get_counter (gt4hip_context *ctx, const char *name, uint64_t *value);
+/* Diagnostic: the partition launch of a pair merge alone, with tiles of tile_records merged records (any length: tests cut
+ * small lists into many tiles).  host_part receives 2 x (tiles + 1) words, tiles = ceil ((|a| + |b|) / tile_records):
+ * boundary t = {records of a, records of b} before tile t, first list first on equal keys, the second list's record of a
+ * pair that the diagonal cuts pulled into the earlier tile.  Follows option "part_guided". */
+int gt4hip_pair_partition (gt4hip_context *ctx, const gt4hip_list *a, const gt4hip_list *b, uint64_t tile_records, uint64_t *host_part);
 
 #ifdef __cplusplus
 }

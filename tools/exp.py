@@ -35,7 +35,7 @@ from genometester4_amd import capi, synth  # noqa: E402
 
 
 def _opts(ctx):
-    for opt in ("scan_group", "dynamic", "spin_limit", "kway_g", "kway_vt", "grid", "geom0", "geom1", "two_pass", "a_rows"):
+    for opt in ("scan_group", "dynamic", "spin_limit", "kway_g", "kway_vt", "grid", "geom0", "geom1", "two_pass", "a_rows", "part_guided"):
         if os.environ.get(opt.upper()):
             ctx.set_option(opt, int(os.environ[opt.upper()]))
 
