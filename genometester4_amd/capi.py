@@ -19,6 +19,7 @@ OK = 0
 EINVAL, ENODEVICE, ENOMEM, ERULE, EHIP, EWORDLEN, EINTERNAL = 1, 2, 3, 4, 5, 6, 7
 EFORMAT = 11
 MAKER_FORWARD_ONLY, MAKER_TEXT_ON_DEVICE = 1, 2
+GMER_ON_DEVICE, GMER_PLAIN_ATOMICS = 2, 4
 MAKER_ERR_START, MAKER_ERR_PLUS, MAKER_ERR_AT, MAKER_ERR_PLUS_EOF = 1, 2, 3, 4
 OP_UNION, OP_INTRSEC, OP_DIFF1, OP_DIFF2 = 1, 2, 4, 8
 RULE_DEFAULT, RULE_ADD, RULE_SUBTRACT, RULE_MIN, RULE_MAX, RULE_FIRST, RULE_SECOND, RULE_NUMBER = range(8)
@@ -62,6 +63,11 @@ QUERY_HIT_DTYPE = np.dtype([("query", "<u8"), ("rank", "<u8"), ("word", "<u8"), 
 class MakerCarry(C.Structure):
     _fields_ = [("file_type", C.c_uint32), ("in_name", C.c_uint32), ("line_phase", C.c_uint32), ("at_line_start", C.c_uint32),
                 ("ended", C.c_uint32), ("error", C.c_uint32), ("codes", C.c_uint8 * 32)]
+
+
+class GmerStats(C.Structure):
+    _fields_ = [("n_n", C.c_uint64), ("n_nucl", C.c_uint64), ("n_gc", C.c_uint64), ("n_words", C.c_uint64), ("n_hits", C.c_uint64),
+                ("n_kmer_gc", C.c_uint64)]
 
 
 class Subseq(C.Structure):
@@ -124,6 +130,8 @@ SYMBOLS = [
     "gt4hip_list_subset", "gt4hip_subset_state_at",
     "gt4hip_text_to_locations", "gt4hip_locations_free", "gt4hip_pack_locations", "gt4hip_pairs_reserve", "gt4hip_pairs_release",
     "gt4hip_pair_partition",
+    "gt4hip_gmer_db_create", "gt4hip_gmer_db_free", "gt4hip_gmer_db_n_kmers", "gt4hip_gmer_db_last_ms", "gt4hip_gmer_count_words",
+    "gt4hip_gmer_count_text", "gt4hip_gmer_counts_download", "gt4hip_gmer_counts_reset",
 ]
 
 _lib = None
@@ -236,6 +244,15 @@ def lib():
             "gt4hip_list_subset": (C.c_int, [vp, vp, C.POINTER(SubsetParams), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]),
             "gt4hip_subset_state_at": (u64, [u64, u64]),
             "gt4hip_pair_partition": (C.c_int, [vp, vp, vp, u64, vp]),
+            "gt4hip_gmer_db_create": (C.c_int, [vp, vp, u64, u32, C.POINTER(vp)]),
+            "gt4hip_gmer_db_free": (None, [vp]),
+            "gt4hip_gmer_db_n_kmers": (u64, [vp]),
+            "gt4hip_gmer_db_last_ms": (C.c_double, [vp]),
+            "gt4hip_gmer_count_words": (C.c_int, [vp, vp, vp, u64, C.c_uint, C.POINTER(u64), C.POINTER(u64)]),
+            "gt4hip_gmer_count_text": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_uint, C.POINTER(MakerCarry), C.POINTER(MakerCarry),
+                                                 C.POINTER(GmerStats), C.POINTER(u64)]),
+            "gt4hip_gmer_counts_download": (C.c_int, [vp, vp, u64, u64, vp]),
+            "gt4hip_gmer_counts_reset": (C.c_int, [vp, vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -484,6 +501,61 @@ class LocationIndex:
             pass
 
 
+class GmerDb:
+    """A k-mer database resident on the device with a 64-bit counter per k-mer (gt4hip_gmer_db)."""
+
+    def __init__(self, ctx: "Context", words, word_length):
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        self.ctx, self.h, self.word_length = ctx, C.c_void_p(), word_length
+        ctx._chk(lib().gt4hip_gmer_db_create(ctx.h, w.ctypes.data if len(w) else None, len(w), word_length, C.byref(self.h)))
+        ctx._lists.add(self)
+
+    @property
+    def n_kmers(self):
+        return lib().gt4hip_gmer_db_n_kmers(self.h)
+
+    def count_words(self, words, flags=0, n=None):
+        """(hits, GC term) of one batch; `words`: a uint64 array, or with GMER_ON_DEVICE the address of `n` device words"""
+        hits, gc = C.c_uint64(), C.c_uint64()
+        if flags & GMER_ON_DEVICE:
+            ptr = C.c_void_p(words)
+        else:
+            w = np.ascontiguousarray(words, dtype=np.uint64)
+            ptr, n = (w.ctypes.data if len(w) else None), len(w)
+        self.ctx._chk(lib().gt4hip_gmer_count_words(self.ctx.h, self.h, ptr, n, flags, C.byref(hits), C.byref(gc)))
+        return hits.value, gc.value
+
+    def count_text(self, text, carry=None, flags=0, stats=True):
+        """(GmerStats | None, carry for the next piece) of one piece of a file (gt4hip_gmer_count_text); malformed text raises
+        Gt4HipError with code EFORMAT, `error_offset` and `kind` as Context.text_to_words does"""
+        out, st, at = MakerCarry(), GmerStats(), C.c_uint64()
+        buf = (C.c_char * max(len(text), 1)).from_buffer_copy(bytes(text) or b"\0")
+        rc = lib().gt4hip_gmer_count_text(self.ctx.h, self.h, buf, len(text), flags, C.byref(carry) if carry is not None else None, C.byref(out),
+                                          C.byref(st) if stats else None, C.byref(at))
+        if rc:
+            e = Gt4HipError(rc, lib().gt4hip_last_error(self.ctx.h).decode())
+            e.error_offset, e.kind = at.value, out.error
+            raise e
+        return (st if stats else None), out
+
+    def counts(self, first=0, n=None):
+        n = self.n_kmers - first if n is None else n
+        out = np.empty(n, dtype=np.uint64)
+        self.ctx._chk(lib().gt4hip_gmer_counts_download(self.ctx.h, self.h, first, n, out.ctypes.data if n else None))
+        return out
+
+    def reset(self):
+        self.ctx._chk(lib().gt4hip_gmer_counts_reset(self.ctx.h, self.h))
+
+    def last_ms(self):
+        return lib().gt4hip_gmer_db_last_ms(self.h)
+
+    def free(self):
+        if self.h:
+            lib().gt4hip_gmer_db_free(self.h)
+            self.h = None
+
+
 class Context:
     def __init__(self, device=0):
         import weakref
@@ -531,6 +603,10 @@ class Context:
         out = (C.c_uint64 * n_shards)()
         self._chk(lib().gt4hip_shard_cuts(self.h, arr, len(lists), n_shards, out))
         return [int(x) for x in out]
+
+    def gmer_db(self, words, word_length) -> "GmerDb":
+        """Database k-mers (one word each, either strand) -> a device db with a counter per k-mer (gt4hip_gmer_db_create)."""
+        return GmerDb(self, words, word_length)
 
     def words_to_list(self, words, word_length) -> "DeviceList":
         """Packed k-mer words (any order, repeats) -> sorted (word, occurrences) list on the device."""

@@ -181,6 +181,15 @@ void gt4hip_io_destroy (gt4hip_context *ctx);
 #define GT4HIP_MAKER_TILE 4096u
 /* items per tile of gt4hip_subset.hip's decision kernels (counter "subset_tile") */
 #define GT4HIP_SUBSET_TILE 4096u
+/* gt4hip_text_to_words (gt4hip_maker.hip) for gt4hip_gmer.hip: with `counts`, one more pass over the piece's bytes and codes
+ * sets counts[0..2] = 'N' / 'n' among the bytes the reference's reader loop takes (all in front of a NUL but FastQ '+'
+ * lines), bases of sequence lines, and C / G among those (read_character and read_nucleotide, src/gmer_counter.c:917-936) */
+GT4HIP_LOCAL int gt4hip_text_to_words_counted (gt4hip_context *ctx, const void *text, size_t n_bytes, unsigned word_length, unsigned flags,
+                                               const gt4hip_maker_carry *in, gt4hip_maker_carry *out, uint64_t **d_words, uint64_t *n_words,
+                                               uint64_t *error_offset, uint64_t counts[3]);
+/* gt4hip_gmer.hip: k_mk_text_counts on the arrays of a reader call (text, tile states, codes, MakerInfo); out: three zeroed device words */
+GT4HIP_LOCAL void gt4hip_launch_text_counts (hipStream_t stream, int grid, bool fastq, const unsigned char *d_text, size_t n_bytes, uint64_t tiles,
+                                             const uint32_t *tile_state, const unsigned char *codes, const void *info, unsigned long long *out);
 int gt4hip_io_download (gt4hip_context *ctx, const void *dev, void *host, size_t bytes);
 /* host memory (a file mapping, say) -> device memory, waited for: large extents in pieces through the staging threads */
 int gt4hip_io_upload (gt4hip_context *ctx, const void *host, void *dev, size_t bytes);

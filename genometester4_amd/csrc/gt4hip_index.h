@@ -104,7 +104,7 @@ __global__ __launch_bounds__ (MM_THREADS) void k_index_build (const u32 *rec, u6
 }
 
 /* exclusive scan of the tile counts (one workgroup), total in *total */
-__global__ __launch_bounds__ (1024) void k_tile_scan (const u32 *tile_cnt, u64 n_tiles, u64 *tile_off, unsigned long long *total)
+[[maybe_unused]] __global__ __launch_bounds__ (1024) void k_tile_scan (const u32 *tile_cnt, u64 n_tiles, u64 *tile_off, unsigned long long *total)
 {
   __shared__ u64 wsum[1024 / WAVE];
   __shared__ u64 carry;

@@ -25,7 +25,8 @@
  *
  * What sibling kernels share is written once, as inline functions: tile_head (the reader's state at a thread's first byte:
  * k_mk_codes, k_mk_events), load_word_ends and for_each_word (where words end, and the walk over them: k_mk_emit,
- * k_mk_emit_loc), block_scan (all of them and k_mk_summary).  The host half is one MakerCall handed through stages.
+ * k_mk_emit_loc), block_scan (all of them and k_mk_summary).  The tile geometry, tile_head and block_scan live in
+ * gt4hip_maker_tile.h, which gt4hip_gmer.hip's statistics pass shares.  The host half is one MakerCall handed through stages.
  *
  * k_tile_count of gt4hip_index.h is not used: it counts a 4-byte flag per item, which would cost more traffic than
  * the text itself; the counts here come out of the classification.  Algorithmic bytes per text byte: 1 + 1 read, 1
@@ -34,6 +35,7 @@
 #include "gt4hip_device.h"
 #include "gt4hip_host.h"
 #include "gt4hip_index.h"
+#include "gt4hip_maker_tile.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -41,115 +43,11 @@
 namespace gt4 {
 namespace {
 
-constexpr int MK_THREADS = 256;
-constexpr int MK_PER = 16;                              /* bytes (codes) per thread */
-constexpr u64 MK_TILE = (u64) MK_THREADS * MK_PER;      /* bytes of text per tile; codes per tile of the emit stage */
-constexpr int MK_HALO = 32;                             /* codes in front of the first: the carry of the piece before */
-static_assert (MK_TILE == GT4HIP_MAKER_TILE, "what the counters maker_text_tile / maker_code_tile report");
-
-/* what the kernels hand to the host, and k_mk_summary to the kernels behind it */
-struct MakerInfo {
-  u64 nul_pos;  /* offset of the first NUL (the reference's end of file), n when there is none */
-  u64 err;      /* smallest (offset << 3 | GT4HIP_MAKER_ERR_*), ~0 when the text is well formed */
-  u64 n_codes;  /* codes of the text in front of nul_pos */
-  u64 n_words;
-  u32 in_name, phase, at_line_start, pad; /* the carries behind the last byte */
-  /* gt4hip_text_to_locations alone (behind what the kernels of gt4hip_text_to_words read and write) */
-  u64 n_events;  /* name starts, sequence starts and (FastQ) sequence ends of the text */
-  u64 max_pos;   /* largest position of a word */
-  u64 overflow;  /* a word's ordinal or position does not fit its raw field */
-};
-
-/* 16 bytes of text at `off` as four dwords; bytes at `limit` and behind read as 0 */
-__device__ __forceinline__ void load16 (const unsigned char *__restrict__ text, u64 limit, u64 off, u32 w[4])
-{
-  if (off + MK_PER <= limit) {
-    const u32x4 v = *(const u32x4 *) (text + off);
-    w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
-  } else {
-    w[0] = w[1] = w[2] = w[3] = 0;
-#pragma unroll
-    for (int i = 0; i < MK_PER; i++)
-      if (off + i < limit) w[i >> 2] |= (u32) text[off + i] << (8 * (i & 3));
-  }
-}
-
-#define MK_BYTE(w, j) (((w)[(j) >> 2] >> (8 * ((j) & 3))) & 0xffu)
-
 /* c2n of src/fasta.c:66-69, 4 for everything else */
 __device__ __forceinline__ u32 nuc_code (u32 c)
 {
   c |= 0x20u;
   return c == 'a' ? 0u : c == 'c' ? 1u : c == 'g' ? 2u : (c == 't' || c == 'u') ? 3u : 4u;
-}
-
-/* a thread's 16 bytes: bytes >= ' ', '\n's, and whether a '>' stands behind the last '\n' (anywhere when there is none) */
-__device__ __forceinline__ void scan16 (const u32 w[4], u32 *kept, u32 *nl, u32 *tail)
-{
-  u32 k = 0, l = 0, t = 0;
-#pragma unroll
-  for (int j = 0; j < MK_PER; j++) {
-    const u32 c = MK_BYTE (w, j);
-    k += c >= 0x20u;
-    if (c == '\n') l++, t = 0;
-    if (c == '>') t = 1;
-  }
-  *kept = k, *nl = l, *tail = t;
-}
-
-/* (has a '\n', '>' behind the last '\n') of the lanes of a wavefront taken together */
-__device__ __forceinline__ void wave_line_state (u64 m_nl, u64 m_tail, u32 *has, u32 *tail)
-{
-  *has = m_nl != 0;
-  *tail = m_nl ? (m_tail >> (63 - __builtin_clzll (m_nl))) != 0 : m_tail != 0;
-}
-
-/* v summed over the workgroup's threads in front of this one, and over all of them; s_sum: MK_THREADS / WAVE words of LDS
- * that are free again at the caller's next barrier */
-struct BlockScan { u32 before, total; };
-__device__ __forceinline__ BlockScan block_scan (u32 v, u32 *s_sum)
-{
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-  const u32 incl = dpp_inclusive_scan_u32 (v);
-  if (lane == WAVE - 1) s_sum[wv] = incl;
-  __syncthreads ();
-  BlockScan r = { incl - v, 0 };
-  for (int i = 0; i < MK_THREADS / WAVE; i++) {
-    if (i < wv) r.before += s_sum[i];
-    r.total += s_sum[i];
-  }
-  return r;
-}
-
-/* The state of the reader (src/fasta.c's machine) at a thread's first byte of tile t, from the thread's bytes, the
- * workgroup's and the tile's carries: what k_mk_codes and k_mk_events start their byte loops from. */
-struct TileHead {
-  u32 w[4];               /* the thread's 16 bytes, 0 at n_eff and behind */
-  u32 rank, n_codes;      /* bytes >= ' ' of the tile in front of the thread, and of the whole tile */
-  u32 phase, name;        /* lines so far mod 4; in a name */
-};
-__device__ __forceinline__ TileHead tile_head (const unsigned char *__restrict__ text, u64 n_eff, u64 off, const u32 *tile_state, u32 *s_sum, u32 *s_has, u32 *s_tail)
-{
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-  TileHead h;
-  u32 kept, nl, tail;
-  load16 (text, n_eff, off, h.w);
-  scan16 (h.w, &kept, &nl, &tail);
-  const u64 m_nl = __builtin_amdgcn_ballot_w64 (nl != 0), m_tail = __builtin_amdgcn_ballot_w64 (tail != 0);
-  u32 has, wt;
-  wave_line_state (m_nl, m_tail, &has, &wt);
-  if (lane == 0) s_has[wv] = has, s_tail[wv] = wt;
-  const BlockScan sc = block_scan (kept | (nl << 16), s_sum); /* both at most 4096 per tile */
-  const u32 st = *tile_state;
-  h.name = st & 1u;
-  for (int i = 0; i < MK_THREADS / WAVE; i++)
-    if (i < wv) h.name = s_has[i] ? s_tail[i] : (h.name | s_tail[i]);
-  const u64 below = ((u64) 1 << lane) - 1, b_nl = m_nl & below, b_tail = m_tail & below;
-  h.name = b_nl ? (b_tail >> (63 - __builtin_clzll (b_nl))) != 0 : (h.name | (b_tail != 0));
-  h.rank = sc.before & 0xffffu;
-  h.phase = ((st >> 1) + (sc.before >> 16)) & 3u;
-  h.n_codes = sc.total & 0xffffu;
-  return h;
 }
 
 __global__ __launch_bounds__ (MK_THREADS) void k_mk_summary (const unsigned char *__restrict__ text, u64 n, u64 n_tiles, u32 *tile_cnt, u32 *tile_info,
@@ -736,6 +634,19 @@ int maker_totals (MakerCall &m)
   return GT4HIP_OK;
 }
 
+/* gmer_counter's statistics of the piece (k_mk_text_counts, gt4hip_gmer.hip), behind the totals: the codes are in place */
+int maker_text_counts (MakerCall &m, uint64_t counts[3])
+{
+  gt4hip_context *const ctx = m.ctx;
+  unsigned long long *d = NULL;
+  const int rc = m.blk.get (ctx, 3 * 8, (void **) &d);
+  if (rc) return rc;
+  HIPCHK (ctx, hipMemsetAsync (d, 0, 3 * 8, ctx->stream));
+  gt4hip_launch_text_counts (ctx->stream, m.grid, m.c.file_type == GT4HIP_MAKER_FASTQ, m.d_text, m.n_bytes, m.tiles, m.tile_state, m.buf + MK_HALO, m.info, d);
+  HIPCHK (ctx, hipGetLastError ());
+  return gt4hip_read_back (ctx, counts, d, 3 * 8, "reading the text's statistics back failed");
+}
+
 /* the kernels alone: events 0 to 1 and 2 to 3, neither the read-back of the totals nor the allocation of the words between them */
 void record_extract_ms (gt4hip_context *ctx)
 {
@@ -799,13 +710,15 @@ int maker_emit_locations (MakerCall &m)
 /* gt4hip_text_to_words; with `loc`, gt4hip_text_to_locations: the same stages up to the words' count, then the events and
  * k_mk_emit_loc into the caller's arrays instead of k_mk_emit<true> into a block of the context */
 int text_to_words (gt4hip_context *ctx, const void *text, size_t n_bytes, unsigned word_length, unsigned flags, const gt4hip_maker_carry *in,
-                   gt4hip_maker_carry *out, uint64_t **d_words, uint64_t *n_words, uint64_t *error_offset, LocCall *loc)
+                   gt4hip_maker_carry *out, uint64_t **d_words, uint64_t *n_words, uint64_t *error_offset, LocCall *loc, uint64_t *counts = NULL)
 {
   gt4hip_maker_carry dummy;
   MakerCall m = { ctx, text, n_bytes, word_length, flags, out ? out : &dummy, d_words, n_words, error_offset, loc };
+  if (counts) counts[0] = counts[1] = counts[2] = 0;
   int rc = maker_begin (m, in);
   if (rc == MK_DONE) return loc ? finish_locations (ctx, loc, m.out, NULL, 0, 0, loc->in ? loc->in->offset : 0, 0) : GT4HIP_OK;
   if (rc || (rc = maker_classify_count (m)) || (rc = maker_totals (m))) return rc;
+  if (counts && (rc = maker_text_counts (m, counts))) return rc;
   return loc ? maker_emit_locations (m) : maker_emit_words (m);
 }
 
@@ -822,6 +735,12 @@ extern "C" int gt4hip_text_to_words (gt4hip_context *ctx, const void *text, size
                                      gt4hip_maker_carry *out, uint64_t **d_words, uint64_t *n_words, uint64_t *error_offset)
 {
   return text_to_words (ctx, text, n_bytes, word_length, flags, in, out, d_words, n_words, error_offset, NULL);
+}
+
+int gt4hip_text_to_words_counted (gt4hip_context *ctx, const void *text, size_t n_bytes, unsigned word_length, unsigned flags, const gt4hip_maker_carry *in,
+                                  gt4hip_maker_carry *out, uint64_t **d_words, uint64_t *n_words, uint64_t *error_offset, uint64_t counts[3])
+{
+  return text_to_words (ctx, text, n_bytes, word_length, flags, in, out, d_words, n_words, error_offset, NULL, counts);
 }
 
 extern "C" int gt4hip_text_to_locations (gt4hip_context *ctx, const void *text, size_t n_bytes, unsigned word_length, unsigned flags, const gt4hip_locations_carry *in,

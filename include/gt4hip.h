@@ -602,6 +602,56 @@ int gt4hip_pack_locations (gt4hip_context *ctx, uint64_t *d_raw, uint64_t n, uin
 int gt4hip_pairs_reserve (gt4hip_context *ctx, uint64_t n_pairs, uint64_t **d_words, uint64_t **d_values);
 void gt4hip_pairs_release (gt4hip_context *ctx);
 
+/* ---------------------------------------------------------------- gmer_counter: database k-mers counted in reads */
+
+/* A k-mer database resident in HBM (reference src/database.c, src/gmer_counter.c:751-815, without the trie): the
+ * canonical words sorted into 12-byte list records that carry the k-mer's index where a list keeps its count, the bucket
+ * index of those records, and one 64-bit counter per k-mer.  Counters never saturate here: clamping to 16 or 32 bits is the
+ * caller's (the reference stops at 65535, or at 0xffffffff with -32). */
+typedef struct gt4hip_gmer_db gt4hip_gmer_db;
+enum {
+  GT4HIP_GMER_ON_DEVICE = 2,     /* `words` / `text` is device memory (the bit of GT4HIP_MAKER_TEXT_ON_DEVICE)                   */
+  GT4HIP_GMER_PLAIN_ATOMICS = 4  /* every hit its own atomic; default: a wavefront whose hits all fall on ONE k-mer adds their
+                                    number with one atomic (a read of one repeated base), any other wavefront one atomic per hit */
+};
+/* Word i of host_words (n_kmers < 2^32 words below 4^word_length, any order, either strand) owns counter i.  On the device:
+ * canonicalised, sorted with the index as the value (gt4hip_sort_pairs), packed and indexed; the counters start at 0.  Two
+ * words with the same canonical form (a word and its own reverse complement too) are GT4HIP_EINVAL -- the message names
+ * both indices -- found by the kernel that packs the sorted words; nothing is made then.  Free the db before its context. */
+int gt4hip_gmer_db_create (gt4hip_context *ctx, const uint64_t *host_words, uint64_t n_kmers, uint32_t word_length, gt4hip_gmer_db **db);
+void gt4hip_gmer_db_free (gt4hip_gmer_db *db);
+uint64_t gt4hip_gmer_db_n_kmers (const gt4hip_gmer_db *db);
+/* One probe of the bucket index per word, the words looked up as they stand (canonical already, as the reader leaves them);
+ * a hit is one 64-bit atomic add on its k-mer's counter.  *n_hits (may be NULL): words found; *kmer_gc (may be NULL): the
+ * sum over the hits of (w ^ w >> 1) & 1 -- what the reference's n_kmer_gc gains per hit, divided by the word length
+ * (src/gmer_counter.c:799-803 reloads the word inside its loop).  Both are reduced per wavefront, one atomic each per
+ * wavefront and launch.  `flags`: GT4HIP_GMER_ON_DEVICE, GT4HIP_GMER_PLAIN_ATOMICS. */
+int gt4hip_gmer_count_words (gt4hip_context *ctx, gt4hip_gmer_db *db, const uint64_t *words, uint64_t n_words, unsigned flags,
+                             uint64_t *n_hits, uint64_t *kmer_gc);
+/* Device time (HIP events) of the counting kernel of the last gt4hip_gmer_count_words / _count_text on this db. */
+double gt4hip_gmer_db_last_ms (const gt4hip_gmer_db *db);
+
+/* what a piece of text gave (gmer_counter --stats, src/gmer_counter.c:412-419, :767-804) */
+typedef struct {
+  uint64_t n_n;        /* 'N' / 'n' among the bytes the reader's loop takes: every byte in front of a NUL but FastQ '+' lines  */
+  uint64_t n_nucl;     /* bases of sequence lines (the reader's codes 0..3)                                                    */
+  uint64_t n_gc;       /* ... that are C or G                                                                                  */
+  uint64_t n_words;    /* words read                                                                                           */
+  uint64_t n_hits;     /* ... found in the database                                                                            */
+  uint64_t n_kmer_gc;  /* word length x the kmer_gc of gt4hip_gmer_count_words: the reference's n_kmer_gc                      */
+} gt4hip_gmer_stats;
+
+/* gt4hip_text_to_words on a piece of a file, then the counting kernel on its words, which never leave the device.  The carry
+ * and the errors of the text are gt4hip_text_to_words's.  `stats` (may be NULL) is SET to what this piece gave; its first
+ * three fields cost one more streaming pass over the piece's bytes and codes, with the reader's own classification: pieces
+ * cut anywhere add up to what the whole text gives.  `flags`: GT4HIP_GMER_ON_DEVICE (16-byte aligned), GT4HIP_GMER_PLAIN_ATOMICS. */
+int gt4hip_gmer_count_text (gt4hip_context *ctx, gt4hip_gmer_db *db, const void *text, size_t n_bytes, unsigned flags,
+                            const gt4hip_maker_carry *carry_in, gt4hip_maker_carry *carry_out, gt4hip_gmer_stats *stats,
+                            uint64_t *error_offset);
+/* Counters [first, first + n) -> host memory; all counters back to 0. */
+int gt4hip_gmer_counts_download (gt4hip_context *ctx, const gt4hip_gmer_db *db, uint64_t first, uint64_t n, uint64_t *host_counts);
+int gt4hip_gmer_counts_reset (gt4hip_context *ctx, gt4hip_gmer_db *db);
+
 /* ---------------------------------------------------------------- synthetic lists (bench) */
 
 /* Fills `list` (capacity >= n) with n strictly ascending keys < 4^word_length and counts in
