@@ -132,6 +132,7 @@ SYMBOLS = [
     "gt4hip_pair_partition",
     "gt4hip_gmer_db_create", "gt4hip_gmer_db_free", "gt4hip_gmer_db_n_kmers", "gt4hip_gmer_db_last_ms", "gt4hip_gmer_count_words",
     "gt4hip_gmer_count_text", "gt4hip_gmer_counts_download", "gt4hip_gmer_counts_reset",
+    "gt4hip_select_multi", "gt4hip_table_select",
 ]
 
 _lib = None
@@ -253,6 +254,8 @@ def lib():
                                                  C.POINTER(GmerStats), C.POINTER(u64)]),
             "gt4hip_gmer_counts_download": (C.c_int, [vp, vp, u64, u64, vp]),
             "gt4hip_gmer_counts_reset": (C.c_int, [vp, vp]),
+            "gt4hip_select_multi": (C.c_int, [vp, C.POINTER(vp), u32, u32, u32, u32, i32, u32, i32, C.POINTER(MultiResult)]),
+            "gt4hip_table_select": (C.c_int, [vp, C.POINTER(CountTable), u32, u32, u32, i32, u32, i32, C.POINTER(MultiResult)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -554,6 +557,50 @@ class GmerDb:
         if self.h:
             lib().gt4hip_gmer_db_free(self.h)
             self.h = None
+
+
+class DeviceTable:
+    """Owning handle of a gt4hip_count_table of gt4hip_union_table that stays on the device."""
+
+    def __init__(self, ctx: "Context", lists):
+        self.ctx, self.t = ctx, CountTable()
+        arr = (C.c_void_p * len(lists))(*[l.h for l in lists])
+        ctx._chk(lib().gt4hip_union_table(ctx.h, arr, len(lists), C.byref(self.t)))
+        self.live = True
+        ctx._lists.add(self)
+
+    @property
+    def n_keys(self):
+        return self.t.n_keys
+
+    @property
+    def n_lists(self):
+        return self.t.n_lists
+
+    @property
+    def ragged(self) -> bool:
+        return bool(self.t.ragged)
+
+    def compact(self):
+        self.ctx._chk(lib().gt4hip_table_compact(self.ctx.h, C.byref(self.t)))
+
+    def download(self):
+        keys = np.empty(self.t.n_keys, dtype=np.uint64)
+        counts = np.empty((self.t.n_keys, self.t.n_lists), dtype=np.uint32)
+        if self.t.n_keys:
+            self.ctx._chk(lib().gt4hip_table_download(self.ctx.h, C.byref(self.t), 0, self.t.n_keys, keys.ctypes.data, counts.ctypes.data))
+        return keys, counts
+
+    def free(self):
+        if self.live and self.ctx.h:
+            lib().gt4hip_table_free(C.byref(self.t))
+        self.live = False
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class Context:
@@ -869,6 +916,23 @@ class Context:
 
     def intersect_multi(self, lists, cutoff=1, rule=0, count_override=1, count_only=False, out=None):
         return self._multi(lib().gt4hip_intersect_multi, lists, cutoff, rule, count_override, count_only, out)
+
+    def select_multi(self, lists, min_lists, max_lists, cutoff=1, rule=0, count_override=1, count_only=False, out=None):
+        """The records of union_multi whose word lies in min_lists .. max_lists of the lists (gt4hip_select_multi); returns
+        what union_multi returns."""
+        def fn(h, arr, n, cutoff_, rule_, ovr, co, res):
+            return lib().gt4hip_select_multi(h, arr, n, min_lists, max_lists, cutoff_, rule_, ovr, co, res)
+        return self._multi(fn, lists, cutoff, rule, count_override, count_only, out)
+
+    def device_table(self, lists) -> "DeviceTable":
+        """gt4hip_union_table, the table left on the device (ragged or contiguous, as the library built it)."""
+        return DeviceTable(self, lists)
+
+    def table_select(self, table: "DeviceTable", min_lists, max_lists, cutoff=1, rule=0, count_override=1, count_only=False, out=None):
+        """gt4hip_table_select on a resident table, which stays as it is; returns what union_multi returns."""
+        def fn(h, arr, n, cutoff_, rule_, ovr, co, res):
+            return lib().gt4hip_table_select(h, C.byref(table.t), min_lists, max_lists, cutoff_, rule_, ovr, co, res)
+        return self._multi(fn, [], cutoff, rule, count_override, count_only, out)
 
     def union_table(self, lists, probe=False, presence=False, compact=False):
         """(keys, counts) of the count table; compact: through gt4hip_table_compact first (a ragged table made

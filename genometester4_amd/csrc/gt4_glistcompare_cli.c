@@ -26,6 +26,12 @@
  *     call; every worker writes its own extents of the output files).  Inputs of 4 GiB and more, or that
  *     do not fit the device memory, stream through the GPU in key-range chunks.  Outputs are
  *     byte-identical to the single-pass run;
+ *   - -u --min_lists M [--max_lists X] (not in the reference; gt4hip_select_multi) writes the records of the union -- same
+ *     -r rule, same -c cutoff -- whose word lies in at least M and at most X of the N input files, to
+ *     <out>_<k>_select_<M>_<X>.list; either option alone is enough (M = 1, X = N otherwise), two files take the N-way path
+ *     too.  --count_only prints the two lines of -u --count_only for the selected list; -D adds nothing; --gpus and
+ *     GT4HIP_HBM_LIMIT work as for -u.  Before any device is opened, one "Error: ..." line and exit 1 for: the options without
+ *     -u or together with -i, -d, -dd, -du, -mm or --subset; M or X that is no integer; M < 1, X < M or X > N;
  *   - without a usable GPU the program fails: there is no CPU fallback.
  * Environment, all of it read in read_environment():
  *   GT4HIP_GPUS=N            as --gpus N (which overrides it);
@@ -54,20 +60,23 @@
 
 #define MAX_FILES 1024
 
-/* Weak: the product links libgt4hip.so, which defines both; the host-only sanitizer build of this file
- * (tests/harness, a CPU stand-in for the device layer) has no -mm and no --subset path and leaves them NULL. */
+/* Weak: the product links libgt4hip.so, which defines them; the host-only sanitizer build of this file
+ * (tests/harness, a CPU stand-in for the device layer) has no -mm, no --subset and no --min_lists path and leaves them NULL. */
 #pragma weak gt4hip_compare_mismatch
 #pragma weak gt4hip_mismatch_stats_get
 #pragma weak gt4hip_list_subset
+#pragma weak gt4hip_select_multi
 
 enum { OPT_PLAIN, OPT_VERSION, OPT_HELP, OPT_OUT, OPT_CUTOFF, OPT_MM, OPT_UNION, OPT_INTRSEC, OPT_DIFF, OPT_DDIFF, OPT_DU,
-       OPT_COUNT_ONLY, OPT_RULE, OPT_SUBSET, OPT_SEED, OPT_PRINT_OP, OPT_NOSCOUTS, OPT_STREAM, OPT_DEBUG, OPT_GPUS };
+       OPT_COUNT_ONLY, OPT_RULE, OPT_SUBSET, OPT_SEED, OPT_PRINT_OP, OPT_NOSCOUTS, OPT_STREAM, OPT_DEBUG, OPT_GPUS,
+       OPT_MIN_LISTS, OPT_MAX_LISTS };
 
 static const GT4CliOption OPTIONS[] = {
   { "-v", OPT_VERSION }, { "--version", OPT_VERSION }, { "-h", OPT_HELP }, { "--help", OPT_HELP }, { "-?", OPT_HELP },
   { "-o", OPT_OUT }, { "--outputname", OPT_OUT }, { "-c", OPT_CUTOFF }, { "--cutoff", OPT_CUTOFF },
   { "--count_cutoff", OPT_CUTOFF }, /* alias used by the benchmark description; not in the reference */
   { "--gpus", OPT_GPUS },           /* not in the reference: key-range shards over several GPUs */
+  { "--min_lists", OPT_MIN_LISTS }, { "--max_lists", OPT_MAX_LISTS }, /* not in the reference: -u restricted to the words of M to X lists */
   { "-mm", OPT_MM }, { "--mismatch", OPT_MM }, { "-u", OPT_UNION }, { "--union", OPT_UNION },
   { "-i", OPT_INTRSEC }, { "--intersection", OPT_INTRSEC }, { "-d", OPT_DIFF }, { "--difference", OPT_DIFF },
   { "-dd", OPT_DDIFF }, { "--double_difference", OPT_DDIFF }, { "-du", OPT_DU }, { "--diff_union", OPT_DU },
@@ -124,6 +133,9 @@ typedef struct {
   uint32_t subset_method;         /* GT4HIP_SUBSET_* */
   unsigned long long subset_size; /* as the reference holds it: strtoll into an unsigned long long */
   long seed;                      /* --seed; -1 (also when given): the start time */
+  int select;                     /* --min_lists and / or --max_lists */
+  int have_min, have_max;
+  long long min_lists, max_lists; /* as given; check_select settles the defaults (1, the number of files) */
   const char *outputname;
   /* environment */
   int n_gpus;         /* GT4HIP_GPUS, or --gpus N */
@@ -265,6 +277,25 @@ static void parse_argv (int argc, const char *argv[], Options *o)
           print_help (1);
         }
         break;
+      case OPT_MIN_LISTS:
+      case OPT_MAX_LISTS: {
+        const int is_min = !strcmp (arg, "--min_lists");
+        if (!argv[i + 1]) {
+          fprintf (stderr, "Error: %s needs a number of lists\n", arg);
+          exit (1);
+        }
+        errno = 0;
+        const long long v = strtoll (argv[i + 1], &end, 10);
+        if (*end != 0 || end == argv[i + 1] || errno) {
+          fprintf (stderr, "Error: Invalid %s: %s! Must be an integer.\n", arg, argv[i + 1]);
+          exit (1);
+        }
+        o->select = 1;
+        *(is_min ? &o->have_min : &o->have_max) = 1;
+        *(is_min ? &o->min_lists : &o->max_lists) = v;
+        i += 1;
+        break;
+      }
       default:
         fprintf (stderr, "Unknown argument: %s!\n", arg);
         print_help (1);
@@ -354,6 +385,36 @@ static void validate (Options *o)
   }
 }
 
+/* --min_lists / --max_lists: what argv alone decides, before a file or a device is opened; settles the defaults */
+static void check_select (Options *o)
+{
+  if (!o->select) return;
+  const char *with = o->find_subset ? "--subset" : o->nmm ? "-mm" : o->find_intrsec ? "-i" : o->subtraction ? "-du" : o->find_ddiff ? "-dd" : o->find_diff ? "-d" : NULL;
+  if (with) {
+    fprintf (stderr, "Error: --min_lists / --max_lists select from the union of the lists: they cannot be combined with %s\n", with);
+    exit (1);
+  }
+  if (!o->find_union) {
+    fprintf (stderr, "Error: --min_lists / --max_lists select from the union of the lists: -u is needed\n");
+    exit (1);
+  }
+  if (o->nfiles < 2) {
+    fprintf (stderr, "Error: At least 2 list/index files are needed\n");
+    exit (1);
+  }
+  if (!o->have_min) o->min_lists = 1;
+  if (!o->have_max) o->max_lists = o->nfiles;
+  if (o->min_lists < 1 || o->max_lists < o->min_lists || o->max_lists > (long long) o->nfiles) {
+    fprintf (stderr, "Error: --min_lists %lld, --max_lists %lld: 1 <= min_lists <= max_lists <= %u (the number of files) is needed\n", o->min_lists,
+             o->max_lists, o->nfiles);
+    exit (1);
+  }
+  if (!gt4hip_select_multi) {
+    fprintf (stderr, "Error: this build has no --min_lists / --max_lists path\n");
+    exit (1);
+  }
+}
+
 /* ---- what the three execution paths share */
 
 static gt4hip_context *create_context (const Options *o)
@@ -426,10 +487,13 @@ static void print_totals (uint64_t n_words, uint64_t total_count)
   fprintf (stdout, "NUnique\t%llu\nNTotal\t%llu\n", (unsigned long long) n_words, (unsigned long long) total_count);
 }
 
-/* "<out>_<k>_union.list", "_intrsec.list", "<out>_<k>_<mismatches>_diff1.list", "_diff2.list" (reference :814-834, -mm :1072-1091) */
+/* "<out>_<k>_union.list", "_intrsec.list", "<out>_<k>_<mismatches>_diff1.list", "_diff2.list" (reference :814-834, -mm :1072-1091);
+ * under --min_lists / --max_lists the union's place is "<out>_<k>_select_<M>_<X>.list": no file with the reference's name
+ * for the union holds anything else */
 static void output_name (const Options *o, unsigned int wlen, int s, char name[2048])
 {
-  if (s < 2) snprintf (name, 2048, "%s_%u_%s.list", o->outputname, wlen, s ? "intrsec" : "union");
+  if (s == 0 && o->select) snprintf (name, 2048, "%s_%u_select_%lld_%lld.list", o->outputname, wlen, o->min_lists, o->max_lists);
+  else if (s < 2) snprintf (name, 2048, "%s_%u_%s.list", o->outputname, wlen, s ? "intrsec" : "union");
   else snprintf (name, 2048, "%s_%u_%u_%s.list", o->outputname, wlen, o->nmm, s == 2 ? "diff1" : "diff2");
 }
 
@@ -508,13 +572,19 @@ static int run_multi (const Options *o, const GT4ListFile *files, unsigned int w
     GT4ShardResult sres;
     gt4hip_multi_result mres;
     memset (&mres, 0, sizeof mres);
+    const int is_select = is_union && o->select; /* the union restricted to the words of min_lists .. max_lists files */
     if (job) {
-      job->mode = is_union ? GT4_SHARD_UNION_MULTI : GT4_SHARD_INTERSECT_MULTI;
+      job->mode = is_select ? GT4_SHARD_SELECT_MULTI : is_union ? GT4_SHARD_UNION_MULTI : GT4_SHARD_INTERSECT_MULTI;
+      job->min_lists = (unsigned int) o->min_lists;
+      job->max_lists = (unsigned int) o->max_lists;
       job->out_mode = 0644;
       job->out_name[0] = o->countonly ? NULL : name;
     }
     const double t_s = now_seconds ();
     if (job) rc = gt4_shard_run (job, &sres);
+    else if (is_select)
+      rc = gt4hip_select_multi (ctx, (const gt4hip_list *const *) lists, o->nfiles, (uint32_t) o->min_lists, (uint32_t) o->max_lists, o->cutoff, o->rule,
+                                o->count_override, o->countonly, &mres);
     else rc = (is_union ? gt4hip_union_multi : gt4hip_intersect_multi) (ctx, (const gt4hip_list *const *) lists, o->nfiles, o->cutoff, o->rule,
                                                                         o->count_override, o->countonly, &mres);
     const double t_e = now_seconds ();
@@ -531,7 +601,9 @@ static int run_multi (const Options *o, const GT4ListFile *files, unsigned int w
       exit (1);
     }
     v = 0;
-    if (o->debug) {
+    if (is_select && o->verbose && !job) fprintf (stderr, "GPU select kernels: %.3f ms, %llu of %llu distinct words kept\n", mres.device_ms,
+                                                  (unsigned long long) mres.n_words, (unsigned long long) mres.records_read);
+    if (o->debug && !is_select) { /* (the selection is no operation of the reference: -D adds nothing to it) */
       unsigned long long total = 0;
       for (unsigned int f = 0; f < o->nfiles; f++) total += files[f].header.n_words;
       fprintf (stderr, "Combined %u maps: input %llu (%.3f Mwords/s) output %llu (%.3f Mwords/s)\n", o->nfiles, is_union ? total : 0ull,
@@ -542,7 +614,7 @@ static int run_multi (const Options *o, const GT4ListFile *files, unsigned int w
       if (gt4_cli_write_list_file (ctx, mres.out, wlen, n_words, total_count, name, 0644, "Error: ")) exit (1);
       gt4hip_list_free (mres.out);
     }
-    if (o->countonly || o->debug) print_totals (n_words, total_count);
+    if (o->countonly || (o->debug && !is_select)) print_totals (n_words, total_count);
   }
   return v;
 }
@@ -682,7 +754,9 @@ static gt4hip_context *resident_context (const Options *o, const GT4ListFile *fi
   /* inputs + worst-case outputs (+ the N-way tree's intermediates) must fit, else stream in chunks */
   uint64_t free_b = 0, total_b = 0;
   gt4hip_device_memory (ctx, &free_b, &total_b);
-  const uint64_t need = 12 * input_records (o, files) * (o->nfiles == 2 ? 1 + (uint64_t) (o->find_union + o->find_intrsec + o->find_diff + o->find_ddiff) : 4);
+  /* (the selection also holds the count table, a key and a count per file for every input record at worst, and 5 bytes per row) */
+  const uint64_t need = o->select ? input_records (o, files) * (12 * 4 + 13 + 4ull * o->nfiles)
+                                  : 12 * input_records (o, files) * (o->nfiles == 2 ? 1 + (uint64_t) (o->find_union + o->find_intrsec + o->find_diff + o->find_ddiff) : 4);
   if (free_b && need > free_b / 100 * 85) {
     if (o->verbose) fprintf (stderr, "Inputs and outputs need %llu bytes, %llu are free: streaming in key-range chunks\n", (unsigned long long) need, (unsigned long long) free_b);
     gt4hip_destroy (ctx);
@@ -705,9 +779,10 @@ static int run_sharded (const Options *o, GT4ListFile *files, unsigned int wlen)
   job.gather_rccl = o->gather_rccl;
   job.debug = o->verbose;
   job.prm = compare_params (o); /* gt4_shard.c reads prm.ops in pair mode only */
-  const int v = o->nfiles > 2 ? run_multi (o, files, wlen, &job, NULL, NULL) : 0;
-  if (o->nfiles == 2) print_lists_debug (o, files);
-  if (o->nfiles == 2 && job.prm.ops) {
+  const int multi = o->nfiles > 2 || o->select; /* (two files with --min_lists / --max_lists take the N-way path) */
+  const int v = multi ? run_multi (o, files, wlen, &job, NULL, NULL) : 0;
+  if (!multi) print_lists_debug (o, files);
+  if (!multi && job.prm.ops) {
     job.mode = GT4_SHARD_PAIR;
     job.out_mode = 0666;
     char names[4][2048];
@@ -735,7 +810,7 @@ static int run_resident (const Options *o, GT4ListFile *files, unsigned int wlen
   static gt4hip_list *lists[MAX_FILES];
   int v = 0;
   upload_inputs (o, ctx, files, wlen, lists);
-  if (o->nfiles > 2) {
+  if (o->nfiles > 2 || o->select) {
     v = run_multi (o, files, wlen, NULL, ctx, lists);
   } else {
     print_lists_debug (o, files);
@@ -763,6 +838,7 @@ int main (int argc, const char *argv[])
   if (argc <= 1) print_help (1);
   read_environment (&o);
   parse_argv (argc, argv, &o); /* --gpus N overrides GT4HIP_GPUS */
+  check_select (&o);
   const unsigned int wlen = open_inputs (&o, files);
   if (o.find_subset) return run_subset (&o, files, wlen); /* before the two-file checks, as in the reference (:292-315) */
   validate (&o);

@@ -8,7 +8,7 @@
  * three threads over its chunks, each with its own library context on the worker's GPU:
  *
  *   loader   file -> HBM           gt4hip_list_upload_fd (pinned staging, several copy threads)
- *   merger   the operation itself  gt4hip_compare / gt4hip_union_multi / gt4hip_intersect_multi
+ *   merger   the operation itself  gt4hip_compare / gt4hip_union_multi / gt4hip_intersect_multi / gt4hip_select_multi
  *   writer   HBM -> file           gt4hip_list_write_fd at byte 48 + 12 * (records of all earlier chunks)
  *
  * Two chunks are in flight per worker, so loading chunk i+1 and writing chunk i-1 overlap the merge of
@@ -32,6 +32,10 @@
 #include <sys/stat.h>
 #include <sys/wait.h>
 #include <unistd.h>
+
+/* Weak: the product's libgt4hip.so defines it; the host-only build of this file against a CPU stand-in for the device layer
+ * (tests/harness) has no select path and leaves it NULL. */
+#pragma weak gt4hip_select_multi
 
 #define MAX_RANKS 64
 #define SLOTS 2
@@ -110,6 +114,9 @@ static int make_plan (const GT4ShardJob *job, uint64_t hbm_limit, Plan *plan)
    * output at most the chunk's inputs), the N-way tree's intermediates, the gather buffer */
   uint64_t per_record = 12ull * (SLOTS + SLOTS * n_streams (job) + (job->mode == GT4_SHARD_PAIR ? 0 : 2) +
                                  (job->gather_rccl ? (uint64_t) n_streams (job) * job->n_ranks : 0));
+  /* the select mode's count table in its ragged form -- a row of a key and n_files counts per input RECORD -- and the
+   * 5 bytes per row the select kernels keep between their passes */
+  if (job->mode == GT4_SHARD_SELECT_MULTI) per_record += 8 + 4ull * job->n_files + 5;
   uint64_t budget = hbm_limit / per_record;
   if (budget < 1) budget = 1;
   const unsigned int G = (unsigned int) job->n_ranks;
@@ -342,11 +349,17 @@ static void merge_chunk (Worker *w, gt4hip_context *ctx, int slot, unsigned int 
   } else {
     gt4hip_multi_result res;
     memset (&res, 0, sizeof res);
+    if (job->mode == GT4_SHARD_SELECT_MULTI && !gt4hip_select_multi) {
+      worker_fail (w, "Error: %s", "this build has no --min_lists / --max_lists path");
+      return;
+    }
+    const gt4hip_list *const *in = (const gt4hip_list *const *) w->in[slot];
     const int rc = job->mode == GT4_SHARD_UNION_MULTI
-                     ? gt4hip_union_multi (ctx, (const gt4hip_list *const *) w->in[slot], job->n_files, job->prm.cutoff, job->prm.rule,
-                                           job->prm.count_override, job->prm.count_only, &res)
-                     : gt4hip_intersect_multi (ctx, (const gt4hip_list *const *) w->in[slot], job->n_files, job->prm.cutoff, job->prm.rule,
-                                               job->prm.count_override, job->prm.count_only, &res);
+                     ? gt4hip_union_multi (ctx, in, job->n_files, job->prm.cutoff, job->prm.rule, job->prm.count_override, job->prm.count_only, &res)
+                   : job->mode == GT4_SHARD_SELECT_MULTI
+                     ? gt4hip_select_multi (ctx, in, job->n_files, job->min_lists, job->max_lists, job->prm.cutoff, job->prm.rule,
+                                            job->prm.count_override, job->prm.count_only, &res)
+                     : gt4hip_intersect_multi (ctx, in, job->n_files, job->prm.cutoff, job->prm.rule, job->prm.count_override, job->prm.count_only, &res);
     if (rc == GT4HIP_ERULE) {
       __atomic_store_n (&w->sh->rule_rejected, 1, __ATOMIC_RELEASE);
       worker_fail (w, "%s", gt4hip_last_error (ctx));
@@ -436,7 +449,8 @@ static int worker_main (const GT4ShardJob *job, Shared *sh, int rank)
          * profiles/round3/r3_cli_e2e_2x2e9_with_reference.log and round4) -- never more than the 70 % above */
         uint64_t in_records = 0;
         for (unsigned int f = 0; f < job->n_files; f++) in_records += job->files[f].header.n_words;
-        const uint64_t need = 12 * in_records * (job->mode == GT4_SHARD_PAIR ? 1 + (uint64_t) n_streams (job) : 4);
+        const uint64_t need = 12 * in_records * (job->mode == GT4_SHARD_PAIR ? 1 + (uint64_t) n_streams (job) : 4) +
+                              (job->mode == GT4_SHARD_SELECT_MULTI ? in_records * (13 + 4ull * job->n_files) : 0);
         uint64_t want = need / 8;
         if (want < (1ull << 30)) want = 1ull << 30;
         if (want < limit) limit = want;

@@ -14,7 +14,7 @@
 #include "gt4_listfile.h"
 #include "gt4hip.h"
 
-enum { GT4_SHARD_PAIR = 0, GT4_SHARD_UNION_MULTI = 1, GT4_SHARD_INTERSECT_MULTI = 2 };
+enum { GT4_SHARD_PAIR = 0, GT4_SHARD_UNION_MULTI = 1, GT4_SHARD_INTERSECT_MULTI = 2, GT4_SHARD_SELECT_MULTI = 3 };
 
 typedef struct {
   /* inputs (mapped by the caller; strictly ascending keys) */
@@ -24,6 +24,7 @@ typedef struct {
   /* operation */
   int mode;                      /* GT4_SHARD_*                                                  */
   gt4hip_compare_params prm;     /* PAIR: ops, rule, cutoff, subtract, count_override, count_only */
+  unsigned int min_lists, max_lists; /* SELECT_MULTI: the union's records whose word lies in min_lists .. max_lists of the files */
   /* outputs: final file names per stream (union, intrsec, diff1, diff2; N-way: slot 0), NULL = not
    * produced; written as <name>.tmp then renamed */
   const char *out_name[4];

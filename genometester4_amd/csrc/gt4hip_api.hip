@@ -176,6 +176,7 @@ extern "C" int gt4hip_set_option (gt4hip_context *ctx, const char *name, int64_t
   else if (!strcmp (name, "dynamic")) ctx->dynamic = (int) value;
   else if (!strcmp (name, "a_rows")) ctx->a_rows = (int) value;
   else if (!strcmp (name, "part_guided")) ctx->part_guided = (int) value;
+  else if (!strcmp (name, "select_vec")) ctx->select_vec = (int) value;
   else if (!strcmp (name, "kway")) ctx->kway_enabled = (int) value;
   else if (!strcmp (name, "kway_max")) ctx->kway_max = value == 8 ? 8 : (value == 33 ? 33 : 32);
   else if (!strcmp (name, "kway_g")) ctx->kway_g = value;
@@ -212,6 +213,7 @@ extern "C" int gt4hip_get_counter (gt4hip_context *ctx, const char *name, uint64
   else if (!strcmp (name, "subset_passes")) *value = ctx->subset_passes;
   else if (!strcmp (name, "subset_tile")) *value = GT4HIP_SUBSET_TILE;
   else if (!strcmp (name, "subset_us")) *value = (uint64_t) (ctx->subset_ms * 1000.0);
+  else if (!strcmp (name, "select_wide")) *value = ctx->select_wide;
   else return gt4hip_fail (ctx, GT4HIP_EINVAL, "unknown counter %s", name);
   return GT4HIP_OK;
 }

@@ -1,6 +1,6 @@
 /* gt4hip_host.h -- host-side internals shared by the C-ABI implementation files: the context and list objects, and
  * what the units of the library host (gt4hip_api.hip, gt4hip_pair.hip, gt4hip_multi.hip, gt4hip_table.hip,
- * gt4hip_nway.hip) and gt4hip_io / _comm / _sort / _mismatch / _query.hip call in one another. */
+ * gt4hip_nway.hip) and gt4hip_io / _comm / _sort / _mismatch / _query / _select.hip call in one another. */
 #ifndef GT4HIP_HOST_H
 #define GT4HIP_HOST_H
 
@@ -82,6 +82,8 @@ struct gt4hip_context {
   uint64_t query_wide;          /* counter "query_wide": the last gt4hip_query_lookup launched k_query<true> */
   uint64_t subset_passes;       /* counter "subset_passes": passes of the last gt4hip_list_subset (gt4hip_subset.hip) */
   double subset_ms;             /* counter "subset_us": its kernels (HIP events) */
+  int select_vec;               /* option "select_vec": gt4hip_table_select reads rows of a multiple of four counts 16 bytes per lane (0) / every row a dword per lane (-1) */
+  uint64_t select_wide;         /* counter "select_wide": the last gt4hip_table_select read 16 bytes per lane */
   char err[512];
   char info[256];
 };
@@ -176,6 +178,12 @@ int gt4hip_table_alloc (gt4hip_context *ctx, gt4hip_count_table *table, uint64_t
 int gt4hip_table_set_ragged (gt4hip_context *ctx, gt4hip_count_table *table, uint64_t tiles);
 void *gt4hip_table_compact_bases (gt4hip_count_table *table);
 void *gt4hip_table_padded_bases (gt4hip_count_table *table);
+/* ... and the number of tiles (0: the table is contiguous) */
+uint64_t gt4hip_table_ragged_tiles (const gt4hip_count_table *table);
+/* gt4hip_select.hip: rows the emit kernel ranks, stages and writes at a time, and rows per segment of a contiguous table
+ * (a ragged table's segments are the rows of its tiles) */
+#define GT4HIP_SELECT_TILE 1024u
+#define GT4HIP_SELECT_SEGMENT 4096u
 void gt4hip_io_destroy (gt4hip_context *ctx);
 /* bytes of text, and codes, per tile of gt4hip_maker.hip's kernels (counters "maker_text_tile", "maker_code_tile") */
 #define GT4HIP_MAKER_TILE 4096u

@@ -89,6 +89,7 @@ int gt4hip_table_set_ragged (gt4hip_context *ctx, gt4hip_count_table *table, uin
 
 void *gt4hip_table_compact_bases (gt4hip_count_table *table) { return table && table->ragged ? ((TableRagged *) table->ragged)->compact : NULL; }
 void *gt4hip_table_padded_bases (gt4hip_count_table *table) { return table && table->ragged ? ((TableRagged *) table->ragged)->padded : NULL; }
+uint64_t gt4hip_table_ragged_tiles (const gt4hip_count_table *table) { return table && table->ragged ? ((const TableRagged *) table->ragged)->tiles : 0; }
 
 static hipError_t table_gather (gt4hip_context *ctx, const gt4hip_count_table *t, uint64_t first, uint64_t count, void *out_keys, void *out_counts)
 {

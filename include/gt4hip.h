@@ -406,6 +406,26 @@ int gt4hip_table_download (gt4hip_context *ctx, const gt4hip_count_table *table,
                            uint64_t count, uint64_t *host_keys, uint32_t *host_counts);
 void gt4hip_table_free (gt4hip_count_table *table);
 
+/* glistcompare -u --min_lists M --max_lists X (not in the reference): the records of the N-way union whose word lies in M to
+ * X of the N lists.  For a word, p is the number of lists that hold it with a count other than 0 (a record with count 0 does
+ * not make its list a holder: the count table cannot tell it from absence); the result is the subsequence of what
+ * gt4hip_union_multi gives for the same lists, rule, cutoff and override with min_lists <= p <= max_lists, record for record.
+ * min_lists 1 and max_lists n_lists: the union itself (where every stored count is at least 1); both n_lists: the key set of
+ * the intersection.  Rules as gt4hip_union_multi (anything else: GT4HIP_ERULE); an empty list counts towards n_lists and holds
+ * nothing; 1 <= min_lists <= max_lists <= n_lists, else GT4HIP_EINVAL with a message.  `result` as gt4hip_union_multi:
+ * result->out may bring a list of enough capacity (the kept records; n_keys of the table always suffice), device_ms is the
+ * select kernels alone, records_read the table's rows, records_written the kept ones.
+ * gt4hip_select_multi builds the table with gt4hip_union_table (one launch for up to 32 non-empty lists, by merges beyond)
+ * and hands it to gt4hip_table_select, which takes a table as it is, ragged or contiguous, and leaves it unchanged: every row
+ * is read once, (8 + 4 n_lists) bytes, plus 5 bytes of workspace written and read per row; 12 bytes are written per kept
+ * record.  A list gt4hip_table_select makes itself says word length 32: a table does not know its own. */
+int gt4hip_select_multi (gt4hip_context *ctx, const gt4hip_list *const lists[], uint32_t n_lists,
+                         uint32_t min_lists, uint32_t max_lists, uint32_t cutoff, int32_t rule,
+                         uint32_t count_override, int32_t count_only, gt4hip_multi_result *result);
+int gt4hip_table_select (gt4hip_context *ctx, const gt4hip_count_table *table, uint32_t min_lists, uint32_t max_lists,
+                         uint32_t cutoff, int32_t rule, uint32_t count_override, int32_t count_only,
+                         gt4hip_multi_result *result);
+
 /* ---------------------------------------------------------------- (e) key-range shards across GPUs */
 
 /* Every set operation above is key-local, so the key space can be cut into contiguous ranges: shard
@@ -697,6 +717,8 @@ int gt4hip_synchronize (gt4hip_context *ctx);
  *                      neighbours' ranks and the probed keys (gt4hip_corank.h: fewer scattered reads on keys that
  *                      are locally uniform, never more than bisection's and four) / plain bisection; the tile
  *                      ranges are the same either way
+ *   "select_vec" = 0 / -1  gt4hip_table_select reads rows of a multiple of four counts (in 16-byte aligned arrays) 16 bytes
+ *                      per lane / every row a dword per lane, as all other rows are read (bench, tests)
  *   "geom0" / "geom1"  force the 512- / 1024-thread geometry (experiments). */
 int gt4hip_set_option (gt4hip_context *ctx, const char *name, int64_t value);
 /* Diagnostic counters of a context.  "single_pass_fallbacks": calls whose single-pass merge gave up a
@@ -716,7 +738,8 @@ int gt4hip_set_option (gt4hip_context *ctx, const char *name, int64_t value);
  * "mm_unskipped_levels": levels of it run without the early exit of decided words (more than 2^32 - 1 variants a word, no subtract);
  * "subset_passes": passes of the last gt4hip_list_subset until a scan changed no tile's carry-in (0: it had nothing to walk);
  * "subset_tile": items per tile of its kernels; "subset_us": its device time (HIP events around the kernels, the one
- * word read back per pass included). */
+ * word read back per pass included); "select_wide": 1 when the context's last gt4hip_table_select (gt4hip_select_multi's too)
+ * read 16 bytes per lane, else 0. */
 int gt4hip_get_counter (gt4hip_context *ctx, const char *name, uint64_t *value);
 /* Diagnostic: the partition launch of a pair merge alone, with tiles of tile_records merged records (any length: tests cut
  * small lists into many tiles).  host_part receives 2 x (tiles + 1) words, tiles = ceil ((|a| + |b|) / tile_records):
