@@ -133,6 +133,7 @@ SYMBOLS = [
     "gt4hip_gmer_db_create", "gt4hip_gmer_db_free", "gt4hip_gmer_db_n_kmers", "gt4hip_gmer_db_last_ms", "gt4hip_gmer_count_words",
     "gt4hip_gmer_count_text", "gt4hip_gmer_counts_download", "gt4hip_gmer_counts_reset",
     "gt4hip_select_multi", "gt4hip_table_select",
+    "gt4hip_table_pairwise", "gt4hip_pairwise_multi",
 ]
 
 _lib = None
@@ -256,6 +257,8 @@ def lib():
             "gt4hip_gmer_counts_reset": (C.c_int, [vp, vp]),
             "gt4hip_select_multi": (C.c_int, [vp, C.POINTER(vp), u32, u32, u32, u32, i32, u32, i32, C.POINTER(MultiResult)]),
             "gt4hip_table_select": (C.c_int, [vp, C.POINTER(CountTable), u32, u32, u32, i32, u32, i32, C.POINTER(MultiResult)]),
+            "gt4hip_table_pairwise": (C.c_int, [vp, C.POINTER(CountTable), vp, vp, C.POINTER(C.c_float)]),
+            "gt4hip_pairwise_multi": (C.c_int, [vp, C.POINTER(vp), u32, vp, vp, C.POINTER(C.c_float)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -933,6 +936,24 @@ class Context:
         def fn(h, arr, n, cutoff_, rule_, ovr, co, res):
             return lib().gt4hip_table_select(h, C.byref(table.t), min_lists, max_lists, cutoff_, rule_, ovr, co, res)
         return self._multi(fn, [], cutoff, rule, count_override, count_only, out)
+
+    def _pairwise(self, n, call):
+        shared = np.empty((n, n), dtype=np.uint64)
+        min_total = np.empty((n, n), dtype=np.uint64)
+        ms = C.c_float(0)
+        self._chk(call(shared.ctypes.data, min_total.ctypes.data, C.byref(ms)))
+        self.last_pairwise_ms = ms.value
+        return shared, min_total
+
+    def pairwise_multi(self, lists):
+        """(shared, min_total), two n x n uint64 matrices: the words lists i and j both hold with a count other than 0, and
+        the sum of the smaller of their two counts (gt4hip_pairwise_multi); self.last_pairwise_ms: the pairwise kernels."""
+        arr = (C.c_void_p * len(lists))(*[l.h for l in lists])
+        return self._pairwise(len(lists), lambda s, m, ms: lib().gt4hip_pairwise_multi(self.h, arr, len(lists), s, m, ms))
+
+    def table_pairwise(self, table: "DeviceTable"):
+        """gt4hip_table_pairwise on a resident table, which stays as it is; returns what pairwise_multi returns."""
+        return self._pairwise(table.n_lists, lambda s, m, ms: lib().gt4hip_table_pairwise(self.h, C.byref(table.t), s, m, ms))
 
     def union_table(self, lists, probe=False, presence=False, compact=False):
         """(keys, counts) of the count table; compact: through gt4hip_table_compact first (a ragged table made

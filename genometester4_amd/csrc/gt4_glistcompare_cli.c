@@ -32,6 +32,17 @@
  *     too.  --count_only prints the two lines of -u --count_only for the selected list; -D adds nothing; --gpus and
  *     GT4HIP_HBM_LIMIT work as for -u.  Before any device is opened, one "Error: ..." line and exit 1 for: the options without
  *     -u or together with -i, -d, -dd, -du, -mm or --subset; M or X that is no integer; M < 1, X < M or X > N;
+ *   - L1 .. LN --pairwise (not in the reference; gt4hip_pairwise_multi) takes two or more lists, writes no list file and
+ *     prints to stdout the line "#I\tJ\tLIST_I\tLIST_J\tSHARED\tMIN_TOTAL\tUNION\tJACCARD" and one tab-separated line for every
+ *     i <= j, in order of i, then j: the two indices from 0, the two file names as given, the words both lists hold with a count
+ *     other than 0, the sum over the words of the smaller of the two counts (for i != j the NUnique and NTotal of
+ *     `Li Lj -i --count_only`), the size of the union of the two, and shared / union with %.6f (0 where the union is empty).
+ *     The lines with i = j give a list's words and the sum of its counts.  A stored record with count 0 is the same as
+ *     absence, as for --min_lists: the count table cannot tell the two apart.  All lists and their count table are resident
+ *     on one GPU: a job that does not fit, GT4HIP_HBM_LIMIT and GT4HIP_GPUS above 1 are refused with a message and exit 1 (the
+ *     matrices are additive over key ranges: chunks and --gpus can follow); -D adds nothing.  Before any device is opened, one
+ *     "Error: ..." line and exit 1 for: fewer than two lists; the option together with -u, -i, -d, -dd, -du, -mm, --subset,
+ *     --min_lists, --max_lists, -r, -c / --count_cutoff, --count_only or --gpus;
  *   - without a usable GPU the program fails: there is no CPU fallback.
  * Environment, all of it read in read_environment():
  *   GT4HIP_GPUS=N            as --gpus N (which overrides it);
@@ -61,15 +72,17 @@
 #define MAX_FILES 1024
 
 /* Weak: the product links libgt4hip.so, which defines them; the host-only sanitizer build of this file
- * (tests/harness, a CPU stand-in for the device layer) has no -mm, no --subset and no --min_lists path and leaves them NULL. */
+ * (tests/harness, a CPU stand-in for the device layer) has no -mm, no --subset, no --min_lists and no --pairwise path and leaves
+ * them NULL. */
 #pragma weak gt4hip_compare_mismatch
 #pragma weak gt4hip_mismatch_stats_get
 #pragma weak gt4hip_list_subset
 #pragma weak gt4hip_select_multi
+#pragma weak gt4hip_pairwise_multi
 
 enum { OPT_PLAIN, OPT_VERSION, OPT_HELP, OPT_OUT, OPT_CUTOFF, OPT_MM, OPT_UNION, OPT_INTRSEC, OPT_DIFF, OPT_DDIFF, OPT_DU,
        OPT_COUNT_ONLY, OPT_RULE, OPT_SUBSET, OPT_SEED, OPT_PRINT_OP, OPT_NOSCOUTS, OPT_STREAM, OPT_DEBUG, OPT_GPUS,
-       OPT_MIN_LISTS, OPT_MAX_LISTS };
+       OPT_MIN_LISTS, OPT_MAX_LISTS, OPT_PAIRWISE };
 
 static const GT4CliOption OPTIONS[] = {
   { "-v", OPT_VERSION }, { "--version", OPT_VERSION }, { "-h", OPT_HELP }, { "--help", OPT_HELP }, { "-?", OPT_HELP },
@@ -77,6 +90,7 @@ static const GT4CliOption OPTIONS[] = {
   { "--count_cutoff", OPT_CUTOFF }, /* alias used by the benchmark description; not in the reference */
   { "--gpus", OPT_GPUS },           /* not in the reference: key-range shards over several GPUs */
   { "--min_lists", OPT_MIN_LISTS }, { "--max_lists", OPT_MAX_LISTS }, /* not in the reference: -u restricted to the words of M to X lists */
+  { "--pairwise", OPT_PAIRWISE },   /* not in the reference: what every list shares with every other one, to stdout */
   { "-mm", OPT_MM }, { "--mismatch", OPT_MM }, { "-u", OPT_UNION }, { "--union", OPT_UNION },
   { "-i", OPT_INTRSEC }, { "--intersection", OPT_INTRSEC }, { "-d", OPT_DIFF }, { "--difference", OPT_DIFF },
   { "-dd", OPT_DDIFF }, { "--double_difference", OPT_DDIFF }, { "-du", OPT_DU }, { "--diff_union", OPT_DU },
@@ -133,6 +147,8 @@ typedef struct {
   uint32_t subset_method;         /* GT4HIP_SUBSET_* */
   unsigned long long subset_size; /* as the reference holds it: strtoll into an unsigned long long */
   long seed;                      /* --seed; -1 (also when given): the start time */
+  int pairwise;                   /* --pairwise */
+  int have_rule, have_cutoff, have_gpus; /* -r, -c and --gpus were given (check_pairwise) */
   int select;                     /* --min_lists and / or --max_lists */
   int have_min, have_max;
   long long min_lists, max_lists; /* as given; check_select settles the defaults (1, the number of files) */
@@ -193,6 +209,7 @@ static void parse_argv (int argc, const char *argv[], Options *o)
         o->outputname = argv[++i];
         break;
       case OPT_CUTOFF:
+        o->have_cutoff = 1;
         if (!argv[i + 1]) {
           fprintf (stderr, "Warning: No frequency cut-off specified! Using the default value: %d.\n", o->cutoff);
           break;
@@ -230,6 +247,7 @@ static void parse_argv (int argc, const char *argv[], Options *o)
           { "default", GT4HIP_RULE_DEFAULT }, { "add", GT4HIP_RULE_ADD }, { "sum", GT4HIP_RULE_ADD }, { "subtract", GT4HIP_RULE_SUBTRACT },
           { "min", GT4HIP_RULE_MIN }, { "max", GT4HIP_RULE_MAX }, { "first", GT4HIP_RULE_FIRST }, { "second", GT4HIP_RULE_SECOND },
         };
+        o->have_rule = 1;
         i += 1;
         if (i >= argc) print_help (1);
         if (argv[i][0] >= '1' && argv[i][0] <= '9') {
@@ -268,7 +286,9 @@ static void parse_argv (int argc, const char *argv[], Options *o)
       case OPT_NOSCOUTS: break;
       case OPT_STREAM: stream = 1; break;
       case OPT_DEBUG: o->debug += 1; break;
+      case OPT_PAIRWISE: o->pairwise = 1; break;
       case OPT_GPUS:
+        o->have_gpus = 1;
         i += 1;
         if (i >= argc) print_help (1);
         o->n_gpus = atoi (argv[i]);
@@ -411,6 +431,27 @@ static void check_select (Options *o)
   }
   if (!gt4hip_select_multi) {
     fprintf (stderr, "Error: this build has no --min_lists / --max_lists path\n");
+    exit (1);
+  }
+}
+
+/* --pairwise: what argv alone decides, before a file or a device is opened */
+static void check_pairwise (const Options *o)
+{
+  if (!o->pairwise) return;
+  const char *with = o->find_subset ? "--subset" : o->nmm ? "-mm" : o->select ? "--min_lists / --max_lists" : o->find_union ? "-u" : o->find_intrsec ? "-i"
+                     : o->subtraction ? "-du" : o->find_ddiff ? "-dd" : o->find_diff ? "-d" : o->have_rule ? "-r" : o->have_cutoff ? "-c" : o->countonly ? "--count_only"
+                     : o->have_gpus ? "--gpus" : NULL;
+  if (with) {
+    fprintf (stderr, "Error: --pairwise compares every list with every other one by itself: it cannot be combined with %s\n", with);
+    exit (1);
+  }
+  if (o->nfiles < 2) {
+    fprintf (stderr, "Error: At least 2 list/index files are needed\n");
+    exit (1);
+  }
+  if (!gt4hip_pairwise_multi) {
+    fprintf (stderr, "Error: this build has no --pairwise path\n");
     exit (1);
   }
 }
@@ -737,6 +778,53 @@ static uint64_t input_records (const Options *o, const GT4ListFile *files)
   return n;
 }
 
+/* --pairwise: every list against every other one from one count table (gt4hip_pairwise_multi); all of it resident */
+static int run_pairwise (const Options *o, GT4ListFile *files, unsigned int wlen)
+{
+  if (o->hbm_limit || o->n_gpus > 1) {
+    fprintf (stderr, "Error: --pairwise needs all lists resident on one GPU: it cannot be combined with %s\n",
+             o->hbm_limit ? "GT4HIP_HBM_LIMIT" : "GT4HIP_GPUS");
+    return 1;
+  }
+  gt4hip_context *ctx = create_context (o);
+  /* the lists; the count table, a key and a count per file for every input record at worst, beside what builds it (the union's
+   * keys, a merge's output); the workgroups' partial matrices (32 x 32 x 2 numbers each) and the two matrices */
+  uint64_t free_b = 0, total_b = 0;
+  gt4hip_device_memory (ctx, &free_b, &total_b);
+  const uint64_t need = input_records (o, files) * (12 * 4 + 8 + 4ull * o->nfiles) + (64ull << 20) + 16ull * o->nfiles * o->nfiles;
+  if (free_b && need > free_b / 100 * 85) {
+    fprintf (stderr, "Error: %s: --pairwise needs about %llu bytes of device memory, %llu are free (the lists and their count table stay resident on one GPU)\n",
+             gt4hip_strerror (GT4HIP_ENOMEM), (unsigned long long) need, (unsigned long long) free_b);
+    gt4hip_destroy (ctx);
+    return 1;
+  }
+  static gt4hip_list *lists[MAX_FILES];
+  upload_inputs (o, ctx, files, wlen, lists);
+  const size_t n = o->nfiles;
+  uint64_t *shared = (uint64_t *) malloc (n * n * sizeof (uint64_t)), *min_total = (uint64_t *) malloc (n * n * sizeof (uint64_t));
+  if (!shared || !min_total) {
+    fprintf (stderr, "Error: out of memory for the matrices of %u lists\n", o->nfiles);
+    exit (1);
+  }
+  float ms = 0;
+  if (gt4hip_pairwise_multi (ctx, (const gt4hip_list *const *) lists, o->nfiles, shared, min_total, &ms)) {
+    fprintf (stderr, "Error: %s\n", gt4hip_last_error (ctx));
+    exit (1);
+  }
+  if (o->verbose) fprintf (stderr, "GPU pairwise kernels: %.3f ms, %u lists\n", ms, o->nfiles);
+  fprintf (stdout, "#I\tJ\tLIST_I\tLIST_J\tSHARED\tMIN_TOTAL\tUNION\tJACCARD\n");
+  for (size_t i = 0; i < n; i++)
+    for (size_t j = i; j < n; j++) {
+      const uint64_t s = shared[i * n + j], u = shared[i * n + i] + shared[j * n + j] - s;
+      fprintf (stdout, "%u\t%u\t%s\t%s\t%llu\t%llu\t%llu\t%.6f\n", (unsigned int) i, (unsigned int) j, o->fnames[i], o->fnames[j], (unsigned long long) s,
+               (unsigned long long) min_total[i * n + j], (unsigned long long) u, u ? (double) s / (double) u : 0.0);
+    }
+  free (shared);
+  free (min_total);
+  release (o, files, lists, ctx);
+  return 0;
+}
+
 /* Big inputs with no plan given: key-range chunks through the loader / merger / writer pipeline, so that reading the next
  * chunk and writing the previous one overlap the merge (GT4HIP_PIPELINE=0 keeps everything in one piece).  The worker that
  * runs the job (in this process) measures the device's free memory and chooses the chunk budget itself. */
@@ -838,8 +926,10 @@ int main (int argc, const char *argv[])
   if (argc <= 1) print_help (1);
   read_environment (&o);
   parse_argv (argc, argv, &o); /* --gpus N overrides GT4HIP_GPUS */
+  check_pairwise (&o);
   check_select (&o);
   const unsigned int wlen = open_inputs (&o, files);
+  if (o.pairwise) return run_pairwise (&o, files, wlen);
   if (o.find_subset) return run_subset (&o, files, wlen); /* before the two-file checks, as in the reference (:292-315) */
   validate (&o);
   if (o.nmm) return run_mismatch (&o, files, wlen);

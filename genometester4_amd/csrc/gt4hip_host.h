@@ -1,6 +1,6 @@
 /* gt4hip_host.h -- host-side internals shared by the C-ABI implementation files: the context and list objects, and
  * what the units of the library host (gt4hip_api.hip, gt4hip_pair.hip, gt4hip_multi.hip, gt4hip_table.hip,
- * gt4hip_nway.hip) and gt4hip_io / _comm / _sort / _mismatch / _query / _select.hip call in one another. */
+ * gt4hip_nway.hip) and gt4hip_io / _comm / _sort / _mismatch / _query / _select / _pairwise.hip call in one another. */
 #ifndef GT4HIP_HOST_H
 #define GT4HIP_HOST_H
 
@@ -184,6 +184,11 @@ uint64_t gt4hip_table_ragged_tiles (const gt4hip_count_table *table);
  * (a ragged table's segments are the rows of its tiles) */
 #define GT4HIP_SELECT_TILE 1024u
 #define GT4HIP_SELECT_SEGMENT 4096u
+/* gt4hip_pairwise.hip: threads per workgroup of the partial kernel, rows a group of lanes has in flight, and list columns per
+ * block (a workgroup reads THREADS / lanes per row x UNROLL rows per step; gt4hip_table_walk.h: the segments both walk) */
+#define GT4HIP_PAIRWISE_THREADS 256u
+#define GT4HIP_PAIRWISE_UNROLL 4u
+#define GT4HIP_PAIRWISE_BLOCK 32u
 void gt4hip_io_destroy (gt4hip_context *ctx);
 /* bytes of text, and codes, per tile of gt4hip_maker.hip's kernels (counters "maker_text_tile", "maker_code_tile") */
 #define GT4HIP_MAKER_TILE 4096u

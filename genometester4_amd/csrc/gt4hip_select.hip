@@ -3,7 +3,7 @@
  * of the N lists.  gt4hip_table_select reads a per-key count table as gt4hip_union_table leaves it, ragged or
  * contiguous, and writes the selected list; gt4hip_select_multi builds the table and hands it over.
  *
- * The table is walked in SEGMENTS of consecutive rows: the rows of one tile of the N-way tile kernel in a ragged table (they
+ * The table is walked in SEGMENTS of consecutive rows (gt4hip_table_walk.h: SelTable, segment_of, shared with gt4hip_pairwise.hip): the rows of one tile of the N-way tile kernel in a ragged table (they
  * lie together where the tile's records start, so no row is searched for), GT4HIP_SELECT_SEGMENT rows in a contiguous one.
  * Three kernels live here:
  *   k_select_decide<G, MAXR, VEC>  one group of G lanes per row, consecutive lanes on consecutive dwords of the row (VEC 1:
@@ -22,6 +22,7 @@
 #define GT4_RESOLVE_LOOKBACK 0 /* (no chained scan of tile totals here) */
 #include "gt4hip_device.h"
 #include "gt4hip_host.h"
+#include "gt4hip_table_walk.h"
 
 #include <string.h>
 
@@ -35,39 +36,10 @@ constexpr int SEL_RPT = (int) (SEL_TILE / SEL_THREADS); /* rows per thread and t
 constexpr int SEL_UNR = 4;                              /* rows a lane group has in flight */
 static_assert (SEL_TILE % SEL_THREADS == 0, "whole rounds of one row per thread");
 
-struct SelTable {
-  const u64 *keys;
-  const u32 *counts;
-  u32 n_lists;
-  u64 n_keys;
-  const u64 *compact, *padded; /* ragged: rows before every tile, where the tile's rows lie (segments + 1 entries); else NULL */
-  u64 segments;
-};
-
 struct SelRule {
   u32 min_lists, max_lists, cutoff;
   u32 number, count_override; /* rule NUMBER: every kept record carries the override */
 };
-
-/* segment s: its first row in the compact numbering, where that row lies in the arrays, and its rows.  All wave-uniform.
- * Whatever the index says, no row beyond n_keys is touched in the per-row arrays or the output. */
-__device__ __forceinline__ void segment_of (const SelTable &t, u64 s, u64 &row_base, u64 &src_base, u32 &rows)
-{
-  u64 end;
-  if (t.compact) {
-    row_base = t.compact[s];
-    end = t.compact[s + 1];
-    src_base = t.padded[s];
-  } else {
-    row_base = s * (u64) GT4HIP_SELECT_SEGMENT;
-    end = row_base + GT4HIP_SELECT_SEGMENT;
-    src_base = row_base;
-  }
-  if (end > t.n_keys) end = t.n_keys;
-  if (row_base > end) row_base = end;
-  const u64 n = end - row_base;
-  rows = n < 0x40000000ull ? (u32) n : 0x40000000u;
-}
 
 /* sum / maximum over the G lanes of a group, in every lane of it: DPP inside a row of 16 lanes (quad permutes, then the two
  * mirrors: after the quads hold their sums, lane i and lane 7 - i lie in different quads, lane i and lane 15 - i in different
@@ -336,14 +308,7 @@ int table_select (gt4hip_context *ctx, const gt4hip_count_table *table, uint32_t
   if (!table->device_keys || !table->device_counts) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_table_select: a table of %llu keys without its arrays", (unsigned long long) table->n_keys);
   HIPCHK (ctx, hipSetDevice (ctx->device));
   hipStream_t st = ctx->stream;
-  SelTable t;
-  t.keys = (const u64 *) table->device_keys;
-  t.counts = (const u32 *) table->device_counts;
-  t.n_lists = table->n_lists;
-  t.n_keys = table->n_keys;
-  t.compact = (const u64 *) gt4hip_table_compact_bases (const_cast<gt4hip_count_table *> (table));
-  t.padded = (const u64 *) gt4hip_table_padded_bases (const_cast<gt4hip_count_table *> (table));
-  t.segments = t.compact ? gt4hip_table_ragged_tiles (table) : (t.n_keys + GT4HIP_SELECT_SEGMENT - 1) / GT4HIP_SELECT_SEGMENT;
+  const SelTable t = table_walk (table);
   if (!t.segments) return empty_selection (ctx, word_length, count_only, res);
   const SelRule q = { min_lists, max_lists, cutoff, rule == GT4HIP_RULE_NUMBER ? 1u : 0u, ovr };
 

@@ -426,6 +426,26 @@ int gt4hip_table_select (gt4hip_context *ctx, const gt4hip_count_table *table, u
                          uint32_t cutoff, int32_t rule, uint32_t count_override, int32_t count_only,
                          gt4hip_multi_result *result);
 
+/* glistcompare L1 .. LN --pairwise (not in the reference): what every list shares with every other one.  With c_i (w) the
+ * count of word w in list i, 0 where it is absent (a record with count 0 is the same as absence: the count table cannot tell
+ * the two apart), two matrices of n_lists x n_lists numbers, row-major:
+ *   host_shared[i * n_lists + j]     the words w with c_i (w) > 0 and c_j (w) > 0
+ *   host_min_total[i * n_lists + j]  the sum over all words of min (c_i (w), c_j (w))
+ * Both are symmetric and filled in full, both triangles and the diagonal, which holds a list's words with a count other than
+ * 0 and the sum of its counts.  For i != j the two numbers are the NUnique and NTotal lines of `glistcompare Li Lj -i
+ * --count_only` under the default rule; the union's size is shared[i][i] + shared[j][j] - shared[i][j], the two differences'
+ * shared[i][i] - shared[i][j] and shared[j][j] - shared[i][j].  An empty list counts towards n_lists, its row and column are
+ * 0; n_lists = 1 is valid; lists of different word lengths: GT4HIP_EWORDLEN.  device_ms (may be NULL) is the time of the
+ * pairwise kernels alone.
+ * gt4hip_pairwise_multi builds the table with gt4hip_union_table, hands it to gt4hip_table_pairwise and frees it.
+ * gt4hip_table_pairwise takes a table as it is, ragged or contiguous, and leaves it unchanged: up to 32 lists, every row's
+ * counts are read exactly once, 4 n_lists bytes (the keys are not read); beyond that the list columns are taken in blocks of
+ * 32 and the table is read ceil (n_lists / 32) times.  A row that p lists hold costs p (p - 1) / 2 updates. */
+int gt4hip_table_pairwise (gt4hip_context *ctx, const gt4hip_count_table *table,
+                           uint64_t *host_shared, uint64_t *host_min_total, float *device_ms);
+int gt4hip_pairwise_multi (gt4hip_context *ctx, const gt4hip_list *const lists[], uint32_t n_lists,
+                           uint64_t *host_shared, uint64_t *host_min_total, float *device_ms);
+
 /* ---------------------------------------------------------------- (e) key-range shards across GPUs */
 
 /* Every set operation above is key-local, so the key space can be cut into contiguous ranges: shard
