@@ -203,7 +203,7 @@ extern "C" int gt4hip_gmer_db_create (gt4hip_context *ctx, const uint64_t *host_
   db->n = n;
   db->k = k;
   db->last_ms = 0;
-  Blocks blk;
+  TempBlocks blk;
   u64 *d_words = NULL, *d_values = NULL;
   u32 *bad = (u32 *) ctx->scratch;           /* word 0 */
   unsigned long long *dup = ctx->scratch + 1; /* word 1 */
@@ -216,7 +216,7 @@ extern "C" int gt4hip_gmer_db_create (gt4hip_context *ctx, const uint64_t *host_
     rc = gt4hip_io_upload (ctx, host_words, d_words, n * 8);
     if (!rc && hipMemsetAsync (ctx->scratch, 0, 8, ctx->stream) != hipSuccess) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_gmer_db_create: hipMemsetAsync failed");
     if (!rc) {
-      hipLaunchKernelGGL (k_gmer_prepare, dim3 (grid_for (ctx, n, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, d_words, d_values, n, k, bad);
+      hipLaunchKernelGGL (k_gmer_prepare, dim3 (gt4hip_grid (ctx, n, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, d_words, d_values, n, k, bad);
       if (hipGetLastError () != hipSuccess) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_gmer_db_create: canonicalising the words failed");
     }
     if (!rc) rc = gt4hip_read_scratch (ctx, 1);
@@ -224,7 +224,7 @@ extern "C" int gt4hip_gmer_db_create (gt4hip_context *ctx, const uint64_t *host_
     if (!rc) rc = gt4hip_sort_pairs (ctx, d_words, d_values, n, k);
     if (!rc && hipMemsetAsync (dup, 0xff, 8, ctx->stream) != hipSuccess) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_gmer_db_create: hipMemsetAsync failed");
     if (!rc) {
-      hipLaunchKernelGGL (k_gmer_pack, dim3 (grid_for (ctx, n, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, (const u64 *) d_words, (const u64 *) d_values, n,
+      hipLaunchKernelGGL (k_gmer_pack, dim3 (gt4hip_grid (ctx, n, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, (const u64 *) d_words, (const u64 *) d_values, n,
                           (u32 *) db->list->dev, dup);
       if (hipGetLastError () != hipSuccess) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_gmer_db_create: packing the words failed");
     }
@@ -260,7 +260,7 @@ int count_device_words (gt4hip_context *ctx, gt4hip_gmer_db *db, const u64 *d_wo
   db->last_ms = 0;
   if (!n) return GT4HIP_OK;
   HIPCHK (ctx, hipMemsetAsync (ctx->scratch, 0, 16, ctx->stream));
-  const int grid = grid_for (ctx, n, MM_THREADS);
+  const int grid = gt4hip_grid (ctx, n, MM_THREADS);
   HIPCHK (ctx, hipEventRecord (ctx->ev[0], ctx->stream));
   if (flags & GT4HIP_GMER_PLAIN_ATOMICS) hipLaunchKernelGGL (k_gmer_count<false>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, d_words, n, db->ix, db->counters, ctx->scratch);
   else hipLaunchKernelGGL (k_gmer_count<true>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, d_words, n, db->ix, db->counters, ctx->scratch);
@@ -285,7 +285,7 @@ extern "C" int gt4hip_gmer_count_words (gt4hip_context *ctx, gt4hip_gmer_db *db,
   if (kmer_gc) *kmer_gc = 0;
   HIPCHK (ctx, hipSetDevice (ctx->device));
   if (!n) return GT4HIP_OK;
-  Blocks blk;
+  TempBlocks blk;
   const u64 *d_words = (const u64 *) words;
   if (!(flags & GT4HIP_GMER_ON_DEVICE)) {
     u64 *d = NULL;

@@ -1,6 +1,7 @@
-/* gt4hip_host.h -- host-side internals shared by the C-ABI implementation files: the context and list objects, and
- * what the units of the library host (gt4hip_api.hip, gt4hip_pair.hip, gt4hip_multi.hip, gt4hip_table.hip,
- * gt4hip_nway.hip) and gt4hip_io / _comm / _sort / _mismatch / _query / _select / _pairwise.hip call in one another. */
+/* gt4hip_host.h -- host-side internals shared by the C-ABI implementation files: the context and list objects, the
+ * owners of a call's temporaries (TempLists, TempBlocks, TempTable), the grid size of the striding kernels, and what the
+ * units of the library host (gt4hip_api.hip, gt4hip_pair.hip, gt4hip_multi.hip, gt4hip_table.hip, gt4hip_nway.hip) and
+ * gt4hip_io / _comm / _sort / _maker / _mismatch / _query / _gmer / _subset / _select / _pairwise.hip call in one another. */
 #ifndef GT4HIP_HOST_H
 #define GT4HIP_HOST_H
 
@@ -142,6 +143,42 @@ struct GT4HIP_LOCAL TempLists {
   }
 };
 
+/* gt4hip_table.hip: device memory from the context's block pool; the owner is what gt4hip_block_free takes */
+int gt4hip_block_alloc (gt4hip_context *ctx, size_t bytes, void **dev, void **owner);
+void gt4hip_block_free (void *owner);
+
+/* Device blocks that exist for one call, freed like TempLists' lists: in the order acquired.  A block that ends up in an
+ * object that outlives the call is not taken here: gt4hip_block_alloc gives its owner to the object directly. */
+struct GT4HIP_LOCAL TempBlocks {
+  std::vector<void *> owners;
+  TempBlocks () {}
+  TempBlocks (const TempBlocks &) = delete;
+  void operator= (const TempBlocks &) = delete;
+  ~TempBlocks () { clear (); }
+  /* *p = a block of `bytes` bytes (of 16 where that is 0) */
+  int get (gt4hip_context *ctx, size_t bytes, void **p)
+  {
+    void *owner = NULL;
+    const int rc = gt4hip_block_alloc (ctx, bytes ? bytes : 16, p, &owner);
+    if (!rc) owners.push_back (owner);
+    return rc;
+  }
+  void clear ()
+  {
+    for (void *o : owners) gt4hip_block_free (o);
+    owners.clear ();
+  }
+};
+
+/* workgroups of a kernel that strides over `blocks` blocks of work: one each, at most eight per compute unit, at least one */
+inline int gt4hip_grid (const gt4hip_context *ctx, uint64_t blocks)
+{
+  const uint64_t cap = (uint64_t) (ctx->n_cus > 0 ? ctx->n_cus : 256) * 8;
+  return (int) (blocks < 1 ? 1 : blocks < cap ? blocks : cap);
+}
+/* ... over `items` items, `per_block` to a block */
+inline int gt4hip_grid (const gt4hip_context *ctx, uint64_t items, uint64_t per_block) { return gt4hip_grid (ctx, (items + per_block - 1) / per_block); }
+
 /* *out = the caller's list `given` if it holds `need` records (an error if not; `s`: the output stream named in the
  * text, < 0 where the call has one output), else a new list of that capacity, which `made` then owns */
 GT4HIP_LOCAL int gt4hip_output_list (gt4hip_context *ctx, int s, gt4hip_list *given, uint64_t need, uint32_t word_length, TempLists &made, gt4hip_list **out);
@@ -170,8 +207,6 @@ int gt4hip_nway_union (gt4hip_context *ctx, const gt4hip_list *const lists[], ui
                        uint32_t filter, bool count_only, gt4hip_list *out, uint64_t *n_words, uint64_t *total_count, double *device_ms, int *used);
 int gt4hip_nway_table (gt4hip_context *ctx, const gt4hip_list *const lists[], uint32_t k, const uint32_t cols[], gt4hip_count_table *table, int probe,
                        int presence, int *used);
-int gt4hip_block_alloc (gt4hip_context *ctx, size_t bytes, void **dev, void **owner);
-void gt4hip_block_free (void *owner);
 int gt4hip_table_alloc (gt4hip_context *ctx, gt4hip_count_table *table, uint64_t n, uint32_t n_lists);
 /* ragged tables (gt4hip_count_table.ragged): the index of `tiles` tiles -- rows before every tile (compact) and where
  * the tile's rows lie in the arrays (padded), tiles + 1 device u64 each */
@@ -180,6 +215,16 @@ void *gt4hip_table_compact_bases (gt4hip_count_table *table);
 void *gt4hip_table_padded_bases (gt4hip_count_table *table);
 /* ... and the number of tiles (0: the table is contiguous) */
 uint64_t gt4hip_table_ragged_tiles (const gt4hip_count_table *table);
+/* A count table that exists for one call (gt4hip_select_multi, gt4hip_pairwise_multi) */
+struct GT4HIP_LOCAL TempTable {
+  gt4hip_count_table table;
+  TempTable () : table () {}
+  TempTable (const TempTable &) = delete;
+  void operator= (const TempTable &) = delete;
+  ~TempTable () { gt4hip_table_free (&table); }
+};
+/* gt4hip_union_table of lists that must all be there (GT4HIP_EINVAL) and of one word length (GT4HIP_EWORDLEN) */
+GT4HIP_LOCAL int gt4hip_union_table_checked (gt4hip_context *ctx, const gt4hip_list *const lists[], uint32_t n_lists, gt4hip_count_table *table);
 /* gt4hip_select.hip: rows the emit kernel ranks, stages and writes at a time, and rows per segment of a contiguous table
  * (a ragged table's segments are the rows of its tiles) */
 #define GT4HIP_SELECT_TILE 1024u

@@ -162,29 +162,6 @@ namespace {
 
 using namespace gt4;
 
-struct Blocks {
-  std::vector<void *> owners;
-  ~Blocks ()
-  {
-    for (void *o : owners) gt4hip_block_free (o);
-  }
-  int get (gt4hip_context *ctx, size_t bytes, void **p)
-  {
-    void *owner = NULL;
-    const int rc = gt4hip_block_alloc (ctx, bytes ? bytes : 16, p, &owner);
-    if (rc) return rc;
-    owners.push_back (owner);
-    return GT4HIP_OK;
-  }
-};
-
-int grid_for (gt4hip_context *ctx, u64 items, u64 per_block)
-{
-  const u64 want = (items + per_block - 1) / per_block;
-  const u64 cap = (u64) (ctx->n_cus > 0 ? ctx->n_cus : 256) * 8;
-  return (int) (want < 1 ? 1 : want < cap ? want : cap);
-}
-
 /* the geometry of a list's index: 2^b buckets, b = log2 (n) - 3 (windows of ~8 records), at most MM_MAX_INDEX_BITS */
 void size_index (const gt4hip_list *l, Index *ix)
 {
@@ -205,13 +182,13 @@ void size_index (const gt4hip_list *l, Index *ix)
 int fill_index (gt4hip_context *ctx, Index *ix, void *off)
 {
   ix->off = (const u64 *) off;
-  hipLaunchKernelGGL (k_index_build, dim3 (grid_for (ctx, ix->n + 1, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, ix->rec, ix->n, ix->shift, ix->nb,
+  hipLaunchKernelGGL (k_index_build, dim3 (gt4hip_grid (ctx, ix->n + 1, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, ix->rec, ix->n, ix->shift, ix->nb,
                       (u64 *) off);
   HIPCHK (ctx, hipGetLastError ());
   return GT4HIP_OK;
 }
 
-[[maybe_unused]] int build_index (gt4hip_context *ctx, Blocks &blk, const gt4hip_list *l, Index *ix)
+[[maybe_unused]] int build_index (gt4hip_context *ctx, TempBlocks &blk, const gt4hip_list *l, Index *ix)
 {
   size_index (l, ix);
   void *off = NULL;

@@ -516,7 +516,7 @@ struct MakerCall {
   uint64_t **d_words, *n_words, *error_offset;
   LocCall *loc;            /* NULL: gt4hip_text_to_words */
   gt4hip_maker_carry c;    /* what the piece starts from */
-  Blocks blk;
+  TempBlocks blk;
   const unsigned char *d_text;
   const TypeKernels *kern;
   u64 file_off, tiles;     /* where the piece starts in its file (locations); its tiles of text */
@@ -598,7 +598,7 @@ int maker_classify_count (MakerCall &m)
   m.h = MakerInfo { m.n_bytes, ~0ull, 0, 0, m.c.in_name, m.c.line_phase, m.c.at_line_start }; /* (the rest 0) */
   HIPCHK (ctx, hipMemcpyAsync (m.info, &m.h, sizeof m.h, hipMemcpyHostToDevice, st));
   HIPCHK (ctx, hipMemcpyAsync (m.buf, m.c.codes, MK_HALO, hipMemcpyHostToDevice, st));
-  m.grid = grid_for (ctx, tiles, 1);
+  m.grid = gt4hip_grid (ctx, tiles, 1);
   hipEventRecord (ctx->ev[0], st);
   hipLaunchKernelGGL (k_mk_summary, dim3 (m.grid), dim3 (MK_THREADS), 0, st, m.d_text, (u64) m.n_bytes, tiles, m.tile_cnt, m.tile_info, m.info);
   hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, st, m.tile_cnt, tiles, m.tile_off, &m.info->n_words);
@@ -766,7 +766,7 @@ extern "C" int gt4hip_pack_locations (gt4hip_context *ctx, uint64_t *d_raw, uint
     return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_pack_locations: file %llu with %u + %u + 1 bits behind it does not fit 64 bits", (unsigned long long) file, subseq_bits, pos_bits);
   HIPCHK (ctx, hipSetDevice (ctx->device));
   if (!n) return GT4HIP_OK;
-  hipLaunchKernelGGL (k_pack_locations, dim3 (grid_for (ctx, n, 256)), dim3 (256), 0, ctx->stream, (u64 *) d_raw, (u64) n, (u64) file, subseq_bits, pos_bits);
+  hipLaunchKernelGGL (k_pack_locations, dim3 (gt4hip_grid (ctx, n, 256)), dim3 (256), 0, ctx->stream, (u64 *) d_raw, (u64) n, (u64) file, subseq_bits, pos_bits);
   HIPCHK (ctx, hipGetLastError ());
   HIPCHK (ctx, hipStreamSynchronize (ctx->stream));
   return GT4HIP_OK;

@@ -216,7 +216,7 @@ int compact (gt4hip_context *ctx, const u32 *keep, u64 n, u32 *tile_cnt, u64 *ti
   if (!n) return GT4HIP_OK;
   const u64 tiles = (n + MM_TILE - 1) / MM_TILE;
   HIPCHK (ctx, hipMemsetAsync (ctx->scratch, 0, 16, ctx->stream));
-  const int grid = grid_for (ctx, tiles, 1);
+  const int grid = gt4hip_grid (ctx, tiles, 1);
   hipLaunchKernelGGL (k_tile_count, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, keep, n, tiles, tile_cnt);
   hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, ctx->stream, tile_cnt, tiles, tile_off, ctx->scratch);
   hipLaunchKernelGGL ((k_scatter<SRC_REC, DST_REC>), dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, keep, n, tiles, tile_off, src_keys, cnt, dst_keys,
@@ -244,7 +244,7 @@ struct Side {
   bool done;            /* final records written */
 };
 
-int side_alloc (gt4hip_context *ctx, Blocks &blk, Side &s)
+int side_alloc (gt4hip_context *ctx, TempBlocks &blk, Side &s)
 {
   const u64 n = s.x->n_words, tiles = n / MM_TILE + 2;
   int rc = GT4HIP_OK;
@@ -293,7 +293,7 @@ int run_level (gt4hip_context *ctx, Side &s, u32 k, u32 c, u32 cutoff, u32 subtr
     L.early = subtract || L.n_var <= 0xffffffffull;
     L.cnt = s.scnt;
     L.drop = s.drop;
-    const int grid = grid_for (ctx, L.total, MM_THREADS);
+    const int grid = gt4hip_grid (ctx, L.total, MM_THREADS);
     const u64 stride = (u64) grid * MM_THREADS;
     L.stride_w = stride / L.n_var;
     L.stride_r = stride % L.n_var;
@@ -309,7 +309,7 @@ int run_level (gt4hip_context *ctx, Side &s, u32 k, u32 c, u32 cutoff, u32 subtr
     *probes += ctx->scratch_host[2];
   }
   /* above k there are no variants: s = 0 */
-  hipLaunchKernelGGL (k_decide, dim3 (grid_for (ctx, s.n, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, s.scnt, s.drop, s.n, subtract, cutoff, s.keep);
+  hipLaunchKernelGGL (k_decide, dim3 (gt4hip_grid (ctx, s.n, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, s.scnt, s.drop, s.n, subtract, cutoff, s.keep);
   HIPCHK (ctx, hipGetLastError ());
   return GT4HIP_OK;
 }
@@ -349,7 +349,7 @@ extern "C" int gt4hip_compare_mismatch (gt4hip_context *ctx, const gt4hip_list *
   gt4hip_mismatch_stats st;
   memset (&st, 0, sizeof st);
   ctx->mm_wide_levels = ctx->mm_unskipped_levels = 0;
-  Blocks blk;
+  TempBlocks blk;
   hipEvent_t e0 = NULL, e1 = NULL, e2 = NULL;
   gt4hip_list *made[4] = { NULL, NULL, NULL, NULL };
   u64 out_n[4] = { 0, 0, 0, 0 }, out_sum[4] = { 0, 0, 0, 0 };
@@ -398,7 +398,7 @@ extern "C" int gt4hip_compare_mismatch (gt4hip_context *ctx, const gt4hip_list *
     Side &s = sides[i];
     const u64 nx = s.x->n_words;
     if (nx) {
-      hipLaunchKernelGGL (k_prepass, dim3 (grid_for (ctx, nx, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, (const u32 *) s.x->dev, nx, s.other,
+      hipLaunchKernelGGL (k_prepass, dim3 (gt4hip_grid (ctx, nx, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, (const u32 *) s.x->dev, nx, s.other,
                           (u32) (s.slot == 3), cutoff, subtract, s.keep, s.val);
       if (hipGetLastError () != hipSuccess) return fail (gt4hip_fail (ctx, GT4HIP_EHIP, "k_prepass launch failed"));
     }

@@ -345,8 +345,9 @@ extern "C" int gt4hip_shard_cuts (gt4hip_context *ctx, const gt4hip_list *const 
     for (uint32_t g = 1; g < n_shards; g++) first_keys[g] = gt4hip_shard_first_key (wl, n_shards, g);
     return GT4HIP_OK;
   }
-  void *dev = NULL, *owner = NULL;
-  int rc = gt4hip_block_alloc (ctx, (size_t) m_total * 8, &dev, &owner);
+  TempBlocks blk;
+  void *dev = NULL;
+  int rc = blk.get (ctx, (size_t) m_total * 8, &dev);
   if (rc) return rc;
   std::vector<unsigned long long> host ((size_t) m_total);
   uint64_t at = 0;
@@ -358,7 +359,7 @@ extern "C" int gt4hip_shard_cuts (gt4hip_context *ctx, const gt4hip_list *const 
     at += m;
   }
   rc = gt4hip_read_back (ctx, host.data (), dev, (size_t) m_total * 8, "gt4hip_shard_cuts");
-  gt4hip_block_free (owner);
+  blk.clear (); /* (before the host sort) */
   if (rc) return rc;
   std::sort (host.begin (), host.end ());
   for (uint32_t g = 1; g < n_shards; g++) {

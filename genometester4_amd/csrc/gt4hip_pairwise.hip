@@ -134,22 +134,6 @@ using namespace gt4;
 
 namespace {
 
-/* device blocks of one call, from the context's pool */
-struct PwBlocks {
-  void *owner[4];
-  int n = 0;
-  ~PwBlocks ()
-  {
-    for (int i = 0; i < n; i++) gt4hip_block_free (owner[i]);
-  }
-  int get (gt4hip_context *ctx, size_t bytes, void **p)
-  {
-    const int rc = gt4hip_block_alloc (ctx, bytes ? bytes : 16, p, &owner[n]);
-    if (!rc) n++;
-    return rc;
-  }
-};
-
 template <int G>
 void launch_partial (bool same, dim3 grid, hipStream_t st, const SelTable &t, const PwPass &b, u64 *ws)
 {
@@ -177,10 +161,9 @@ int table_pairwise (gt4hip_context *ctx, const gt4hip_count_table *table, uint64
 
   u32 g = 2; /* lanes per row: the next power of two that holds a block's columns */
   while (g < (n < PW_BLOCK ? n : PW_BLOCK)) g *= 2;
-  const u64 cap = (u64) (ctx->n_cus > 0 ? ctx->n_cus : 256) * 8;
-  const dim3 grid ((unsigned) (t.segments < cap ? t.segments : cap));
+  const dim3 grid ((unsigned) gt4hip_grid (ctx, t.segments));
   const size_t cells = (size_t) n * n;
-  PwBlocks blk;
+  TempBlocks blk;
   u64 *ws = NULL, *out = NULL;
   int rc = blk.get (ctx, (size_t) grid.x * 2 * g * g * 8, (void **) &ws);
   if (!rc) rc = blk.get (ctx, 2 * cells * 8, (void **) &out);
@@ -226,14 +209,8 @@ extern "C" int gt4hip_pairwise_multi (gt4hip_context *ctx, const gt4hip_list *co
                                        uint64_t *host_min_total, float *device_ms)
 {
   if (!ctx || !lists || !n_lists || !host_shared || !host_min_total) return GT4HIP_EINVAL;
-  for (uint32_t j = 0; j < n_lists; j++) {
-    if (!lists[j]) return GT4HIP_EINVAL;
-    if (lists[j]->word_length != lists[0]->word_length) return gt4hip_fail (ctx, GT4HIP_EWORDLEN, "word lengths differ");
-  }
-  gt4hip_count_table table;
-  int rc = gt4hip_union_table (ctx, lists, n_lists, &table);
+  TempTable t;
+  const int rc = gt4hip_union_table_checked (ctx, lists, n_lists, &t.table);
   if (rc) return rc;
-  rc = table_pairwise (ctx, &table, host_shared, host_min_total, device_ms);
-  gt4hip_table_free (&table);
-  return rc;
+  return table_pairwise (ctx, &t.table, host_shared, host_min_total, device_ms);
 }

@@ -665,7 +665,7 @@ extern "C" int gt4hip_query_lookup (gt4hip_context *ctx, gt4hip_query_index *qi,
   ctx->query_wide = 0;
   if (!n) return GT4HIP_OK;
   HIPCHK (ctx, hipSetDevice (ctx->device));
-  Blocks blk;
+  TempBlocks blk;
   u64 *d_words = NULL;
   u32 *d_values = NULL;
   unsigned char *d_found = NULL;
@@ -678,11 +678,11 @@ extern "C" int gt4hip_query_lookup (gt4hip_context *ctx, gt4hip_query_index *qi,
   HIPCHK (ctx, hipMemcpyAsync (d_words, words, n * 8, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK (ctx, hipEventRecord (tm.e0, ctx->stream));
   if (!prm->n_mm) {
-    hipLaunchKernelGGL (k_query_exact, dim3 (grid_for (ctx, n, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, d_words, n, Q.ix, Q.k, Q.canonize, d_values,
+    hipLaunchKernelGGL (k_query_exact, dim3 (gt4hip_grid (ctx, n, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, d_words, n, Q.ix, Q.k, Q.canonize, d_values,
                         d_found);
   } else {
     HIPCHK (ctx, hipMemsetAsync (d_values, 0, n * 4, ctx->stream));
-    const int grid = grid_for (ctx, Q.total, MM_THREADS);
+    const int grid = gt4hip_grid (ctx, Q.total, MM_THREADS);
     const u64 stride = (u64) grid * MM_THREADS;
     Q.stride_w = stride / Q.n_var;
     Q.stride_r = stride % Q.n_var;
@@ -690,7 +690,7 @@ extern "C" int gt4hip_query_lookup (gt4hip_context *ctx, gt4hip_query_index *qi,
     if (!ctx->query_wide) hipLaunchKernelGGL (k_query<false>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, Q, d_values);
     else hipLaunchKernelGGL (k_query<true>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, Q, d_values);
     HIPCHK (ctx, hipGetLastError ());
-    hipLaunchKernelGGL (k_query_found, dim3 (grid_for (ctx, n, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, d_values, n, d_found);
+    hipLaunchKernelGGL (k_query_found, dim3 (gt4hip_grid (ctx, n, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, d_values, n, d_found);
   }
   HIPCHK (ctx, hipGetLastError ());
   HIPCHK (ctx, hipEventRecord (tm.e1, ctx->stream));
@@ -712,7 +712,7 @@ extern "C" int gt4hip_query_lookup_all (gt4hip_context *ctx, gt4hip_query_index 
   qi->last_ms = 0;
   if (!n) return GT4HIP_OK;
   HIPCHK (ctx, hipSetDevice (ctx->device));
-  Blocks blk;
+  TempBlocks blk;
   u64 *d_words = NULL;
   if ((rc = blk.get (ctx, n * 8, (void **) &d_words))) return rc;
   Query Q;
@@ -729,7 +729,7 @@ extern "C" int gt4hip_query_lookup_all (gt4hip_context *ctx, gt4hip_query_index 
   HIPCHK (ctx, hipEventCreate (&tm.e1));
   HIPCHK (ctx, hipMemcpyAsync (d_words, words, n * 8, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK (ctx, hipEventRecord (tm.e0, ctx->stream));
-  const int grid = grid_for (ctx, tiles, 1);
+  const int grid = gt4hip_grid (ctx, tiles, 1);
   hipLaunchKernelGGL (k_query_all<false>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, Q, tiles, tile_cnt, (const u64 *) NULL, (gt4hip_query_hit *) NULL);
   hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, ctx->stream, tile_cnt, tiles, tile_off, ctx->scratch);
   HIPCHK (ctx, hipGetLastError ());
@@ -765,7 +765,7 @@ extern "C" int gt4hip_list_count_stats (gt4hip_context *ctx, const gt4hip_list *
   host[1] = 0;
   if (list->n_words) {
     HIPCHK (ctx, hipMemcpyAsync (out, host, 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL (k_count_stats, dim3 (grid_for (ctx, list->n_words, MM_THREADS * 4)), dim3 (MM_THREADS), 0, ctx->stream, (const u32 *) list->dev,
+    hipLaunchKernelGGL (k_count_stats, dim3 (gt4hip_grid (ctx, list->n_words, MM_THREADS * 4)), dim3 (MM_THREADS), 0, ctx->stream, (const u32 *) list->dev,
                         list->n_words, out);
     HIPCHK (ctx, hipGetLastError ());
     HIPCHK (ctx, hipMemcpyAsync (host, out, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -783,7 +783,7 @@ extern "C" int gt4hip_list_count_split (gt4hip_context *ctx, const gt4hip_list *
   *below = *above = 0;
   if (!list->n_words) return GT4HIP_OK;
   HIPCHK (ctx, hipMemsetAsync (ctx->scratch, 0, 16, ctx->stream));
-  hipLaunchKernelGGL (k_count_split, dim3 (grid_for (ctx, list->n_words, MM_THREADS * 4)), dim3 (MM_THREADS), 0, ctx->stream, (const u32 *) list->dev,
+  hipLaunchKernelGGL (k_count_split, dim3 (gt4hip_grid (ctx, list->n_words, MM_THREADS * 4)), dim3 (MM_THREADS), 0, ctx->stream, (const u32 *) list->dev,
                       list->n_words, med, ctx->scratch);
   HIPCHK (ctx, hipGetLastError ());
   HIPCHK (ctx, hipMemcpyAsync (ctx->scratch_host, ctx->scratch, 16, hipMemcpyDeviceToHost, ctx->stream));
@@ -800,12 +800,12 @@ extern "C" int gt4hip_list_count_histogram (gt4hip_context *ctx, const gt4hip_li
   memset (hist, 0, (size_t) max * 8);
   if (!list->n_words) return GT4HIP_OK;
   HIPCHK (ctx, hipSetDevice (ctx->device));
-  Blocks blk;
+  TempBlocks blk;
   unsigned long long *d = NULL;
   int rc = blk.get (ctx, (size_t) max * 8, (void **) &d);
   if (rc) return rc;
   HIPCHK (ctx, hipMemsetAsync (d, 0, (size_t) max * 8, ctx->stream));
-  const int grid = grid_for (ctx, list->n_words, MM_THREADS * 4);
+  const int grid = gt4hip_grid (ctx, list->n_words, MM_THREADS * 4);
   if (max <= HIST_LDS_BINS)
     hipLaunchKernelGGL (k_count_histogram<true>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, (const u32 *) list->dev, list->n_words, max, d);
   else hipLaunchKernelGGL (k_count_histogram<false>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, (const u32 *) list->dev, list->n_words, max, d);
@@ -825,7 +825,7 @@ extern "C" int gt4hip_list_gc (gt4hip_context *ctx, const gt4hip_list *list, uin
   HIPCHK (ctx, hipSetDevice (ctx->device));
   const u64 mask = k == 32 ? ~0ull : (1ull << (2 * k)) - 1;
   HIPCHK (ctx, hipMemsetAsync (ctx->scratch, 0, 8, ctx->stream));
-  hipLaunchKernelGGL (k_gc, dim3 (grid_for (ctx, list->n_words, MM_THREADS * 4)), dim3 (MM_THREADS), 0, ctx->stream, (const u32 *) list->dev, list->n_words,
+  hipLaunchKernelGGL (k_gc, dim3 (gt4hip_grid (ctx, list->n_words, MM_THREADS * 4)), dim3 (MM_THREADS), 0, ctx->stream, (const u32 *) list->dev, list->n_words,
                       mask, ctx->scratch);
   HIPCHK (ctx, hipGetLastError ());
   HIPCHK (ctx, hipMemcpyAsync (ctx->scratch_host, ctx->scratch, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -883,7 +883,7 @@ extern "C" int gt4hip_location_index_create (gt4hip_context *ctx, const void *ho
   li->bits.pos_mask = mask (n_pos_bits);
   /* the k-mer section goes through a device buffer of PIECE entries (and the one behind them: the end of the last count) */
   const u64 PIECE = 1ull << 22;
-  Blocks blk;
+  TempBlocks blk;
   u64 *tmp = NULL;
   u32 *bad = (u32 *) ctx->scratch;
   int rc = gt4hip_list_new (ctx, n_words, word_length, &li->list);
@@ -895,7 +895,7 @@ extern "C" int gt4hip_location_index_create (gt4hip_context *ctx, const void *ho
     const u64 n = n_words - i0 < PIECE ? n_words - i0 : PIECE, with_next = i0 + n < n_words ? n + 1 : n;
     rc = gt4hip_io_upload (ctx, (const char *) host_kmers + i0 * 16, tmp, with_next * 16);
     if (rc) break;
-    hipLaunchKernelGGL (k_index_split, dim3 (grid_for (ctx, n, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, (const u64 *) tmp, i0, n, n_words, num_locations,
+    hipLaunchKernelGGL (k_index_split, dim3 (gt4hip_grid (ctx, n, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, (const u64 *) tmp, i0, n, n_words, num_locations,
                         (u32 *) li->list->dev, li->first, bad);
     if (hipGetLastError () != hipSuccess || hipStreamSynchronize (ctx->stream) != hipSuccess) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_location_index_create: decoding the k-mer section failed");
   }
@@ -924,7 +924,7 @@ extern "C" int gt4hip_query_lookup_locations (gt4hip_context *ctx, gt4hip_query_
   qi->last_ms = qi->gather_ms = 0;
   if (!n) return GT4HIP_OK;
   HIPCHK (ctx, hipSetDevice (ctx->device));
-  Blocks blk;
+  TempBlocks blk;
   u64 *d_words = NULL;
   if ((rc = blk.get (ctx, n * 8, (void **) &d_words))) return rc;
   Query Q;
@@ -944,7 +944,7 @@ extern "C" int gt4hip_query_lookup_locations (gt4hip_context *ctx, gt4hip_query_
   HIPCHK (ctx, hipEventCreate (&tg.e0));
   HIPCHK (ctx, hipMemcpyAsync (d_words, words, n * 8, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK (ctx, hipEventRecord (tm.e0, ctx->stream));
-  const int grid = grid_for (ctx, tiles, 1);
+  const int grid = gt4hip_grid (ctx, tiles, 1);
   hipLaunchKernelGGL (k_query_loc<false>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, Q, (const u64 *) li->first, tiles, tile_cnt, tile_loc, (const u64 *) NULL,
                       (const u64 *) NULL, (gt4hip_query_hit *) NULL, (u64 *) NULL, (u64 *) NULL);
   hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, ctx->stream, tile_cnt, tiles, tile_off, ctx->scratch);
@@ -969,7 +969,7 @@ extern "C" int gt4hip_query_lookup_locations (gt4hip_context *ctx, gt4hip_query_
     HIPCHK (ctx, hipEventRecord (tg.e0, ctx->stream));
     if (total_locs) {
       const u64 g_tiles = (total_locs + GATHER_TILE - 1) / GATHER_TILE;
-      hipLaunchKernelGGL (k_gather_locations, dim3 (grid_for (ctx, g_tiles, 1)), dim3 (MM_THREADS), 0, ctx->stream, (const u64 *) seg_off, (const u64 *) seg_src, total_hits,
+      hipLaunchKernelGGL (k_gather_locations, dim3 (gt4hip_grid (ctx, g_tiles, 1)), dim3 (MM_THREADS), 0, ctx->stream, (const u64 *) seg_off, (const u64 *) seg_src, total_hits,
                           total_locs, (const u64 *) li->locs, li->bits, d_locs);
       HIPCHK (ctx, hipGetLastError ());
     }

@@ -232,22 +232,6 @@ using namespace gt4;
 
 namespace {
 
-/* device blocks of one call, from the context's pool */
-struct SelBlocks {
-  void *owner[8];
-  int n = 0;
-  ~SelBlocks ()
-  {
-    for (int i = 0; i < n; i++) gt4hip_block_free (owner[i]);
-  }
-  int get (gt4hip_context *ctx, size_t bytes, void **p)
-  {
-    const int rc = gt4hip_block_alloc (ctx, bytes ? bytes : 16, p, &owner[n]);
-    if (!rc) n++;
-    return rc;
-  }
-};
-
 template <int G, int VEC>
 void launch_decide (bool maxr, dim3 grid, hipStream_t st, const SelTable &t, const SelRule &q, u32 *row_cnt, unsigned char *row_keep, u32 *seg_cnt, u64 *seg_sum)
 {
@@ -312,7 +296,7 @@ int table_select (gt4hip_context *ctx, const gt4hip_count_table *table, uint32_t
   if (!t.segments) return empty_selection (ctx, word_length, count_only, res);
   const SelRule q = { min_lists, max_lists, cutoff, rule == GT4HIP_RULE_NUMBER ? 1u : 0u, ovr };
 
-  SelBlocks blk;
+  TempBlocks blk;
   u32 *row_cnt = NULL, *seg_cnt = NULL;
   unsigned char *row_keep = NULL;
   u64 *seg_sum = NULL, *seg_off = NULL;
@@ -326,8 +310,7 @@ int table_select (gt4hip_context *ctx, const gt4hip_count_table *table, uint32_t
   if (!rc) rc = blk.get (ctx, (size_t) t.segments * 8, (void **) &seg_off);
   if (rc) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_table_select: the workspace of %llu rows in %llu segments", (unsigned long long) t.n_keys, (unsigned long long) t.segments);
 
-  const u64 cap = (u64) (ctx->n_cus > 0 ? ctx->n_cus : 256) * 8;
-  const dim3 grid ((unsigned) (t.segments < cap ? t.segments : cap));
+  const dim3 grid ((unsigned) gt4hip_grid (ctx, t.segments));
   const bool maxr = rule == GT4HIP_RULE_MAX;
   HIPCHK (ctx, hipEventRecord (ctx->ev[0], st));
   /* rows of a multiple of four counts in arrays that are 16-byte aligned (the library's own are): 16 bytes per lane */
@@ -391,13 +374,7 @@ extern "C" int gt4hip_select_multi (gt4hip_context *ctx, const gt4hip_list *cons
   int rc = union_rule (ctx, "select_multi", &rule);
   if (!rc) rc = check_bounds (ctx, "gt4hip_select_multi", min_lists, max_lists, n_lists);
   if (rc) return rc;
-  for (uint32_t j = 0; j < n_lists; j++) {
-    if (!lists[j]) return GT4HIP_EINVAL;
-    if (lists[j]->word_length != lists[0]->word_length) return gt4hip_fail (ctx, GT4HIP_EWORDLEN, "word lengths differ");
-  }
-  gt4hip_count_table table;
-  if ((rc = gt4hip_union_table (ctx, lists, n_lists, &table))) return rc;
-  rc = table_select (ctx, &table, lists[0]->word_length, min_lists, max_lists, cutoff, rule, ovr, count_only != 0, res);
-  gt4hip_table_free (&table);
-  return rc;
+  TempTable t;
+  if ((rc = gt4hip_union_table_checked (ctx, lists, n_lists, &t.table))) return rc;
+  return table_select (ctx, &t.table, lists[0]->word_length, min_lists, max_lists, cutoff, rule, ovr, count_only != 0, res);
 }

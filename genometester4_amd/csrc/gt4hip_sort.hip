@@ -645,16 +645,15 @@ static int radix_sort_device (gt4hip_context *ctx, const char *who, u64 *words, 
   const uint64_t tiles = (n + RADIX_TILE - 1) / RADIX_TILE;
   if (tiles >= (1ull << 32)) return gt4hip_fail (ctx, GT4HIP_EINVAL, "%s: %llu words", who, (unsigned long long) n);
   const size_t ws_bytes = sizeof (RadixHead) + (size_t) tiles * RADIX_MAX_DIGITS * 8;
+  TempBlocks blk;
   RadixHead *ws = NULL;
-  void *ws_owner = NULL;
-  if (gt4hip_block_alloc (ctx, ws_bytes, (void **) &ws, &ws_owner)) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "%s: workspace of %llu bytes", who, (unsigned long long) ws_bytes);
+  if (blk.get (ctx, ws_bytes, (void **) &ws)) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "%s: workspace of %llu bytes", who, (unsigned long long) ws_bytes);
   u64 *ghist = &ws->bases[0][0], *state = (u64 *) (ws + 1);
   u32 *err = &ws->ctl.err;
   const u32 spin_limit = ctx->spin_limit ? ctx->spin_limit : SPIN_LIMIT;
   hipStream_t st = ctx->stream;
   hipError_t e = hipMemsetAsync (ws, 0, ws_bytes, st);
-  u64 hb = (n + (u64) HIST_NT * HIST_ITEMS - 1) / ((u64) HIST_NT * HIST_ITEMS);
-  if (hb > (u64) ctx->n_cus * 8) hb = (u64) ctx->n_cus * 8;
+  const int hb = gt4hip_grid (ctx, n, (u64) HIST_NT * HIST_ITEMS);
   hipLaunchKernelGGL (k_radix_hist, dim3 ((unsigned) hb), dim3 (HIST_NT), 0, st, words, n, plan, ghist);
   hipLaunchKernelGGL (k_radix_bases, dim3 (passes), dim3 (RADIX_MAX_DIGITS), 0, st, ghist);
   u64 *src = words, *dst = tmp, *vsrc = vals, *vdst = vtmp;
@@ -675,7 +674,6 @@ static int radix_sort_device (gt4hip_context *ctx, const char *who, u64 *words, 
   if (e == hipSuccess) e = hipGetLastError ();
   if (e == hipSuccess) e = hipMemcpyAsync (ctx->scratch_host, err, 4, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize (st);
-  gt4hip_block_free (ws_owner);
   if (e != hipSuccess) return gt4hip_fail (ctx, GT4HIP_EHIP, "%s: %s", who, hipGetErrorString (e));
   if ((u32) ctx->scratch_host[0]) return gt4hip_fail (ctx, GT4HIP_EHIP, "%s: a chained-scan wait gave up (device shared with a stuck workgroup?)", who);
   *result = src;
@@ -692,9 +690,9 @@ static int sort_in_place (gt4hip_context *ctx, const char *who, void *device_wor
   HIPCHK (ctx, hipSetDevice (ctx->device));
   if (n < 2) return GT4HIP_OK;
   const size_t stream_bytes = (size_t) n * 8, scratch_bytes = device_values ? 2 * stream_bytes : stream_bytes;
+  TempBlocks blk;
   u64 *tmp = NULL;
-  void *tmp_owner = NULL;
-  if (gt4hip_block_alloc (ctx, scratch_bytes, (void **) &tmp, &tmp_owner)) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "%s: %llu bytes of scratch", who, (unsigned long long) scratch_bytes);
+  if (blk.get (ctx, scratch_bytes, (void **) &tmp)) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "%s: %llu bytes of scratch", who, (unsigned long long) scratch_bytes);
   u64 *res = NULL, *vres = NULL;
   if (device_values) hipEventRecord (ctx->ev[0], ctx->stream);
   int rc = radix_sort_device (ctx, who, (u64 *) device_words, tmp, n, word_length, &res, (u64 *) device_values, device_values ? tmp + n : NULL, &vres);
@@ -708,7 +706,6 @@ static int sort_in_place (gt4hip_context *ctx, const char *who, void *device_wor
   if (!rc && e != hipSuccess) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "%s: %s", who, hipGetErrorString (e));
   float ms = 0;
   if (device_values && hipEventElapsedTime (&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->sort_ms = ms;
-  gt4hip_block_free (tmp_owner);
   return rc;
 }
 
@@ -729,39 +726,32 @@ extern "C" int gt4hip_sort_pairs (gt4hip_context *ctx, void *device_words, void 
 static int fold_sorted_words (gt4hip_context *ctx, const u64 *words, uint64_t n_words, uint32_t word_length, gt4hip_list **out)
 {
   hipStream_t st = ctx->stream;
-  int rc = GT4HIP_OK;
-  gt4hip_list *l = NULL;
-  hipError_t e;
   const uint64_t tiles = (n_words + FOLD_TILE - 1) / FOLD_TILE;
   if (tiles >= (1ull << 32)) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_words_to_list: %llu words", (unsigned long long) n_words);
   /* workspace: control words, tile states, runs before every tile (+ the total) */
+  TempLists made; /* (a list that is not handed out goes after the workspace) */
+  TempBlocks blk;
   ScanControl *ws = NULL;
-  void *ws_owner = NULL;
   const size_t cleared = sizeof (ScanControl) + (size_t) tiles * 8, bytes = cleared + (size_t) (tiles + 1) * 8;
-  if (gt4hip_block_alloc (ctx, bytes, (void **) &ws, &ws_owner)) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_words_to_list: workspace");
+  if (blk.get (ctx, bytes, (void **) &ws)) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_words_to_list: workspace");
   u64 *state = (u64 *) (ws + 1), *tile_excl = state + tiles;
-  e = hipMemsetAsync (ws, 0, cleared, st);
+  hipError_t e = hipMemsetAsync (ws, 0, cleared, st);
   hipLaunchKernelGGL (k_fold_count, dim3 ((unsigned) tiles), dim3 (FOLD_NT), 0, st, words, n_words, state, tile_excl, tiles, &ws->ticket[0], ctx->scratch, &ws->err,
                       ctx->spin_limit ? ctx->spin_limit : SPIN_LIMIT);
   if (e == hipSuccess) e = hipMemcpyAsync (ctx->scratch_host, ctx->scratch, 8, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipMemcpyAsync (ctx->scratch_host + 1, &ws->err, 4, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize (st);
-  if (e != hipSuccess) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_words_to_list: %s", hipGetErrorString (e));
-  else if ((u32) ctx->scratch_host[1]) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_words_to_list: a chained-scan wait gave up (device shared with a stuck workgroup?)");
-  if (!rc) {
-    const uint64_t n_heads = ctx->scratch_host[0];
-    rc = gt4hip_list_new (ctx, n_heads, word_length, &l);
-    if (!rc) {
-      hipLaunchKernelGGL (k_fold_records, dim3 ((unsigned) tiles), dim3 (FOLD_NT), 0, st, words, n_words, tile_excl, tiles, (u32 *) l->dev);
-      e = hipStreamSynchronize (st);
-      if (e != hipSuccess) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_words_to_list: %s", hipGetErrorString (e));
-    }
-  }
-  gt4hip_block_free (ws_owner);
-  if (rc) {
-    if (l) gt4hip_list_free (l);
-    return rc;
-  }
+  if (e != hipSuccess) return gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_words_to_list: %s", hipGetErrorString (e));
+  if ((u32) ctx->scratch_host[1]) return gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_words_to_list: a chained-scan wait gave up (device shared with a stuck workgroup?)");
+  const uint64_t n_heads = ctx->scratch_host[0];
+  gt4hip_list *l = NULL;
+  const int rc = gt4hip_list_new (ctx, n_heads, word_length, &l);
+  if (rc) return rc;
+  made.adopt (l);
+  hipLaunchKernelGGL (k_fold_records, dim3 ((unsigned) tiles), dim3 (FOLD_NT), 0, st, words, n_words, tile_excl, tiles, (u32 *) l->dev);
+  e = hipStreamSynchronize (st);
+  if (e != hipSuccess) return gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_words_to_list: %s", hipGetErrorString (e));
+  made.release ();
   *out = l;
   return GT4HIP_OK;
 }
@@ -774,9 +764,9 @@ extern "C" int gt4hip_device_words_to_list (gt4hip_context *ctx, void *device_wo
   HIPCHK (ctx, hipSetDevice (ctx->device));
   *out = NULL;
   if (!n_words) return gt4hip_list_new (ctx, 0, word_length, out);
+  TempBlocks blk;
   u64 *tmp = NULL;
-  void *tmp_owner = NULL;
-  if (gt4hip_block_alloc (ctx, (size_t) n_words * 8, (void **) &tmp, &tmp_owner))
+  if (blk.get (ctx, (size_t) n_words * 8, (void **) &tmp))
     return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_device_words_to_list: %llu bytes of scratch", (unsigned long long) n_words * 8);
   hipEventRecord (ctx->ev[0], ctx->stream);
   u64 *res = NULL;
@@ -789,7 +779,6 @@ extern "C" int gt4hip_device_words_to_list (gt4hip_context *ctx, void *device_wo
   float ms = 0;
   if (hipEventElapsedTime (&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->sort_ms = ms;
   if (hipEventElapsedTime (&ms, ctx->ev[1], ctx->ev[2]) == hipSuccess) ctx->fold_ms = ms;
-  gt4hip_block_free (tmp_owner);
   return rc;
 }
 
@@ -837,9 +826,9 @@ extern "C" int gt4hip_pairs_to_index (gt4hip_context *ctx, void *device_words, v
   tmp.adopt (runs);
   const uint64_t n_runs = runs->n_words, tiles = (n_runs + INDEX_TILE - 1) / INDEX_TILE;
   if (tiles >= (1ull << 31)) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_pairs_to_index: %llu distinct words", (unsigned long long) n_runs);
+  TempBlocks blk; /* (after `tmp`: the sums go before the runs) */
   u64 *sums = NULL;
-  void *sums_owner = NULL;
-  if (gt4hip_block_alloc (ctx, (size_t) tiles * 16, (void **) &sums, &sums_owner)) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_pairs_to_index: workspace");
+  if (blk.get (ctx, (size_t) tiles * 16, (void **) &sums)) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_pairs_to_index: workspace");
   hipStream_t st = ctx->stream;
   const u32 *rec = (const u32 *) runs->dev;
   if (n_pairs > 0xffffffffull) {
@@ -847,38 +836,29 @@ extern "C" int gt4hip_pairs_to_index (gt4hip_context *ctx, void *device_words, v
      * and its record would then hold the count mod 2^32.  All records kept, the counts must add up to the pairs. */
     hipLaunchKernelGGL (k_index_sums, dim3 ((unsigned) tiles), dim3 (INDEX_NT), 0, st, rec, n_runs, 1u, 0xffffffffu, sums, sums + tiles);
     hipLaunchKernelGGL (k_index_scan, dim3 (1), dim3 (1024), 0, st, sums, sums + tiles, tiles, ctx->scratch);
-    rc = gt4hip_read_scratch (ctx, 2);
-    if (!rc && ctx->scratch_host[1] != n_pairs)
-      rc = gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_pairs_to_index: a word with 2^32 or more locations (the counts of %llu pairs add up to %llu)", (unsigned long long) n_pairs,
-                        (unsigned long long) ctx->scratch_host[1]);
-    if (rc) {
-      gt4hip_block_free (sums_owner);
-      return rc;
-    }
+    if ((rc = gt4hip_read_scratch (ctx, 2))) return rc;
+    if (ctx->scratch_host[1] != n_pairs)
+      return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_pairs_to_index: a word with 2^32 or more locations (the counts of %llu pairs add up to %llu)", (unsigned long long) n_pairs,
+                          (unsigned long long) ctx->scratch_host[1]);
   }
   hipLaunchKernelGGL (k_index_sums, dim3 ((unsigned) tiles), dim3 (INDEX_NT), 0, st, rec, n_runs, min_locations, max_locations, sums, sums + tiles);
   hipLaunchKernelGGL (k_index_scan, dim3 (1), dim3 (1024), 0, st, sums, sums + tiles, tiles, ctx->scratch);
-  rc = gt4hip_read_scratch (ctx, 2);
+  if ((rc = gt4hip_read_scratch (ctx, 2))) return rc;
   const uint64_t n_kmers = ctx->scratch_host[0], n_locations = ctx->scratch_host[1];
-  if (!rc && n_kmers) {
+  if (n_kmers) {
+    /* (the context's from the start: not a block of this call) */
     void *kmers = NULL, *owner = NULL;
-    if (gt4hip_block_alloc (ctx, (size_t) n_kmers * 16, &kmers, &owner)) {
-      rc = gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_pairs_to_index: %llu k-mers", (unsigned long long) n_kmers);
-    } else {
-      ctx->index_kmers = (gt4hip_list *) owner;
-      hipLaunchKernelGGL (k_index_write, dim3 ((unsigned) tiles), dim3 (INDEX_NT), 0, st, rec, n_runs, min_locations, max_locations, sums, sums + tiles, (u64 *) kmers);
-      hipError_t e = hipGetLastError ();
-      if (e == hipSuccess) e = hipStreamSynchronize (st);
-      if (e != hipSuccess) {
-        gt4hip_index_free (ctx);
-        rc = gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_pairs_to_index: %s", hipGetErrorString (e));
-      } else {
-        out->d_kmers = (const uint64_t *) kmers;
-      }
+    if (gt4hip_block_alloc (ctx, (size_t) n_kmers * 16, &kmers, &owner)) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_pairs_to_index: %llu k-mers", (unsigned long long) n_kmers);
+    ctx->index_kmers = (gt4hip_list *) owner;
+    hipLaunchKernelGGL (k_index_write, dim3 ((unsigned) tiles), dim3 (INDEX_NT), 0, st, rec, n_runs, min_locations, max_locations, sums, sums + tiles, (u64 *) kmers);
+    hipError_t e = hipGetLastError ();
+    if (e == hipSuccess) e = hipStreamSynchronize (st);
+    if (e != hipSuccess) {
+      gt4hip_index_free (ctx);
+      return gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_pairs_to_index: %s", hipGetErrorString (e));
     }
+    out->d_kmers = (const uint64_t *) kmers;
   }
-  gt4hip_block_free (sums_owner);
-  if (rc) return rc;
   out->n_kmers = n_kmers;
   out->n_locations = n_locations;
   return GT4HIP_OK;

@@ -319,23 +319,6 @@ __global__ void k_subset_compact (const u32 *rec, const u32 *selected, const u64
 
 /* ------------------------------------------------------------------ host */
 
-/* device blocks that live as long as the call */
-struct Blocks {
-  std::vector<void *> owners;
-  ~Blocks ()
-  {
-    for (void *o : owners) gt4hip_block_free (o);
-  }
-  int get (gt4hip_context *ctx, u64 bytes, void **p)
-  {
-    void *owner = NULL;
-    const int rc = gt4hip_block_alloc (ctx, (size_t) (bytes ? bytes : 16), p, &owner);
-    if (rc) return rc;
-    owners.push_back (owner);
-    return GT4HIP_OK;
-  }
-};
-
 struct Timer {
   hipEvent_t e0 = NULL, e1 = NULL;
   ~Timer ()
@@ -345,12 +328,6 @@ struct Timer {
   }
 };
 
-int grid_of (gt4hip_context *ctx, u64 blocks)
-{
-  const u64 cap = (u64) (ctx->n_cus > 0 ? ctx->n_cus : 256) * 8;
-  return (int) (blocks < 1 ? 1 : blocks < cap ? blocks : cap);
-}
-
 /* one level of a scan: the sums of its tiles and their prefix sums, sized once for every pass */
 struct ScanLevel {
   u64 n, n_tiles;
@@ -358,7 +335,7 @@ struct ScanLevel {
 };
 
 /* the levels of a scan over n >= 1 elements: level 0 is the input itself, level l + 1 the tile sums of level l */
-int scan_plan (gt4hip_context *ctx, u64 n, Blocks &blk, std::vector<ScanLevel> &levels)
+int scan_plan (gt4hip_context *ctx, u64 n, TempBlocks &blk, std::vector<ScanLevel> &levels)
 {
   levels.clear ();
   for (;;) {
@@ -376,7 +353,7 @@ int scan_plan (gt4hip_context *ctx, u64 n, Blocks &blk, std::vector<ScanLevel> &
 template <int MODE>
 void scan_level (gt4hip_context *ctx, const ScanLevel &L, const void *in, u64 *out, bool reduce)
 {
-  const int grid = grid_of (ctx, L.n_tiles);
+  const int grid = gt4hip_grid (ctx, L.n_tiles);
   if (reduce) hipLaunchKernelGGL (k_subset_scan_reduce<MODE>, dim3 (grid), dim3 (SCAN_THREADS), 0, ctx->stream, in, L.n, L.n_tiles, L.sums);
   else hipLaunchKernelGGL (k_subset_scan_apply<MODE>, dim3 (grid), dim3 (SCAN_THREADS), 0, ctx->stream, in, L.n, L.n_tiles, (const u64 *) L.offsets, out);
 }
@@ -401,7 +378,7 @@ const char *const METHOD_NAMES[3] = { "rand", "rand_unique", "rand_weighted_uniq
 template <int EMIT>
 void launch_pass (gt4hip_context *ctx, bool weighted, const SubsetJob &J, const u64 *carry, u64 *tile_sum, const SubsetEmit &E, u64 *error)
 {
-  const int grid = grid_of (ctx, J.tiles);
+  const int grid = gt4hip_grid (ctx, J.tiles);
   if (weighted && EMIT != EMIT_OCCURRENCES) hipLaunchKernelGGL ((k_subset_pass<true, EMIT == EMIT_OCCURRENCES ? EMIT_NONE : EMIT>), dim3 (grid), dim3 (SUBSET_THREADS), 0, ctx->stream, J, carry, tile_sum, E, error);
   else hipLaunchKernelGGL ((k_subset_pass<false, EMIT>), dim3 (grid), dim3 (SUBSET_THREADS), 0, ctx->stream, J, carry, tile_sum, E, error);
 }
@@ -437,7 +414,7 @@ extern "C" int gt4hip_list_subset (gt4hip_context *ctx, const gt4hip_list *list,
   if (!list->n_words || !prm->size) return empty_result (ctx, list->word_length, out, n_words, total_count);
   HIPCHK (ctx, hipSetDevice (ctx->device));
 
-  Blocks blk;
+  TempBlocks blk;
   Timer tm;
   std::vector<ScanLevel> levels;
   int rc;
@@ -476,7 +453,7 @@ extern "C" int gt4hip_list_subset (gt4hip_context *ctx, const gt4hip_list *list,
   memset (&E, 0, sizeof E);
   u64 *const word = ctx->scratch; /* [0] carry-ins changed, [1] items selected, [2] a tile passed its bound, [3] total_count */
 
-  hipLaunchKernelGGL (k_subset_guess, dim3 (grid_of (ctx, (J.tiles + 255) / 256)), dim3 (256), 0, ctx->stream, J, weighted ? 1 : 0, carry[0]);
+  hipLaunchKernelGGL (k_subset_guess, dim3 (gt4hip_grid (ctx, (J.tiles + 255) / 256)), dim3 (256), 0, ctx->stream, J, weighted ? 1 : 0, carry[0]);
   HIPCHK (ctx, hipGetLastError ());
   u64 selected = 0;
   for (u64 pass = 1;; pass++) {
@@ -488,7 +465,7 @@ extern "C" int gt4hip_list_subset (gt4hip_context *ctx, const gt4hip_list *list,
     launch_pass<EMIT_NONE> (ctx, weighted, J, carry[0], tile_sum, E, word + 2);
     HIPCHK (ctx, hipGetLastError ());
     HIPCHK (ctx, scan_run<SCAN_U64> (ctx, levels, tile_sum, carry[1]));
-    hipLaunchKernelGGL (k_subset_changed, dim3 (grid_of (ctx, (J.tiles + SCAN_THREADS - 1) / SCAN_THREADS)), dim3 (SCAN_THREADS), 0, ctx->stream,
+    hipLaunchKernelGGL (k_subset_changed, dim3 (gt4hip_grid (ctx, (J.tiles + SCAN_THREADS - 1) / SCAN_THREADS)), dim3 (SCAN_THREADS), 0, ctx->stream,
                         (const u64 *) carry[0], (const u64 *) carry[1], J.tiles, word);
     HIPCHK (ctx, hipGetLastError ());
     if ((rc = gt4hip_read_scratch (ctx, 3))) return rc;
@@ -535,7 +512,7 @@ extern "C" int gt4hip_list_subset (gt4hip_context *ctx, const gt4hip_list *list,
     const u64 kept = ctx->scratch_host[0];
     if ((rc = gt4hip_list_new (ctx, kept, list->word_length, &res))) return rc;
     made.adopt (res);
-    hipLaunchKernelGGL (k_subset_compact, dim3 (grid_of (ctx, (J.n + 255) / 256)), dim3 (256), 0, ctx->stream, J.rec, (const u32 *) sel, (const u64 *) pos, J.n,
+    hipLaunchKernelGGL (k_subset_compact, dim3 (gt4hip_grid (ctx, (J.n + 255) / 256)), dim3 (256), 0, ctx->stream, J.rec, (const u32 *) sel, (const u64 *) pos, J.n,
                         (u32 *) res->dev, kept);
     HIPCHK (ctx, hipGetLastError ());
     *n_words = kept;

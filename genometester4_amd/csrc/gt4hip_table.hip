@@ -227,6 +227,15 @@ extern "C" int gt4hip_union_table (gt4hip_context *ctx, const gt4hip_list *const
   return rc;
 }
 
+int gt4hip_union_table_checked (gt4hip_context *ctx, const gt4hip_list *const lists[], uint32_t n_lists, gt4hip_count_table *table)
+{
+  for (uint32_t j = 0; j < n_lists; j++) {
+    if (!lists[j]) return GT4HIP_EINVAL;
+    if (lists[j]->word_length != lists[0]->word_length) return gt4hip_fail (ctx, GT4HIP_EWORDLEN, "word lengths differ");
+  }
+  return gt4hip_union_table (ctx, lists, n_lists, table);
+}
+
 /* keys = the keys of lists[0]; column j = the count of each of them in list j (0 when absent), or,
  * with `presence`, 1 when list j holds the key and 0 when it does not (a count may be 0 itself).
  * Two merges per list: lists[0] n L_j keeping L_j's count, then aligned with lists[0] as above. */
@@ -297,15 +306,14 @@ extern "C" int gt4hip_table_download (gt4hip_context *ctx, const gt4hip_count_ta
   HIPCHK (ctx, hipSetDevice (ctx->device));
   if (t->ragged) {
     /* gathered into a staging block on the device, then copied */
+    TempBlocks blk;
     char *tmp = NULL;
-    void *owner = NULL;
     const size_t kb = (size_t) count * 8, cb = (size_t) count * t->n_lists * 4;
-    if (gt4hip_block_alloc (ctx, kb + cb, (void **) &tmp, &owner)) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_table_download: %zu bytes of staging", kb + cb);
+    if (blk.get (ctx, kb + cb, (void **) &tmp)) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_table_download: %zu bytes of staging", kb + cb);
     hipError_t e = table_gather (ctx, t, first, count, host_keys ? tmp : NULL, host_counts ? tmp + kb : NULL);
     if (e == hipSuccess && host_keys) e = hipMemcpyAsync (host_keys, tmp, kb, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && host_counts) e = hipMemcpyAsync (host_counts, tmp + kb, cb, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize (ctx->stream);
-    gt4hip_block_free (owner);
     if (e != hipSuccess) return gt4hip_fail (ctx, GT4HIP_EHIP, "gt4hip_table_download: %s", hipGetErrorString (e));
     return GT4HIP_OK;
   }
