@@ -39,8 +39,7 @@ __global__ __launch_bounds__ (MM_THREADS) void k_gmer_prepare (u64 *__restrict__
   for (u64 i = (u64) blockIdx.x * MM_THREADS + threadIdx.x; i < n; i += (u64) gridDim.x * MM_THREADS) {
     const u64 w = words[i];
     wrong |= k < 32 && (w >> (2 * k)) != 0;
-    const u64 rc = revcomp (w, k);
-    words[i] = rc < w ? rc : w;
+    words[i] = canonical (w, k, 1);
     values[i] = i;
   }
   if (__builtin_amdgcn_ballot_w64 (wrong) && (threadIdx.x & (WAVE - 1)) == 0) atomicOr (bad, 1u);

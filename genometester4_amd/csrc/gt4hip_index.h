@@ -1,7 +1,8 @@
 /* gt4hip_index.h -- what the mismatch difference (gt4hip_mismatch.hip) and the query entry points (gt4hip_query.hip)
- * share: the bucket index over a packed list and its lookup, the reverse complement, the enumeration of substitution
- * variants by rank, the tile-count / scan half of the stable compaction, and the host code that sizes and builds an
- * index.  Include after gt4hip_device.h and gt4hip_host.h; everything here has internal linkage, every file that
+ * share: the bucket index over a packed list and its lookup, the reverse complement and the canonical form of a word, the
+ * enumeration of substitution variants by rank, the steps of the stable compaction over tiles (a tile's total, the scan
+ * of the totals, a kept item's place in its round) with the count and scan kernels, and the host code that
+ * sizes and builds an index.  Include after gt4hip_device.h and gt4hip_host.h; everything here has internal linkage, every file that
  * includes it gets its own copy. */
 #ifndef GT4HIP_INDEX_H
 #define GT4HIP_INDEX_H
@@ -69,6 +70,14 @@ __device__ __forceinline__ u64 revcomp (u64 w, u32 k)
   return __builtin_bitreverse64 (x) >> (64u - 2u * k);
 }
 
+/* the word as a list holds it: the smaller of itself and its reverse complement (canonize == 0: itself) */
+__device__ __forceinline__ u64 canonical (u64 w, u32 k, u32 canonize)
+{
+  if (!canonize) return w;
+  const u64 rc = revcomp (w, k);
+  return rc < w ? rc : w;
+}
+
 /* offsets[s] for s in (prefix (i - 1), prefix (i)] is i; the slots after the last record's prefix are n */
 __global__ __launch_bounds__ (MM_THREADS) void k_index_build (const u32 *rec, u64 n, u32 shift, u64 nb, u64 *off)
 {
@@ -81,30 +90,118 @@ __global__ __launch_bounds__ (MM_THREADS) void k_index_build (const u32 *rec, u6
 
 /* ------------------------------------------------------------------ stable compaction */
 
-/* Tile t covers items [t * MM_TILE, (t + 1) * MM_TILE); round r of it items t * MM_TILE + r * MM_THREADS + thread. */
+/* Tile t covers items [t * MM_TILE, (t + 1) * MM_TILE); round r of it items t * MM_TILE + r * MM_THREADS + thread.  A
+ * count pass adds up what every tile keeps (tile_total), one scan turns the counts into offsets (tile_scan), a fill pass
+ * gives every kept item of a round its place behind the tile's offset (round_place).  All three are a workgroup's: every
+ * thread of it calls them, the same number of times. */
+constexpr int MM_WAVES = MM_THREADS / WAVE;
+
+__device__ __forceinline__ u32 wave_total (u32 v) { return dpp_wave_sum_u32 (v); }
+__device__ __forceinline__ u64 wave_total (u64 v) { return wave_sum (v); }
+
+/* A tile's total in two steps with a barrier between them: every wavefront posts its sum to its entry of `part` (MM_WAVES
+ * entries of LDS), then one thread adds the entries. */
+template <class T>
+__device__ __forceinline__ void wave_post (T mine, T *part)
+{
+  mine = wave_total (mine);
+  if ((threadIdx.x & (WAVE - 1)) == 0) part[threadIdx.x / WAVE] = mine;
+}
+template <class T>
+__device__ __forceinline__ T posted (const T *part)
+{
+  T s = 0;
+  for (int w = 0; w < MM_WAVES; w++) s += part[w];
+  return s;
+}
+
+/* *out = the sum of every thread's `mine`, stored by thread 0; part is free again on return.  Two barriers a call, and no
+ * more for a second quantity with a row of its own. */
+template <class T>
+__device__ __forceinline__ void tile_total (T mine, T *part, T *out)
+{
+  wave_post (mine, part);
+  __syncthreads ();
+  if (threadIdx.x == 0) *out = posted (part);
+  __syncthreads ();
+}
+template <class T, class U>
+__device__ __forceinline__ void tile_total (T mine, T *part, T *out, U mine2, U *part2, U *out2)
+{
+  wave_post (mine, part);
+  wave_post (mine2, part2);
+  __syncthreads ();
+  if (threadIdx.x == 0) {
+    *out = posted (part);
+    *out2 = posted (part2);
+  }
+  __syncthreads ();
+}
+
+/* what the wavefronts before this thread's posted to `part`, and in *round what all of them did */
+template <class T>
+__device__ __forceinline__ T waves_before (const T *part, T *round)
+{
+  const int wv = threadIdx.x / WAVE;
+  T before = 0, all = 0;
+  for (int w = 0; w < MM_WAVES; w++) {
+    before += w < wv ? part[w] : 0;
+    all += part[w];
+  }
+  *round = all;
+  return before;
+}
+
+/* One round of a fill pass: this thread's place among the round's kept items, in thread order, and their number in
+ * *round.  part: MM_WAVES entries of LDS.  One barrier inside; part is read after it, so the caller ends the round with a
+ * barrier of its own before the next round writes it again. */
+__device__ __forceinline__ u32 round_place (bool keep, u32 *part, u32 *round)
+{
+  const int lane = threadIdx.x & (WAVE - 1);
+  const u64 m = __builtin_amdgcn_ballot_w64 (keep);
+  if (lane == 0) part[threadIdx.x / WAVE] = (u32) __popcll (m);
+  __syncthreads ();
+  return waves_before (part, round) + (u32) __popcll (m & ((1ull << lane) - 1));
+}
+
+/* A quantity per item beside it (the sum of `v` over the threads before this one), in a row of LDS of its own and inside
+ * the same two barriers: wave_offset BEFORE round_place gives the part of the sum that lies in this wavefront and posts the
+ * wavefront's total, waves_before (part, &round) AFTER round_place adds the wavefronts before it. */
+__device__ __forceinline__ u64 wave_offset (u64 v, u64 *part)
+{
+  const int lane = threadIdx.x & (WAVE - 1);
+  const u64 incl = wave_inclusive_scan (v, lane);
+  if (lane == WAVE - 1) part[threadIdx.x / WAVE] = incl;
+  return incl - v;
+}
+
 [[maybe_unused]] __global__ __launch_bounds__ (MM_THREADS) void k_tile_count (const u32 *keep, u64 n, u64 n_tiles, u32 *tile_cnt)
 {
-  __shared__ u32 part[MM_THREADS / WAVE];
+  __shared__ u32 part[MM_WAVES];
   for (u64 t = blockIdx.x; t < n_tiles; t += gridDim.x) {
     u32 c = 0;
     for (int r = 0; r < MM_ROUNDS; r++) {
       const u64 i = t * MM_TILE + (u64) r * MM_THREADS + threadIdx.x;
       c += i < n && keep[i];
     }
+    /* (tile_total, open-coded: with this kernel and k_scatter on the helpers the -mm pre-pass measured 1.5 % slower
+     * than with this text, profiles/HISTORY.md) */
     c = dpp_wave_sum_u32 (c);
     if ((threadIdx.x & (WAVE - 1)) == 0) part[threadIdx.x / WAVE] = c;
     __syncthreads ();
     if (threadIdx.x == 0) {
       u32 s = 0;
-      for (int w = 0; w < MM_THREADS / WAVE; w++) s += part[w];
+      for (int w = 0; w < MM_WAVES; w++) s += part[w];
       tile_cnt[t] = s;
     }
     __syncthreads ();
   }
 }
 
-/* exclusive scan of the tile counts (one workgroup), total in *total */
-[[maybe_unused]] __global__ __launch_bounds__ (1024) void k_tile_scan (const u32 *tile_cnt, u64 n_tiles, u64 *tile_off, unsigned long long *total)
+/* exclusive scan of the tile counts (one workgroup of 1024), total in *total; T: u32 (k_tile_scan) or u64 (k_tile_scan64
+ * of gt4hip_query.hip), widened on load */
+template <class T>
+__device__ __forceinline__ void tile_scan (const T *tile_cnt, u64 n_tiles, u64 *tile_off, unsigned long long *total)
 {
   __shared__ u64 wsum[1024 / WAVE];
   __shared__ u64 carry;
@@ -125,6 +222,11 @@ __global__ __launch_bounds__ (MM_THREADS) void k_index_build (const u32 *rec, u6
     __syncthreads ();
   }
   if (threadIdx.x == 0) *total = carry;
+}
+
+[[maybe_unused]] __global__ __launch_bounds__ (1024) void k_tile_scan (const u32 *tile_cnt, u64 n_tiles, u64 *tile_off, unsigned long long *total)
+{
+  tile_scan (tile_cnt, n_tiles, tile_off, total);
 }
 
 /* Variant `r` of the c-substitution variants of a k-base word: r = combination * 3^c + substitutions, the

@@ -77,6 +77,8 @@ __global__ __launch_bounds__ (MM_THREADS) void k_scatter (const u32 *keep, u64 n
     for (int r = 0; r < MM_ROUNDS; r++) {
       const u64 i = t * MM_TILE + (u64) r * MM_THREADS + threadIdx.x;
       const bool k = i < n && keep[i];
+      /* (round_place of gt4hip_index.h, open-coded: with this kernel and k_tile_count on the helpers the -mm pre-pass
+       * measured 1.5 % slower than with this text, profiles/HISTORY.md) */
       const u64 m = __builtin_amdgcn_ballot_w64 (k);
       if (lane == 0) part[wv] = (u32) __popcll (m);
       __syncthreads ();
@@ -148,8 +150,7 @@ __global__ __launch_bounds__ (MM_THREADS) void k_level (Level L, unsigned long l
       const bool skip = L.early && (L.subtract ? L.drop[w] != 0 : L.cnt[w] >= L.cutoff);
       if (!skip) {
         const u64 v = L.words[w] ^ variant_mask<WIDE> (r, L.pow3, L.k, L.c);
-        const u64 rc = revcomp (v, L.k);
-        const u64 cv = rc < v ? rc : v;
+        const u64 cv = canonical (v, L.k, 1);
         const bool pm = find (L.m, cv) != ~0ull;
         my_probes++;
         if (L.subtract) {

@@ -19,12 +19,14 @@
  *
  * --all (gt4hip_query_lookup_all) returns the hits themselves in (query, rank) order: tiles of the flattened space
  * count their hits, one scan turns the counts into offsets, and a second pass over the same tiles repeats the probes
- * and writes every hit to its place.  Nothing of the size of the variant space is ever stored.
+ * and writes every hit to its place (k_query_hits<FILL, LOC>, on the compaction steps of gt4hip_index.h).  Nothing of
+ * the size of the variant space is ever stored.
  *
  * --locations (gt4hip_location_index, gt4hip_query_lookup_locations) returns the hits with every place they occur in a
- * resident GT4I index: the --all passes also count and scan the hits' locations (64-bit), the fill pass leaves per hit
- * where its locations start in the output and in the index, and one segmented gather, dealt by output element, copies
- * and decodes them (k_gather_locations).
+ * resident GT4I index: the same kernel with LOC set also counts the hits' locations (64-bit), a second scan turns those
+ * into offsets, the fill pass leaves per hit where its locations start in the output and in the index, and one segmented
+ * gather, dealt by output element, copies and decodes them (k_gather_locations).  Both entry points are one host body in
+ * stages (lookup_hits).
  *
  * The statistics are one streaming pass each over the 12-byte records: four records per thread as three 16-byte
  * loads where the list is 16-byte aligned, a wavefront reduction, one atomic per wavefront.
@@ -56,13 +58,6 @@ struct Query {
   u64 base[GT4HIP_QUERY_MAX_MM + 2]; /* base[c]: first rank with c substitutions; base[n_mm + 1] = V */
   u64 pow3[GT4HIP_QUERY_MAX_MM + 1];
 };
-
-__device__ __forceinline__ u64 canonical (u64 w, u32 k, u32 canonize)
-{
-  if (!canonize) return w;
-  const u64 rc = revcomp (w, k);
-  return rc < w ? rc : w;
-}
 
 /* variant `r` of query word `wq` (already canonical), as it is looked up */
 template <bool WIDE>
@@ -132,17 +127,34 @@ __global__ __launch_bounds__ (MM_THREADS) void k_query_found (const u32 *values,
   for (u64 i = (u64) blockIdx.x * MM_THREADS + threadIdx.x; i < n; i += (u64) gridDim.x * MM_THREADS) found[i] = values[i] != 0;
 }
 
-/* --all.  Tile t covers items [t * MM_TILE, (t + 1) * MM_TILE) of the flattened space, as in the compaction of
- * gt4hip_mismatch.hip.  FILL == false: tile_cnt[t] = hits of the tile.  FILL == true: the hits to hits[tile_off[t]...]
- * in item order (the probes are repeated: the variant space itself is never stored). */
-template <bool FILL>
-__global__ __launch_bounds__ (MM_THREADS) void k_query_all (Query Q, u64 n_tiles, u32 *tile_cnt, const u64 *tile_off, gt4hip_query_hit *hits)
+/* The arrays of a hit pass over `n_tiles` tiles.  The count pass writes tile_cnt (and tile_loc); the scans make tile_off
+ * (and tile_loc_off) of them; the fill pass reads those and writes the rest.  The second group is --locations' only. */
+struct HitPass {
+  u64 n_tiles;
+  u32 *tile_cnt;          /* hits of a tile */
+  const u64 *tile_off;
+  gt4hip_query_hit *hits;
+  const u64 *first;       /* per record of the list: its first location in the index */
+  u64 *tile_loc;          /* locations of a tile's hits */
+  const u64 *tile_loc_off;
+  u64 *seg_off, *seg_src; /* per hit: its first location's place in the output, and in the index */
+};
+
+/* --all and --locations.  Tile t covers items [t * MM_TILE, (t + 1) * MM_TILE) of the flattened space, as in the
+ * compaction of gt4hip_mismatch.hip.  FILL == false: tile_cnt[t] = hits of the tile.  FILL == true: the hits to
+ * hits[tile_off[t]...] in item order (the probes are repeated: the variant space itself is never stored).  LOC: the
+ * locations of every hit are counted beside it, a record's count being their number: tile_loc[t] = those of the tile's
+ * hits, and for hit h the place of its first location in the output (seg_off[h], from tile_loc_off[t] on) and in the index
+ * (seg_src[h]). */
+template <bool FILL, bool LOC>
+__global__ __launch_bounds__ (MM_THREADS) void k_query_hits (Query Q, HitPass P)
 {
-  __shared__ u32 part[MM_THREADS / WAVE];
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-  for (u64 t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-    u64 pos = FILL ? tile_off[t] : 0;
+  __shared__ u32 part[MM_WAVES];
+  __shared__ u64 lpart[LOC ? MM_WAVES : 1];
+  for (u64 t = blockIdx.x; t < P.n_tiles; t += gridDim.x) {
+    u64 pos = FILL ? P.tile_off[t] : 0, lpos = FILL && LOC ? P.tile_loc_off[t] : 0;
     u32 mine = 0;
+    u64 lmine = 0;
     for (int rd = 0; rd < MM_ROUNDS; rd++) {
       const u64 g = t * MM_TILE + (u64) rd * MM_THREADS + threadIdx.x;
       u64 q = 0, r = 0, cv = 0, j = ~0ull;
@@ -153,40 +165,40 @@ __global__ __launch_bounds__ (MM_THREADS) void k_query_all (Query Q, u64 n_tiles
         j = find (Q.ix, cv);
       }
       const bool hit = j != ~0ull;
-      if (!FILL) {
+      u32 cnt = 0;
+      if constexpr (LOC) cnt = hit ? Q.ix.rec[3 * j + 2] : 0u;
+      if constexpr (!FILL) {
         mine += hit;
+        lmine += cnt;
       } else {
-        const u64 m = __builtin_amdgcn_ballot_w64 (hit);
-        if (lane == 0) part[wv] = (u32) __popcll (m);
-        __syncthreads ();
-        u32 before = 0, round = 0;
-        for (int x = 0; x < MM_THREADS / WAVE; x++) {
-          before += x < wv ? part[x] : 0;
-          round += part[x];
-        }
+        u32 round;
+        u64 loff = 0, lround = 0;
+        if constexpr (LOC) loff = wave_offset (cnt, lpart);
+        const u64 h = pos + round_place (hit, part, &round);
+        if constexpr (LOC) loff += lpos + waves_before (lpart, &lround);
         if (hit) {
-          gt4hip_query_hit h;
-          h.query = q;
-          h.rank = r;
-          h.word = cv;
-          h.count = Q.ix.rec[3 * j + 2];
-          h.reserved = 0;
-          hits[pos + before + (u32) __popcll (m & ((1ull << lane) - 1))] = h;
+          gt4hip_query_hit o;
+          o.query = q;
+          o.rank = r;
+          o.word = cv;
+          o.count = LOC ? cnt : Q.ix.rec[3 * j + 2];
+          o.reserved = 0;
+          P.hits[h] = o;
+        }
+        if constexpr (LOC) {
+          if (hit) {
+            P.seg_off[h] = loff;
+            P.seg_src[h] = P.first[j];
+          }
         }
         pos += round;
+        lpos += lround;
         __syncthreads ();
       }
     }
-    if (!FILL) {
-      mine = dpp_wave_sum_u32 (mine);
-      if (lane == 0) part[wv] = mine;
-      __syncthreads ();
-      if (threadIdx.x == 0) {
-        u32 s = 0;
-        for (int x = 0; x < MM_THREADS / WAVE; x++) s += part[x];
-        tile_cnt[t] = s;
-      }
-      __syncthreads ();
+    if constexpr (!FILL) {
+      if constexpr (LOC) tile_total (mine, part, &P.tile_cnt[t], lmine, lpart, &P.tile_loc[t]);
+      else tile_total (mine, part, &P.tile_cnt[t]);
     }
   }
 }
@@ -213,110 +225,10 @@ __global__ __launch_bounds__ (MM_THREADS) void k_index_split (const u64 *__restr
   if (__builtin_amdgcn_ballot_w64 (wrong) && (threadIdx.x & (WAVE - 1)) == 0) atomicOr (bad, 1u);
 }
 
-/* k_query_all with the locations of every hit counted beside it.  FILL == false: tile_cnt[t] = hits of the tile,
- * tile_loc[t] = their locations.  FILL == true: the hits in item order from hits[tile_off[t]], and for hit h the place
- * of its first location in the output (seg_off[h], from tile_loc_off[t] on) and in the index (seg_src[h]). */
-template <bool FILL>
-__global__ __launch_bounds__ (MM_THREADS) void k_query_loc (Query Q, const u64 *__restrict__ first, u64 n_tiles, u32 *tile_cnt, u64 *tile_loc, const u64 *tile_off,
-                                                            const u64 *tile_loc_off, gt4hip_query_hit *hits, u64 *seg_off, u64 *seg_src)
-{
-  __shared__ u32 part[MM_THREADS / WAVE];
-  __shared__ u64 lpart[MM_THREADS / WAVE];
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-  for (u64 t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-    u64 pos = FILL ? tile_off[t] : 0, lpos = FILL ? tile_loc_off[t] : 0;
-    u32 mine = 0;
-    u64 lmine = 0;
-    for (int rd = 0; rd < MM_ROUNDS; rd++) {
-      const u64 g = t * MM_TILE + (u64) rd * MM_THREADS + threadIdx.x;
-      u64 q = 0, r = 0, cv = 0, j = ~0ull;
-      if (g < Q.total) {
-        q = g / Q.n_var;
-        r = g - q * Q.n_var;
-        cv = query_variant<true> (Q, canonical (Q.words[q], Q.k, Q.canonize), r);
-        j = find (Q.ix, cv);
-      }
-      const bool hit = j != ~0ull;
-      const u32 cnt = hit ? Q.ix.rec[3 * j + 2] : 0u;
-      if (!FILL) {
-        mine += hit;
-        lmine += cnt;
-      } else {
-        const u64 m = __builtin_amdgcn_ballot_w64 (hit);
-        const u64 incl = wave_inclusive_scan ((u64) cnt, lane);
-        if (lane == 0) part[wv] = (u32) __popcll (m);
-        if (lane == WAVE - 1) lpart[wv] = incl;
-        __syncthreads ();
-        u32 before = 0, round = 0;
-        u64 lbefore = 0, lround = 0;
-        for (int x = 0; x < MM_THREADS / WAVE; x++) {
-          before += x < wv ? part[x] : 0;
-          round += part[x];
-          lbefore += x < wv ? lpart[x] : 0;
-          lround += lpart[x];
-        }
-        if (hit) {
-          const u64 h = pos + before + (u32) __popcll (m & ((1ull << lane) - 1));
-          gt4hip_query_hit o;
-          o.query = q;
-          o.rank = r;
-          o.word = cv;
-          o.count = cnt;
-          o.reserved = 0;
-          hits[h] = o;
-          seg_off[h] = lpos + lbefore + incl - cnt;
-          seg_src[h] = first[j];
-        }
-        pos += round;
-        lpos += lround;
-        __syncthreads ();
-      }
-    }
-    if (!FILL) {
-      mine = dpp_wave_sum_u32 (mine);
-      lmine = wave_sum (lmine);
-      if (lane == 0) {
-        part[wv] = mine;
-        lpart[wv] = lmine;
-      }
-      __syncthreads ();
-      if (threadIdx.x == 0) {
-        u32 s = 0;
-        u64 ls = 0;
-        for (int x = 0; x < MM_THREADS / WAVE; x++) {
-          s += part[x];
-          ls += lpart[x];
-        }
-        tile_cnt[t] = s;
-        tile_loc[t] = ls;
-      }
-      __syncthreads ();
-    }
-  }
-}
-
-/* k_tile_scan for 64-bit counts: a tile's locations do not fit 32 bits */
+/* k_tile_scan of 64-bit counts: the locations of a tile's hits do not fit 32 bits */
 __global__ __launch_bounds__ (1024) void k_tile_scan64 (const u64 *tile_cnt, u64 n_tiles, u64 *tile_off, unsigned long long *total)
 {
-  __shared__ u64 wsum[1024 / WAVE];
-  __shared__ u64 carry;
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads ();
-  for (u64 base = 0; base < n_tiles; base += 1024) {
-    const u64 i = base + threadIdx.x;
-    const u64 v = i < n_tiles ? tile_cnt[i] : 0;
-    const u64 incl = wave_inclusive_scan (v, lane);
-    if (lane == WAVE - 1) wsum[wv] = incl;
-    __syncthreads ();
-    u64 before = carry;
-    for (int w = 0; w < wv; w++) before += wsum[w];
-    if (i < n_tiles) tile_off[i] = before + incl - v;
-    __syncthreads ();
-    if (threadIdx.x == 1023) carry = before + incl;
-    __syncthreads ();
-  }
-  if (threadIdx.x == 0) *total = carry;
+  tile_scan (tile_cnt, n_tiles, tile_off, total);
 }
 
 /* how a packed location comes apart (index_map_get_location, src/index-map.c:197-208) */
@@ -702,57 +614,6 @@ extern "C" int gt4hip_query_lookup (gt4hip_context *ctx, gt4hip_query_index *qi,
   return GT4HIP_OK;
 }
 
-extern "C" int gt4hip_query_lookup_all (gt4hip_context *ctx, gt4hip_query_index *qi, const uint64_t *words, uint64_t n, const gt4hip_query_params *prm,
-                                        gt4hip_query_hit *hits, uint64_t capacity, uint64_t *n_hits)
-{
-  if (!ctx || !qi || !prm || !n_hits || (n && !words) || (capacity && !hits)) return GT4HIP_EINVAL;
-  int rc = check_params (ctx, "gt4hip_query_lookup_all", qi, prm);
-  if (rc) return rc;
-  *n_hits = 0;
-  qi->last_ms = 0;
-  if (!n) return GT4HIP_OK;
-  HIPCHK (ctx, hipSetDevice (ctx->device));
-  TempBlocks blk;
-  u64 *d_words = NULL;
-  if ((rc = blk.get (ctx, n * 8, (void **) &d_words))) return rc;
-  Query Q;
-  if ((rc = fill_query (ctx, "gt4hip_query_lookup_all", qi, prm, d_words, n, &Q))) return rc;
-  const u64 tiles = Q.total / MM_TILE + (Q.total % MM_TILE != 0);
-  if (tiles > (1ull << 31))
-    return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_query_lookup_all: %llu queries of %llu variants each are too many for one call: split the batch",
-                        (unsigned long long) n, (unsigned long long) Q.n_var);
-  u32 *tile_cnt = NULL;
-  u64 *tile_off = NULL;
-  if ((rc = blk.get (ctx, tiles * 4, (void **) &tile_cnt)) || (rc = blk.get (ctx, tiles * 8, (void **) &tile_off))) return rc;
-  Timer tm;
-  HIPCHK (ctx, hipEventCreate (&tm.e0));
-  HIPCHK (ctx, hipEventCreate (&tm.e1));
-  HIPCHK (ctx, hipMemcpyAsync (d_words, words, n * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK (ctx, hipEventRecord (tm.e0, ctx->stream));
-  const int grid = gt4hip_grid (ctx, tiles, 1);
-  hipLaunchKernelGGL (k_query_all<false>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, Q, tiles, tile_cnt, (const u64 *) NULL, (gt4hip_query_hit *) NULL);
-  hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, ctx->stream, tile_cnt, tiles, tile_off, ctx->scratch);
-  HIPCHK (ctx, hipGetLastError ());
-  HIPCHK (ctx, hipMemcpyAsync (ctx->scratch_host, ctx->scratch, 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK (ctx, hipStreamSynchronize (ctx->stream));
-  const u64 total_hits = ctx->scratch_host[0];
-  *n_hits = total_hits;
-  if (total_hits && total_hits <= capacity) {
-    gt4hip_query_hit *d_hits = NULL;
-    if ((rc = blk.get (ctx, total_hits * sizeof (gt4hip_query_hit), (void **) &d_hits))) return rc;
-    hipLaunchKernelGGL (k_query_all<true>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, Q, tiles, tile_cnt, tile_off, d_hits);
-    HIPCHK (ctx, hipGetLastError ());
-    HIPCHK (ctx, hipEventRecord (tm.e1, ctx->stream));
-    HIPCHK (ctx, hipMemcpyAsync (hits, d_hits, total_hits * sizeof (gt4hip_query_hit), hipMemcpyDeviceToHost, ctx->stream));
-  } else {
-    HIPCHK (ctx, hipEventRecord (tm.e1, ctx->stream));
-  }
-  HIPCHK (ctx, hipStreamSynchronize (ctx->stream));
-  float ms = 0;
-  if (hipEventElapsedTime (&ms, tm.e0, tm.e1) == hipSuccess) qi->last_ms = ms;
-  return GT4HIP_OK;
-}
-
 /* ------------------------------------------------------------------ statistics */
 
 extern "C" int gt4hip_list_count_stats (gt4hip_context *ctx, const gt4hip_list *list, uint32_t *min, uint32_t *max)
@@ -912,84 +773,162 @@ extern "C" int gt4hip_location_index_create (gt4hip_context *ctx, const void *ho
   return GT4HIP_OK;
 }
 
+/* ------------------------------------------------------------------ --all and --locations: one call in stages */
+
+namespace {
+
+/* A call of gt4hip_query_lookup_all (li == NULL) or gt4hip_query_lookup_locations, `who` in its messages. */
+struct HitCall {
+  gt4hip_context *ctx;
+  const char *who;
+  gt4hip_query_index *qi;
+  const gt4hip_location_index *li;
+  TempBlocks blk;
+  Timer tm, tg; /* tm: the call's kernels (last_ms); tg.e0: where the gather starts (gather_ms) */
+  Query Q;
+  HitPass P;
+  int grid;
+  u64 total_hits, total_locs;
+};
+
+template <bool FILL>
+void launch_hits (const HitCall &c)
+{
+  if (c.li) hipLaunchKernelGGL ((k_query_hits<FILL, true>), dim3 (c.grid), dim3 (MM_THREADS), 0, c.ctx->stream, c.Q, c.P);
+  else hipLaunchKernelGGL ((k_query_hits<FILL, false>), dim3 (c.grid), dim3 (MM_THREADS), 0, c.ctx->stream, c.Q, c.P);
+}
+
+/* the query words on the device, the Query, the tiles and their arrays; the clock starts behind the upload */
+int hits_prepare (HitCall &c, const uint64_t *words, u64 n, const gt4hip_query_params *prm)
+{
+  gt4hip_context *ctx = c.ctx;
+  int rc;
+  u64 *d_words = NULL;
+  if ((rc = c.blk.get (ctx, n * 8, (void **) &d_words))) return rc;
+  if ((rc = fill_query (ctx, c.who, c.qi, prm, d_words, n, &c.Q))) return rc;
+  const u64 tiles = c.Q.total / MM_TILE + (c.Q.total % MM_TILE != 0);
+  if (tiles > (1ull << 31))
+    return gt4hip_fail (ctx, GT4HIP_EINVAL, "%s: %llu queries of %llu variants each are too many for one call: split the batch", c.who, (unsigned long long) n,
+                        (unsigned long long) c.Q.n_var);
+  c.P.n_tiles = tiles;
+  c.grid = gt4hip_grid (ctx, tiles, 1);
+  if ((rc = c.blk.get (ctx, tiles * 4, (void **) &c.P.tile_cnt))) return rc;
+  if (c.li && (rc = c.blk.get (ctx, tiles * 8, (void **) &c.P.tile_loc))) return rc;
+  if ((rc = c.blk.get (ctx, tiles * 8, (void **) &c.P.tile_off))) return rc;
+  if (c.li) {
+    if ((rc = c.blk.get (ctx, tiles * 8, (void **) &c.P.tile_loc_off))) return rc;
+    c.P.first = c.li->first;
+  }
+  HIPCHK (ctx, hipEventCreate (&c.tm.e0));
+  HIPCHK (ctx, hipEventCreate (&c.tm.e1));
+  if (c.li) HIPCHK (ctx, hipEventCreate (&c.tg.e0));
+  HIPCHK (ctx, hipMemcpyAsync (d_words, words, n * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK (ctx, hipEventRecord (c.tm.e0, ctx->stream));
+  return GT4HIP_OK;
+}
+
+/* the count pass, the scan of the hits (and of their locations), the totals back on the host */
+int hits_count (HitCall &c)
+{
+  gt4hip_context *ctx = c.ctx;
+  launch_hits<false> (c);
+  hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, ctx->stream, (const u32 *) c.P.tile_cnt, c.P.n_tiles, (u64 *) c.P.tile_off, ctx->scratch);
+  if (c.li)
+    hipLaunchKernelGGL (k_tile_scan64, dim3 (1), dim3 (1024), 0, ctx->stream, (const u64 *) c.P.tile_loc, c.P.n_tiles, (u64 *) c.P.tile_loc_off, ctx->scratch + 1);
+  HIPCHK (ctx, hipGetLastError ());
+  HIPCHK (ctx, hipMemcpyAsync (ctx->scratch_host, ctx->scratch, c.li ? 16 : 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK (ctx, hipStreamSynchronize (ctx->stream));
+  c.total_hits = ctx->scratch_host[0];
+  c.total_locs = c.li ? ctx->scratch_host[1] : 0;
+  return GT4HIP_OK;
+}
+
+/* the fill pass, the gather of the locations where there is an index, the clock stopped, the copies to the caller started */
+int hits_fill (HitCall &c, gt4hip_query_hit *hits, gt4hip_location *locations)
+{
+  gt4hip_context *ctx = c.ctx;
+  const u64 total_hits = c.total_hits, total_locs = c.total_locs;
+  int rc;
+  if (total_locs > (1ull << 59)) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "%s: %llu locations", c.who, (unsigned long long) total_locs);
+  gt4hip_location *d_locs = NULL;
+  if ((rc = c.blk.get (ctx, total_hits * sizeof (gt4hip_query_hit), (void **) &c.P.hits))) return rc;
+  if (c.li && ((rc = c.blk.get (ctx, total_hits * 8, (void **) &c.P.seg_off)) || (rc = c.blk.get (ctx, total_hits * 8, (void **) &c.P.seg_src)) ||
+               (rc = c.blk.get (ctx, total_locs * sizeof (gt4hip_location), (void **) &d_locs))))
+    return rc;
+  launch_hits<true> (c);
+  HIPCHK (ctx, hipGetLastError ());
+  if (c.li) {
+    HIPCHK (ctx, hipEventRecord (c.tg.e0, ctx->stream));
+    if (total_locs) {
+      const u64 g_tiles = (total_locs + GATHER_TILE - 1) / GATHER_TILE;
+      hipLaunchKernelGGL (k_gather_locations, dim3 (gt4hip_grid (ctx, g_tiles, 1)), dim3 (MM_THREADS), 0, ctx->stream, (const u64 *) c.P.seg_off, (const u64 *) c.P.seg_src,
+                          total_hits, total_locs, (const u64 *) c.li->locs, c.li->bits, d_locs);
+      HIPCHK (ctx, hipGetLastError ());
+    }
+  }
+  HIPCHK (ctx, hipEventRecord (c.tm.e1, ctx->stream));
+  HIPCHK (ctx, hipMemcpyAsync (hits, c.P.hits, total_hits * sizeof (gt4hip_query_hit), hipMemcpyDeviceToHost, ctx->stream));
+  if (!c.li) return GT4HIP_OK;
+  if (total_locs * sizeof (gt4hip_location) < ((size_t) 32 << 20)) {
+    HIPCHK (ctx, hipMemcpyAsync (locations, d_locs, total_locs * sizeof (gt4hip_location), hipMemcpyDeviceToHost, ctx->stream));
+  } else { /* in pieces through the staging threads, as large lists are */
+    HIPCHK (ctx, hipStreamSynchronize (ctx->stream));
+    if ((rc = gt4hip_io_download (ctx, d_locs, locations, total_locs * sizeof (gt4hip_location)))) return rc;
+  }
+  return GT4HIP_OK;
+}
+
+/* The hits of n > 0 words, and with `li` their locations; the caller has checked its arguments.  *n_hits and *n_locations are
+ * always the totals; the arrays are filled only where both capacities suffice. */
+int lookup_hits (gt4hip_context *ctx, const char *who, gt4hip_query_index *qi, const gt4hip_location_index *li, const uint64_t *words, u64 n,
+                 const gt4hip_query_params *prm, gt4hip_query_hit *hits, u64 hit_capacity, uint64_t *n_hits, gt4hip_location *locations, u64 loc_capacity,
+                 uint64_t *n_locations)
+{
+  HIPCHK (ctx, hipSetDevice (ctx->device));
+  HitCall c = { ctx, who, qi, li };
+  int rc;
+  if ((rc = hits_prepare (c, words, n, prm)) || (rc = hits_count (c))) return rc;
+  *n_hits = c.total_hits;
+  if (li) *n_locations = c.total_locs;
+  if (c.total_hits && c.total_hits <= hit_capacity && c.total_locs <= loc_capacity) {
+    if ((rc = hits_fill (c, hits, locations))) return rc;
+  } else {
+    if (li) HIPCHK (ctx, hipEventRecord (c.tg.e0, ctx->stream));
+    HIPCHK (ctx, hipEventRecord (c.tm.e1, ctx->stream));
+  }
+  HIPCHK (ctx, hipStreamSynchronize (ctx->stream));
+  float ms = 0;
+  if (hipEventElapsedTime (&ms, c.tm.e0, c.tm.e1) == hipSuccess) qi->last_ms = ms;
+  if (li && hipEventElapsedTime (&ms, c.tg.e0, c.tm.e1) == hipSuccess) qi->gather_ms = ms;
+  return GT4HIP_OK;
+}
+
+}  // namespace
+
+extern "C" int gt4hip_query_lookup_all (gt4hip_context *ctx, gt4hip_query_index *qi, const uint64_t *words, uint64_t n, const gt4hip_query_params *prm,
+                                        gt4hip_query_hit *hits, uint64_t capacity, uint64_t *n_hits)
+{
+  if (!ctx || !qi || !prm || !n_hits || (n && !words) || (capacity && !hits)) return GT4HIP_EINVAL;
+  const int rc = check_params (ctx, "gt4hip_query_lookup_all", qi, prm);
+  if (rc) return rc;
+  *n_hits = 0;
+  qi->last_ms = 0;
+  if (!n) return GT4HIP_OK;
+  return lookup_hits (ctx, "gt4hip_query_lookup_all", qi, NULL, words, n, prm, hits, capacity, n_hits, NULL, 0, NULL);
+}
+
 extern "C" int gt4hip_query_lookup_locations (gt4hip_context *ctx, gt4hip_query_index *qi, const gt4hip_location_index *li, const uint64_t *words, uint64_t n,
                                               const gt4hip_query_params *prm, gt4hip_query_hit *hits, uint64_t hit_capacity, uint64_t *n_hits,
                                               gt4hip_location *locations, uint64_t loc_capacity, uint64_t *n_locations)
 {
   if (!ctx || !qi || !li || !prm || !n_hits || !n_locations || (n && !words) || (hit_capacity && !hits) || (loc_capacity && !locations)) return GT4HIP_EINVAL;
   if (qi->list != li->list) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_query_lookup_locations: the query index was not made of this location index's list");
-  int rc = check_params (ctx, "gt4hip_query_lookup_locations", qi, prm);
+  const int rc = check_params (ctx, "gt4hip_query_lookup_locations", qi, prm);
   if (rc) return rc;
   *n_hits = *n_locations = 0;
   qi->last_ms = qi->gather_ms = 0;
   if (!n) return GT4HIP_OK;
-  HIPCHK (ctx, hipSetDevice (ctx->device));
-  TempBlocks blk;
-  u64 *d_words = NULL;
-  if ((rc = blk.get (ctx, n * 8, (void **) &d_words))) return rc;
-  Query Q;
-  if ((rc = fill_query (ctx, "gt4hip_query_lookup_locations", qi, prm, d_words, n, &Q))) return rc;
-  const u64 tiles = Q.total / MM_TILE + (Q.total % MM_TILE != 0);
-  if (tiles > (1ull << 31))
-    return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_query_lookup_locations: %llu queries of %llu variants each are too many for one call: split the batch",
-                        (unsigned long long) n, (unsigned long long) Q.n_var);
-  u32 *tile_cnt = NULL;
-  u64 *tile_loc = NULL, *tile_off = NULL, *tile_loc_off = NULL;
-  if ((rc = blk.get (ctx, tiles * 4, (void **) &tile_cnt)) || (rc = blk.get (ctx, tiles * 8, (void **) &tile_loc)) || (rc = blk.get (ctx, tiles * 8, (void **) &tile_off)) ||
-      (rc = blk.get (ctx, tiles * 8, (void **) &tile_loc_off)))
-    return rc;
-  Timer tm, tg;
-  HIPCHK (ctx, hipEventCreate (&tm.e0));
-  HIPCHK (ctx, hipEventCreate (&tm.e1));
-  HIPCHK (ctx, hipEventCreate (&tg.e0));
-  HIPCHK (ctx, hipMemcpyAsync (d_words, words, n * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK (ctx, hipEventRecord (tm.e0, ctx->stream));
-  const int grid = gt4hip_grid (ctx, tiles, 1);
-  hipLaunchKernelGGL (k_query_loc<false>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, Q, (const u64 *) li->first, tiles, tile_cnt, tile_loc, (const u64 *) NULL,
-                      (const u64 *) NULL, (gt4hip_query_hit *) NULL, (u64 *) NULL, (u64 *) NULL);
-  hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, ctx->stream, tile_cnt, tiles, tile_off, ctx->scratch);
-  hipLaunchKernelGGL (k_tile_scan64, dim3 (1), dim3 (1024), 0, ctx->stream, (const u64 *) tile_loc, tiles, tile_loc_off, ctx->scratch + 1);
-  HIPCHK (ctx, hipGetLastError ());
-  HIPCHK (ctx, hipMemcpyAsync (ctx->scratch_host, ctx->scratch, 16, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK (ctx, hipStreamSynchronize (ctx->stream));
-  const u64 total_hits = ctx->scratch_host[0], total_locs = ctx->scratch_host[1];
-  *n_hits = total_hits;
-  *n_locations = total_locs;
-  if (total_hits && total_hits <= hit_capacity && total_locs <= loc_capacity) {
-    if (total_locs > (1ull << 59)) return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_query_lookup_locations: %llu locations", (unsigned long long) total_locs);
-    gt4hip_query_hit *d_hits = NULL;
-    gt4hip_location *d_locs = NULL;
-    u64 *seg_off = NULL, *seg_src = NULL;
-    if ((rc = blk.get (ctx, total_hits * sizeof (gt4hip_query_hit), (void **) &d_hits)) || (rc = blk.get (ctx, total_hits * 8, (void **) &seg_off)) ||
-        (rc = blk.get (ctx, total_hits * 8, (void **) &seg_src)) || (rc = blk.get (ctx, total_locs * sizeof (gt4hip_location), (void **) &d_locs)))
-      return rc;
-    hipLaunchKernelGGL (k_query_loc<true>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, Q, (const u64 *) li->first, tiles, tile_cnt, tile_loc, (const u64 *) tile_off,
-                        (const u64 *) tile_loc_off, d_hits, seg_off, seg_src);
-    HIPCHK (ctx, hipGetLastError ());
-    HIPCHK (ctx, hipEventRecord (tg.e0, ctx->stream));
-    if (total_locs) {
-      const u64 g_tiles = (total_locs + GATHER_TILE - 1) / GATHER_TILE;
-      hipLaunchKernelGGL (k_gather_locations, dim3 (gt4hip_grid (ctx, g_tiles, 1)), dim3 (MM_THREADS), 0, ctx->stream, (const u64 *) seg_off, (const u64 *) seg_src, total_hits,
-                          total_locs, (const u64 *) li->locs, li->bits, d_locs);
-      HIPCHK (ctx, hipGetLastError ());
-    }
-    HIPCHK (ctx, hipEventRecord (tm.e1, ctx->stream));
-    HIPCHK (ctx, hipMemcpyAsync (hits, d_hits, total_hits * sizeof (gt4hip_query_hit), hipMemcpyDeviceToHost, ctx->stream));
-    if (total_locs * sizeof (gt4hip_location) < ((size_t) 32 << 20)) {
-      HIPCHK (ctx, hipMemcpyAsync (locations, d_locs, total_locs * sizeof (gt4hip_location), hipMemcpyDeviceToHost, ctx->stream));
-    } else { /* in pieces through the staging threads, as large lists are */
-      HIPCHK (ctx, hipStreamSynchronize (ctx->stream));
-      if ((rc = gt4hip_io_download (ctx, d_locs, locations, total_locs * sizeof (gt4hip_location)))) return rc;
-    }
-  } else {
-    HIPCHK (ctx, hipEventRecord (tg.e0, ctx->stream));
-    HIPCHK (ctx, hipEventRecord (tm.e1, ctx->stream));
-  }
-  HIPCHK (ctx, hipStreamSynchronize (ctx->stream));
-  float ms = 0;
-  if (hipEventElapsedTime (&ms, tm.e0, tm.e1) == hipSuccess) qi->last_ms = ms;
-  if (hipEventElapsedTime (&ms, tg.e0, tm.e1) == hipSuccess) qi->gather_ms = ms;
-  return GT4HIP_OK;
+  return lookup_hits (ctx, "gt4hip_query_lookup_locations", qi, li, words, n, prm, hits, hit_capacity, n_hits, locations, loc_capacity, n_locations);
 }
 
 extern "C" double gt4hip_query_index_gather_ms (const gt4hip_query_index *qi) { return qi ? qi->gather_ms : 0.0; }

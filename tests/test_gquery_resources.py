@@ -29,12 +29,24 @@ def K():
 def test_query_kernels_do_not_spill(K):
     rows = K.table("gt4hip_query.hip")
     names = [r["name"] for r in rows]
-    for want in ("k_query<false>", "k_query<true>", "k_query_exact", "k_query_all<false>", "k_query_all<true>", "k_count_stats", "k_count_split",
-                 "k_count_histogram<true>", "k_count_histogram<false>", "k_gc"):
+    for want in ("k_query<false>", "k_query<true>", "k_query_exact", "k_query_hits<false, false>", "k_query_hits<true, false>", "k_query_hits<false, true>",
+                 "k_query_hits<true, true>", "k_count_stats", "k_count_split", "k_count_histogram<true>", "k_count_histogram<false>", "k_gc"):
         assert want in names, names
     bad = [(r["name"], r["vspill"], r["sspill"], r["scratch"]) for r in rows if r["vspill"] or r["sspill"] or r["scratch"]]
     assert not bad, bad
     assert all(r["vgpr"] <= 64 for r in rows), rows  # eight wavefronts per SIMD, as the grids are sized for
+
+
+# (VGPR, LDS bytes) of k_query_all<FILL> and k_query_loc<FILL> before they became k_query_hits<FILL, LOC>: ceilings
+HITS_BEFORE = {
+    "k_query_hits<false, false>": (28, 16), "k_query_hits<true, false>": (36, 16), "k_query_hits<false, true>": (36, 48), "k_query_hits<true, true>": (54, 48),
+}
+
+
+def test_the_merged_hit_kernel_costs_no_more_than_its_two_parents(K):
+    rows = {r["name"]: (r["vgpr"], r["lds"]) for r in K.table("gt4hip_query.hip")}
+    for name, (vgpr, lds) in HITS_BEFORE.items():
+        assert rows[name][0] <= vgpr and rows[name][1] <= lds, (name, rows[name])
 
 
 def test_mismatch_kernels_keep_their_resources(K):
