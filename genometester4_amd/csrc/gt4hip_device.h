@@ -78,6 +78,49 @@ __device__ __forceinline__ u32 dpp_wave_sum_u32 (u32 v)
   return (u32) __builtin_amdgcn_readlane ((int) dpp_inclusive_scan_u32 (v), WAVE - 1);
 }
 
+__device__ __forceinline__ u32 wave_prefix (u32 v, int) { return dpp_inclusive_scan_u32 (v); }
+__device__ __forceinline__ u64 wave_prefix (u64 v, int lane) { return wave_inclusive_scan (v, lane); }
+
+/* Exclusive scan of N arrays (one or two) of n entries each by ONE workgroup of 1024 threads, all of which call it:
+ * out[a][i] = in[a][0] + .. + in[a][i - 1], total[a] = the whole sum (total == nullptr: not wanted).  out[a] may be
+ * in[a]; In is widened to Out on load.  Rounds of 1024 entries: a wave scan, the wavefronts' totals through LDS, the
+ * rounds before through `carry` -- three barriers a round, which the arrays share. */
+template <int N, class In, class Out>
+__device__ __forceinline__ void workgroup_scan (const In *const (&in)[N], Out *const (&out)[N], u64 n, Out *total)
+{
+  static_assert (N == 1 || N == 2, "one array or two");
+  __shared__ Out wsum[N][1024 / WAVE];
+  __shared__ Out carry[N];
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  if (threadIdx.x == 0)
+    for (int a = 0; a < N; a++) carry[a] = 0;
+  __syncthreads ();
+  for (u64 base = 0; base < n; base += 1024) {
+    const u64 i = base + threadIdx.x;
+    Out v[N], incl[N], before[N];
+#pragma unroll
+    for (int a = 0; a < N; a++) v[a] = i < n ? (Out) in[a][i] : (Out) 0;
+#pragma unroll
+    for (int a = 0; a < N; a++) {
+      incl[a] = wave_prefix (v[a], lane);
+      if (lane == WAVE - 1) wsum[a][wv] = incl[a];
+    }
+    __syncthreads ();
+#pragma unroll
+    for (int a = 0; a < N; a++) {
+      before[a] = carry[a];
+      for (int w = 0; w < wv; w++) before[a] += wsum[a][w];
+      if (i < n) out[a][i] = before[a] + incl[a] - v[a];
+    }
+    __syncthreads ();
+    if (threadIdx.x == 1023)
+      for (int a = 0; a < N; a++) carry[a] = before[a] + incl[a];
+    __syncthreads ();
+  }
+  if (total && threadIdx.x == 0)
+    for (int a = 0; a < N; a++) total[a] = carry[a];
+}
+
 /* Exclusive prefix of the chunk ballots' popcounts (up to 128 chunks: two per lane, packed into
  * the halves of one dword for a single scan) and the empty sentinel chunk behind them; returns the
  * tile total.  Every lane of the calling wavefront takes part. */

@@ -91,7 +91,7 @@ __global__ __launch_bounds__ (MM_THREADS) void k_index_build (const u32 *rec, u6
 /* ------------------------------------------------------------------ stable compaction */
 
 /* Tile t covers items [t * MM_TILE, (t + 1) * MM_TILE); round r of it items t * MM_TILE + r * MM_THREADS + thread.  A
- * count pass adds up what every tile keeps (tile_total), one scan turns the counts into offsets (tile_scan), a fill pass
+ * count pass adds up what every tile keeps (tile_total), one scan turns the counts into offsets (k_tile_scan), a fill pass
  * gives every kept item of a round its place behind the tile's offset (round_place).  All three are a workgroup's: every
  * thread of it calls them, the same number of times. */
 constexpr int MM_WAVES = MM_THREADS / WAVE;
@@ -198,35 +198,10 @@ __device__ __forceinline__ u64 wave_offset (u64 v, u64 *part)
   }
 }
 
-/* exclusive scan of the tile counts (one workgroup of 1024), total in *total; T: u32 (k_tile_scan) or u64 (k_tile_scan64
- * of gt4hip_query.hip), widened on load */
-template <class T>
-__device__ __forceinline__ void tile_scan (const T *tile_cnt, u64 n_tiles, u64 *tile_off, unsigned long long *total)
-{
-  __shared__ u64 wsum[1024 / WAVE];
-  __shared__ u64 carry;
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads ();
-  for (u64 base = 0; base < n_tiles; base += 1024) {
-    const u64 i = base + threadIdx.x;
-    const u64 v = i < n_tiles ? tile_cnt[i] : 0;
-    const u64 incl = wave_inclusive_scan (v, lane);
-    if (lane == WAVE - 1) wsum[wv] = incl;
-    __syncthreads ();
-    u64 before = carry;
-    for (int w = 0; w < wv; w++) before += wsum[w];
-    if (i < n_tiles) tile_off[i] = before + incl - v;
-    __syncthreads ();
-    if (threadIdx.x == 1023) carry = before + incl;
-    __syncthreads ();
-  }
-  if (threadIdx.x == 0) *total = carry;
-}
-
+/* exclusive scan of the tile counts, widened to 64 bits, total in *total (k_tile_scan64 of gt4hip_query.hip: 64-bit counts) */
 [[maybe_unused]] __global__ __launch_bounds__ (1024) void k_tile_scan (const u32 *tile_cnt, u64 n_tiles, u64 *tile_off, unsigned long long *total)
 {
-  tile_scan (tile_cnt, n_tiles, tile_off, total);
+  workgroup_scan<1> ({tile_cnt}, {tile_off}, n_tiles, total);
 }
 
 /* Variant `r` of the c-substitution variants of a k-base word: r = combination * 3^c + substitutions, the

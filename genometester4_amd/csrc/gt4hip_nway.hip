@@ -59,6 +59,14 @@
  *      k_nway_base_sums, _scan, rows before every tile and where its rows lie (the ragged count table's index)
  *      k_nway_tile_bases,
  *      k_nway_padded_bases
+ *
+ * gt4hip_nway_part.h    the constants, K5, every rule of K6 once (a tile's key range, bucket constants, the clustering
+ *                       test, the cut search of eight lists, a list's prefix over the brackets), k_nway_partition,
+ *                       k_nway_probe, k_nway_emit and the count table's index kernels; its scans are workgroup_scan
+ *                       (gt4hip_device.h)
+ * gt4hip_nway_rows8.h,  what differs between the widths: k_nway_sample_counts, what k_nway_partition_rows stages in
+ * gt4hip_nway_rows32.h  LDS, how k_nway_bracket_bases deals the lists to wavefronts, k_nway_need
+ * gt4hip_nway_tile.h    K7; gt4hip_nway_host.h: the host side of a call
  */
 #define GT4_RESOLVE_LOOKBACK 0
 #include "gt4hip_device.h"

@@ -104,16 +104,158 @@ __device__ __forceinline__ u64 nway_boundary_key (const u32 *__restrict__ merged
   return load_key (merged, sidx);
 }
 
+/* The key range [lo, hi] of a tile lies between the boundary keys: lo = the boundary key in front + 1, hi = the one
+ * behind.  The first tile starts at the smallest first key of the lists, the last one ends at their largest last key. */
+__device__ __forceinline__ u64 nway_first_key (const NwayParams &p)
+{
+  u64 lo = ~0ull;
+  for (u32 j = 0; j < p.k; j++)
+    if (p.n[j]) {
+      const u64 f = load_key (p.list[j], 0);
+      lo = f < lo ? f : lo;
+    }
+  return lo;
+}
+
+__device__ __forceinline__ u64 nway_last_key (const NwayParams &p)
+{
+  u64 hi = 0;
+  for (u32 j = 0; j < p.k; j++)
+    if (p.n[j]) {
+      const u64 l = load_key (p.list[j], p.n[j] - 1);
+      hi = l > hi ? l : hi;
+    }
+  return hi;
+}
+
+/* the bucket function of the keys lo .. hi: shift | direct << 8 | multiplier << 32 (decoded by the tile kernel) */
+__device__ __forceinline__ u64 nway_bucket_consts (u64 lo, u64 hi, u32 n_buckets)
+{
+  const u64 D = hi >= lo ? hi - lo : 0ull;
+  const u32 bl = D ? 64u - (u32) __builtin_clzll (D) : 0u;
+  const u32 sh = bl > 32u ? bl - 32u : 0u;
+  const u32 vmax = (u32) (D >> sh);
+  const bool direct = vmax < n_buckets;
+  const u32 mul = direct ? 0u : (u32) (((u64) n_buckets << 32) / ((u64) vmax + 1ull));
+  return (u64) sh | (direct ? 1ull << 8 : (u64) mul << 32);
+}
+
+/* Will the interpolation work?  The tile's own samples tell: G keys spread over thousands of buckets share hardly
+ * any when the keys are spread evenly; stretches of adjacent keys between wide gaps put most of them into a few.
+ * Such a tile is bucketed by its pivot run at once (bit 9 of the bucket constants).  add () takes the tile's samples
+ * in order: those outside [lo, hi] do not count, and neither does a key equal to the one before it (equal keys of
+ * different lists share a bucket by right). */
+struct NwayClusterTest {
+  u64 lo, hi, prev_key = 0;
+  u32 sh, mul, prev = 0xffffffffu, same = 0, cnt = 0;
+  bool direct, have_prev = false;
+  __device__ __forceinline__ NwayClusterTest (u64 lo_, u64 hi_, u64 bk) : lo (lo_), hi (hi_), sh ((u32) bk & 0xffu), mul ((u32) (bk >> 32)), direct ((bk >> 8) & 1u) {}
+  __device__ __forceinline__ void add (u64 key)
+  {
+    if (key < lo || key > hi || (have_prev && key == prev_key)) return;
+    prev_key = key;
+    have_prev = true;
+    const u32 vv = (u32) ((key - lo) >> sh);
+    const u32 b = direct ? vv : __umulhi (vv, mul);
+    same += b == prev ? 1u : 0u;
+    prev = b;
+    cnt++;
+  }
+  __device__ __forceinline__ bool clustered () const { return cnt >= 8 && 2 * same > cnt; }
+};
+
+/* The cuts of the eight lists g0 .. g0 + 7 for tile t > 0 behind boundary key x, from SAMPLE COUNTS (see below):
+ * c0, c1 hold the samples of lists g0 .. g0 + 3 and g0 + 4 .. g0 + 7 in front of the tile inside its bracket as
+ * 16-bit fields, bases_row the bracket's own bases, x_list the list the boundary sample came from (its cut is
+ * behind that very sample, no search).  The eight searches go in step: every round asks for one key of every
+ * list.  a[i] = the cut of list g0 + i (0 for a list past p.k and for tile 0). */
+__device__ __forceinline__ void nway_cut_search8 (const NwayParams &p, u32 g0, u64 t, u64 x, u32 x_list, const u32 *bases_row, u64 c0, u64 c1, u64 (&a)[8])
+{
+  u64 h[8];
+  u32 need = 0; /* bit i: the stretch that holds the cut is not found yet (as an array of bool the 32-list kernel spilt four vector registers) */
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const u32 li = g0 + (u32) i;
+    const u64 c = li < p.k && t > 0 ? (u64) bases_row[li] + (((i < 4 ? c0 : c1) >> (16 * (i & 3))) & 0xffffu) : 0ull;
+    a[i] = h[i] = c * NWAY_SAMPLE;
+    need |= li < p.k && t > 0 && li != x_list ? 1u << i : 0u; /* (c counts the boundary sample itself: c * S is one behind it) */
+  }
+  for (int round = 0; round < 3; round++) { /* (a sample equal to the boundary key merged behind it: one stretch further; the list's tail: one more) */
+    u64 e[8], kk[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      const u64 ni = p.n[g0 + i];
+      e[i] = a[i] + NWAY_SAMPLE < ni ? a[i] + NWAY_SAMPLE : ni;
+      kk[i] = ((need >> i) & 1u) && e[i] > a[i] ? load_key (p.list[g0 + i], e[i] - 1) : 0ull;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      if (!((need >> i) & 1u)) continue;
+      if (e[i] == a[i]) { /* the list ends here */
+        h[i] = a[i];
+        need &= ~(1u << i);
+      } else if (kk[i] <= x) { /* the whole stretch belongs to earlier tiles */
+        a[i] = h[i] = e[i];
+      } else {
+        h[i] = e[i] - 1;
+        need &= ~(1u << i);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 8; i++)
+    if ((need >> i) & 1u) h[i] = p.n[g0 + i]; /* (cannot happen: keys are unique inside a list; searched in full all the same) */
+  for (;;) {
+    bool any = false;
+    u64 km[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) km[i] = a[i] < h[i] ? load_key (p.list[g0 + i], (a[i] + h[i]) >> 1) : 0ull;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      if (a[i] >= h[i]) continue;
+      const u64 mid = (a[i] + h[i]) >> 1;
+      if (km[i] <= x) a[i] = mid + 1;
+      else h[i] = mid;
+      any |= a[i] < h[i];
+    }
+    if (!any) break;
+  }
+}
+
+/* cnt[b * NWAY_MAX + list] for b < n_brackets -> its exclusive prefix over the brackets, by one wavefront */
+__device__ __forceinline__ void nway_bracket_prefix (u32 *__restrict__ cnt, u64 n_brackets, int list, int lane)
+{
+  u64 carry = 0;
+  constexpr int U = 4; /* brackets per lane and round: the loads of a round are asked for together (one per lane and round was a memory round trip per 64 brackets: 0.18 ms for 2e4 brackets) */
+  for (u64 b0 = 0; b0 < n_brackets; b0 += U * WAVE) {
+    u64 v[U], sum = 0;
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const u64 b = b0 + (u64) (U * lane + u);
+      v[u] = b < n_brackets ? cnt[b * NWAY_MAX + list] : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) sum += v[u];
+    const u64 incl = wave_inclusive_scan (sum, lane);
+    u64 before = carry + incl - sum;
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const u64 b = b0 + (u64) (U * lane + u);
+      if (b < n_brackets) cnt[b * NWAY_MAX + list] = (u32) before;
+      before += v[u];
+    }
+    carry += (u64) (u32) __builtin_amdgcn_readlane ((int) (u32) incl, WAVE - 1) | ((u64) (u32) __builtin_amdgcn_readlane ((int) (u32) (incl >> 32), WAVE - 1) << 32);
+  }
+}
+
 /* part[t][i], i < 8: first record of list i that belongs to tile t or a later one.  Tile t > 0 starts
  * behind the boundary key x_t: records with key <= x_t belong to earlier tiles (upper bound), equal
  * keys of different lists therefore always meet in one tile.
- * part[t][8]: the smallest key tile t can hold; part[t][9]: shift | direct << 8 | multiplier << 32 of
- * its bucket function (see nway_bucket). */
+ * part[t][8]: the smallest key tile t can hold; part[t][9]: the constants of its bucket function
+ * (nway_bucket_consts), bit 9: its samples are clustered (NwayClusterTest). */
 /* Two passes, as the pair kernel's partition: pass 0 searches every NWAY_COARSE-th boundary in the whole
  * lists, pass 1 the others between their coarse neighbours (the cuts are monotone in the boundary
  * key): half the dependent reads, and neighbouring threads probe the same few cache lines. */
-__device__ __forceinline__ u64 nway_bucket_consts (u64 lo, u64 hi, u32 n_buckets);
-
 constexpr u64 NWAY_COARSE = 64;
 
 __global__ void k_nway_partition (NwayParams p, const u32 *__restrict__ merged, u64 m_total, u32 G, u32 n_buckets, u64 *__restrict__ part, int pass)
@@ -147,59 +289,17 @@ __global__ void k_nway_partition (NwayParams p, const u32 *__restrict__ merged, 
       v = lo;
     }
   } else if (t < p.num_tiles) {
-    /* key range [lo, hi] of the tile: between the boundary keys; the first tile starts at the smallest
-     * first key, the last one ends at the largest last key */
-    u64 lo, hi;
-    if (t == 0) {
-      lo = ~0ull;
-      for (u32 j = 0; j < p.k; j++)
-        if (p.n[j]) {
-          const u64 f = load_key (p.list[j], 0);
-          lo = f < lo ? f : lo;
-        }
-    } else {
-      lo = nway_boundary_key (merged, m_total, G, p.num_tiles, t) + 1ull;
-    }
-    if (t + 1 == p.num_tiles) {
-      hi = 0;
-      for (u32 j = 0; j < p.k; j++)
-        if (p.n[j]) {
-          const u64 l = load_key (p.list[j], p.n[j] - 1);
-          hi = l > hi ? l : hi;
-        }
-    } else {
-      hi = nway_boundary_key (merged, m_total, G, p.num_tiles, t + 1);
-    }
+    const u64 lo = t == 0 ? nway_first_key (p) : nway_boundary_key (merged, m_total, G, p.num_tiles, t) + 1ull;
+    const u64 hi = t + 1 == p.num_tiles ? nway_last_key (p) : nway_boundary_key (merged, m_total, G, p.num_tiles, t + 1);
     if (i == NWAY_MAX) {
       v = lo;
     } else {
-      const u64 D = hi >= lo ? hi - lo : 0ull;
-      const u32 bl = D ? 64u - (u32) __builtin_clzll (D) : 0u;
-      const u32 sh = bl > 32u ? bl - 32u : 0u;
-      const u32 vmax = (u32) (D >> sh);
-      const bool direct = vmax < n_buckets;
-      const u32 mul = direct ? 0u : (u32) (((u64) n_buckets << 32) / ((u64) vmax + 1ull));
-      v = (u64) sh | (direct ? 1ull << 8 : (u64) mul << 32);
-      /* Will the interpolation work?  The tile's own samples tell: G keys spread over thousands of
-       * buckets share hardly any when the keys are spread evenly; stretches of adjacent keys between
-       * wide gaps put most of them into a few.  Such a tile is bucketed by its pivot run at once. */
+      v = nway_bucket_consts (lo, hi, n_buckets);
       if (merged && t + 1 < p.num_tiles) {
         const u64 first = t * (u64) G, last = (t + 1) * (u64) G < m_total ? (t + 1) * (u64) G : m_total;
-        u32 prev = 0xffffffffu, same = 0, cnt = 0;
-        u64 prev_key = 0;
-        bool have_prev = false;
-        for (u64 j = first; j < last; j++) {
-          const u64 x = load_key (merged, j);
-          if (x < lo || x > hi || (have_prev && x == prev_key)) continue; /* (equal keys of different lists share a bucket by right) */
-          prev_key = x;
-          have_prev = true;
-          const u32 vv = (u32) ((x - lo) >> sh);
-          const u32 b = direct ? vv : __umulhi (vv, mul);
-          same += b == prev ? 1u : 0u;
-          prev = b;
-          cnt++;
-        }
-        if (cnt >= 8 && 2 * same > cnt) v |= 1ull << 9;
+        NwayClusterTest test (lo, hi, v);
+        for (u64 j = first; j < last; j++) test.add (load_key (merged, j));
+        if (test.clustered ()) v |= 1ull << 9;
       }
     }
   }
@@ -272,44 +372,9 @@ __global__ __launch_bounds__ (256) void k_nway_probe (const u32 *__restrict__ li
  *   k_nway_emit    the final table: row base + prefix inside the block; the second half's cuts by eight
  *                  upper bounds of the pivot key inside the tile's runs, key ranges and bucket constants per half */
 
-__device__ __forceinline__ u64 nway_bucket_consts (u64 lo, u64 hi, u32 n_buckets)
-{
-  const u64 D = hi >= lo ? hi - lo : 0ull;
-  const u32 bl = D ? 64u - (u32) __builtin_clzll (D) : 0u;
-  const u32 sh = bl > 32u ? bl - 32u : 0u;
-  const u32 vmax = (u32) (D >> sh);
-  const bool direct = vmax < n_buckets;
-  const u32 mul = direct ? 0u : (u32) (((u64) n_buckets << 32) / ((u64) vmax + 1ull));
-  return (u64) sh | (direct ? 1ull << 8 : (u64) mul << 32);
-}
-
-
 __global__ __launch_bounds__ (1024) void k_nway_need_scan (u32 *__restrict__ block_sums, u32 n_blocks, u32 *__restrict__ total)
 {
-  __shared__ u32 wsum[16];
-  __shared__ u32 carry_s;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads ();
-  for (u32 b0 = 0; b0 < n_blocks; b0 += 1024) {
-    const u32 i = b0 + threadIdx.x;
-    const u32 v = i < n_blocks ? block_sums[i] : 0u;
-    const u32 incl = dpp_inclusive_scan_u32 (v);
-    if (lane == 63) wsum[wid] = incl;
-    __syncthreads ();
-    u32 before = 0, all = 0;
-    for (int w = 0; w < 16; w++) {
-      const u32 x = wsum[w];
-      before += w < wid ? x : 0u;
-      all += x;
-    }
-    const u32 c = carry_s;
-    if (i < n_blocks) block_sums[i] = c + before + incl - v;
-    __syncthreads ();
-    if (threadIdx.x == 0) carry_s = c + all;
-    __syncthreads ();
-  }
-  if (threadIdx.x == 0) *total = carry_s;
+  workgroup_scan<1> ({block_sums}, {block_sums}, n_blocks, total);
 }
 
 __global__ __launch_bounds__ (NWAY_SPLIT_BLOCK) void k_nway_emit (NwayParams p, const u64 *__restrict__ part, u32 num_tiles, const u32 *__restrict__ need, const u32 *__restrict__ block_base,
@@ -348,17 +413,7 @@ __global__ __launch_bounds__ (NWAY_SPLIT_BLOCK) void k_nway_emit (NwayParams p, 
   }
   const u64 pivot = load_key (p.list[longest], part[t * NWAY_PSTRIDE + longest] + (best - 1) / 2);
   /* the tile's largest possible key: the next tile's smallest minus one; the last tile ends at the lists' largest key */
-  u64 hi_key;
-  if (t + 1 < num_tiles) {
-    hi_key = part[(t + 1) * NWAY_PSTRIDE + NWAY_MAX] - 1ull;
-  } else {
-    hi_key = 0;
-    for (u32 j = 0; j < p.k; j++)
-      if (p.n[j]) {
-        const u64 l = load_key (p.list[j], p.n[j] - 1);
-        hi_key = l > hi_key ? l : hi_key;
-      }
-  }
+  const u64 hi_key = t + 1 < num_tiles ? part[(t + 1) * NWAY_PSTRIDE + NWAY_MAX] - 1ull : nway_last_key (p);
   const u64 clustered = row_bk & (1ull << 9);
   /* a piece that still does not fit (runs of very different length: the pivot halves the longest only) sends the
    * call back to fewer samples per tile */
@@ -412,42 +467,20 @@ __global__ __launch_bounds__ (1024) void k_nway_base_sums (const u32 *__restrict
 
 __global__ __launch_bounds__ (1024) void k_nway_base_scan (u64 *__restrict__ block_sums, u64 n_blocks)
 {
-  __shared__ u64 wsum[16];
-  __shared__ u64 carry_s;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads ();
-  for (u64 b0 = 0; b0 < n_blocks; b0 += 1024) {
-    const u64 i = b0 + threadIdx.x;
-    const u64 v = i < n_blocks ? block_sums[i] : 0ull;
-    const u64 incl = wave_inclusive_scan (v, lane);
-    if (lane == 63) wsum[wid] = incl;
-    __syncthreads ();
-    u64 before = 0, all = 0;
-    for (int w = 0; w < 16; w++) {
-      const u64 x = wsum[w];
-      before += w < wid ? x : 0;
-      all += x;
-    }
-    const u64 c = carry_s;
-    if (i < n_blocks) block_sums[i] = c + before + incl - v;
-    __syncthreads ();
-    if (threadIdx.x == 0) carry_s = c + all;
-    __syncthreads ();
-  }
+  workgroup_scan<1> ({block_sums}, {block_sums}, n_blocks, (u64 *) nullptr);
 }
 
 /* bases[t] for t <= tiles (bases[tiles] = the total) */
 __global__ __launch_bounds__ (1024) void k_nway_tile_bases (const u32 *__restrict__ totals, u64 tiles, const u64 *__restrict__ block_base, u64 *__restrict__ bases)
 {
-  __shared__ u64 wsum[16];
+  __shared__ u64 ws[16];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const u64 i = (u64) blockIdx.x * 1024 + threadIdx.x;
   const u64 v = i < tiles ? (u64) totals[i] : 0ull;
   const u64 incl = wave_inclusive_scan (v, lane);
-  if (lane == 63) wsum[wid] = incl;
+  if (lane == 63) ws[wid] = incl;
   __syncthreads ();
   u64 before = block_base[blockIdx.x];
-  for (int w = 0; w < wid; w++) before += wsum[w];
+  for (int w = 0; w < wid; w++) before += ws[w];
   if (i <= tiles) bases[i] = before + incl - v;
 }

@@ -22,30 +22,7 @@ __global__ __launch_bounds__ (256) void k_nway_sample_counts (const u32 *__restr
 
 __global__ __launch_bounds__ (1024) void k_nway_bracket_bases (u32 *__restrict__ cnt, u64 n_brackets)
 {
-  const int lane = threadIdx.x & 63;
-  for (int list = threadIdx.x >> 6; list < NWAY_MAX; list += 16) {
-    u64 carry = 0;
-    constexpr int U = 4;
-    for (u64 b0 = 0; b0 < n_brackets; b0 += U * WAVE) {
-      u64 v[U], sum = 0;
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const u64 b = b0 + (u64) (U * lane + u);
-        v[u] = b < n_brackets ? cnt[b * NWAY_MAX + list] : 0u;
-      }
-#pragma unroll
-      for (int u = 0; u < U; u++) sum += v[u];
-      const u64 incl = wave_inclusive_scan (sum, lane);
-      u64 before = carry + incl - sum;
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const u64 b = b0 + (u64) (U * lane + u);
-        if (b < n_brackets) cnt[b * NWAY_MAX + list] = (u32) before;
-        before += v[u];
-      }
-      carry += (u64) (u32) __builtin_amdgcn_readlane ((int) (u32) incl, WAVE - 1) | ((u64) (u32) __builtin_amdgcn_readlane ((int) (u32) (incl >> 32), WAVE - 1) << 32);
-    }
-  }
+  for (int list = threadIdx.x >> 6; list < NWAY_MAX; list += 16) nway_bracket_prefix (cnt, n_brackets, list, threadIdx.x & 63); /* two lists per wavefront */
 }
 
 constexpr u32 NWAY_G_MAX = 64; /* samples per tile the bracket's LDS copy has room for */
@@ -76,27 +53,7 @@ __global__ __launch_bounds__ (64, 5) void k_nway_partition_rows (NwayParams p, c
   const u64 first = t * (u64) G, end = !tile || first >= m_total ? first : (first + G < m_total ? first + G : m_total);
   /* the tile's key range and bucket function (as k_nway_partition) */
   if (tile) {
-    u64 lo, hi;
-    if (t == 0) {
-      lo = ~0ull;
-      for (u32 j = 0; j < p.k; j++)
-        if (p.n[j]) {
-          const u64 f = load_key (p.list[j], 0);
-          lo = f < lo ? f : lo;
-        }
-    } else {
-      lo = x + 1ull;
-    }
-    if (t + 1 == nt) {
-      hi = 0;
-      for (u32 j = 0; j < p.k; j++)
-        if (p.n[j]) {
-          const u64 l = load_key (p.list[j], p.n[j] - 1);
-          hi = l > hi ? l : hi;
-        }
-    } else {
-      hi = y;
-    }
+    const u64 lo = t == 0 ? nway_first_key (p) : x + 1ull, hi = t + 1 == nt ? nway_last_key (p) : y;
     part[t * NWAY_PSTRIDE + NWAY_MAX] = lo;
     part[t * NWAY_PSTRIDE + NWAY_MAX + 1] = nway_bucket_consts (lo, hi, n_buckets);
   } else if (row) {
@@ -118,57 +75,10 @@ __global__ __launch_bounds__ (64, 5) void k_nway_partition_rows (NwayParams p, c
     c0 = wave_inclusive_scan (c0, lane) - c0; /* (every lane takes part) */
     c1 = wave_inclusive_scan (c1, lane) - c1;
     if (tile) {
-      u64 a[8], h[8];
-      bool need[8];
+      u64 a[8];
+      nway_cut_search8 (p, g0, t, x, x_list, bases + br * NWAY_MAX, c0, c1, a);
 #pragma unroll
-      for (int i = 0; i < 8; i++) {
-        const u32 li = g0 + (u32) i;
-        const u64 c = li < p.k && t > 0 ? (u64) bases[br * NWAY_MAX + li] + (((i < 4 ? c0 : c1) >> (16 * (i & 3))) & 0xffffu) : 0ull;
-        a[i] = h[i] = c * NWAY_SAMPLE;
-        need[i] = li < p.k && t > 0 && li != x_list;
-      }
-      for (int round = 0; round < 3; round++) {
-        u64 e[8], kk[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-          const u64 ni = p.n[g0 + i];
-          e[i] = a[i] + NWAY_SAMPLE < ni ? a[i] + NWAY_SAMPLE : ni;
-          kk[i] = need[i] && e[i] > a[i] ? load_key (p.list[g0 + i], e[i] - 1) : 0ull;
-        }
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-          if (!need[i]) continue;
-          if (e[i] == a[i]) {
-            h[i] = a[i];
-            need[i] = false;
-          } else if (kk[i] <= x) {
-            a[i] = h[i] = e[i];
-          } else {
-            h[i] = e[i] - 1;
-            need[i] = false;
-          }
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 8; i++)
-        if (need[i]) h[i] = p.n[g0 + i];
-      for (;;) {
-        bool any = false;
-        u64 km[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) km[i] = a[i] < h[i] ? load_key (p.list[g0 + i], (a[i] + h[i]) >> 1) : 0ull;
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-          if (a[i] >= h[i]) continue;
-          const u64 mid = (a[i] + h[i]) >> 1;
-          if (km[i] <= x) a[i] = mid + 1;
-          else h[i] = mid;
-          any |= a[i] < h[i];
-        }
-        if (!any) break;
-      }
-#pragma unroll
-      for (int i = 0; i < 8; i++) part[t * NWAY_PSTRIDE + g0 + i] = g0 + (u32) i < p.k && t > 0 ? a[i] : 0ull;
+      for (int i = 0; i < 8; i++) part[t * NWAY_PSTRIDE + g0 + i] = a[i];
     } else if (row) { /* t == num_tiles: the lists' ends */
       for (u32 i = 0; i < 8; i++) part[t * NWAY_PSTRIDE + g0 + i] = g0 + i < p.k ? p.n[g0 + i] : 0ull;
     }

@@ -20,28 +20,7 @@ __global__ __launch_bounds__ (256) void k_nway_sample_counts (const u32 *__restr
 
 __global__ __launch_bounds__ (64 * NWAY_MAX) void k_nway_bracket_bases (u32 *__restrict__ cnt, u64 n_brackets)
 {
-  const int lane = threadIdx.x & 63, list = threadIdx.x >> 6;
-  u64 carry = 0;
-  constexpr int U = 4; /* brackets per lane and round: the loads of a round are asked for together (one per lane and round was a memory round trip per 64 brackets: 0.18 ms for 2e4 brackets) */
-  for (u64 b0 = 0; b0 < n_brackets; b0 += U * WAVE) {
-    u64 v[U], sum = 0;
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      const u64 b = b0 + (u64) (U * lane + u);
-      v[u] = b < n_brackets ? cnt[b * NWAY_MAX + list] : 0u;
-    }
-#pragma unroll
-    for (int u = 0; u < U; u++) sum += v[u];
-    const u64 incl = wave_inclusive_scan (sum, lane);
-    u64 before = carry + incl - sum;
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      const u64 b = b0 + (u64) (U * lane + u);
-      if (b < n_brackets) cnt[b * NWAY_MAX + list] = (u32) before;
-      before += v[u];
-    }
-    carry += (u64) (u32) __builtin_amdgcn_readlane ((int) (u32) incl, WAVE - 1) | ((u64) (u32) __builtin_amdgcn_readlane ((int) (u32) (incl >> 32), WAVE - 1) << 32);
-  }
+  nway_bracket_prefix (cnt, n_brackets, threadIdx.x >> 6, threadIdx.x & 63); /* a wavefront per list */
 }
 
 constexpr u32 NWAY_G_MAX = 32; /* samples per tile the bracket's LDS copy has room for */
@@ -72,45 +51,15 @@ __global__ __launch_bounds__ (64) void k_nway_partition_rows (NwayParams p, cons
   const u32 x_list = has_x ? merged[3 * (t == nt - 1 ? m_total - 1 : t * (u64) G - 1) + 2] : 0xffffffffu;
   /* the tile's key range and bucket function (as k_nway_partition) */
   u64 lo_key = 0, bk = 0;
-  u32 sh = 0, mul = 0;
-  bool direct = false;
   const bool tile = row && t < nt;
   u64 c0 = 0, c1 = 0; /* the tile's own samples per list: 16-bit fields, lists 0..3 and 4..7 */
   if (tile) {
-    u64 lo, hi;
-    if (t == 0) {
-      lo = ~0ull;
-      for (u32 j = 0; j < p.k; j++)
-        if (p.n[j]) {
-          const u64 f = load_key (p.list[j], 0);
-          lo = f < lo ? f : lo;
-        }
-    } else {
-      lo = x + 1ull;
-    }
-    if (t + 1 == nt) {
-      hi = 0;
-      for (u32 j = 0; j < p.k; j++)
-        if (p.n[j]) {
-          const u64 l = load_key (p.list[j], p.n[j] - 1);
-          hi = l > hi ? l : hi;
-        }
-    } else {
-      hi = y;
-    }
-    const u64 D = hi >= lo ? hi - lo : 0ull;
-    const u32 bl = D ? 64u - (u32) __builtin_clzll (D) : 0u;
-    sh = bl > 32u ? bl - 32u : 0u;
-    const u32 vmax = (u32) (D >> sh);
-    direct = vmax < n_buckets;
-    mul = direct ? 0u : (u32) (((u64) n_buckets << 32) / ((u64) vmax + 1ull));
-    lo_key = lo;
-    bk = (u64) sh | (direct ? 1ull << 8 : (u64) mul << 32);
+    lo_key = t == 0 ? nway_first_key (p) : x + 1ull;
+    const u64 hi = t + 1 == nt ? nway_last_key (p) : y;
+    bk = nway_bucket_consts (lo_key, hi, n_buckets);
     /* the tile's own samples: counts per list, and whether the interpolation will work on them */
     const u64 first = t * (u64) G, end = first >= m_total ? first : (first + G < m_total ? first + G : m_total);
-    u32 prev = 0xffffffffu, same = 0, cnt = 0;
-    u64 prev_key = 0;
-    bool have_prev = false;
+    NwayClusterTest test (lo_key, hi, bk);
     for (u64 j0 = first; j0 < end; j0 += 8) { /* (eight samples asked for at once) */
       u64 sk[8];
       u32 sid[8];
@@ -123,76 +72,22 @@ __global__ __launch_bounds__ (64) void k_nway_partition_rows (NwayParams p, cons
 #pragma unroll
       for (int u = 0; u < 8; u++) {
         if (j0 + u >= end) continue;
-        const u64 s = sk[u];
         const u64 one = 1ull << (16 * (sid[u] & 3u));
         c0 += sid[u] < 4u ? one : 0ull;
         c1 += sid[u] < 4u ? 0ull : one;
-        if (s < lo || s > hi || (have_prev && s == prev_key)) continue; /* (equal keys of different lists share a bucket by right) */
-        prev_key = s;
-        have_prev = true;
-        const u32 vv = (u32) ((s - lo) >> sh);
-        const u32 b = direct ? vv : __umulhi (vv, mul);
-        same += b == prev ? 1u : 0u;
-        prev = b;
-        cnt++;
+        test.add (sk[u]);
       }
     }
-    if (t + 1 < nt && cnt >= 8 && 2 * same > cnt) bk |= 1ull << 9;
+    if (t + 1 < nt && test.clustered ()) bk |= 1ull << 9;
   }
   /* samples in front of the tile = the bracket's base + the earlier lanes' (every lane takes part) */
   c0 = wave_inclusive_scan (c0, lane) - c0;
   c1 = wave_inclusive_scan (c1, lane) - c1;
   if (tile) {
-    /* the eight searches in step: every round asks for one key of every list */
-    u64 a[NWAY_MAX], h[NWAY_MAX];
-    bool need[NWAY_MAX]; /* the stretch that holds the cut is not found yet */
+    u64 a[8];
+    nway_cut_search8 (p, 0, t, x, x_list, bases + br * NWAY_MAX, c0, c1, a);
 #pragma unroll
-    for (int i = 0; i < NWAY_MAX; i++) {
-      const u64 c = (u32) i < p.k && t > 0 ? (u64) bases[br * NWAY_MAX + i] + (((i < 4 ? c0 : c1) >> (16 * (i & 3))) & 0xffffu) : 0ull;
-      a[i] = h[i] = c * NWAY_SAMPLE;
-      need[i] = (u32) i < p.k && t > 0 && (u32) i != x_list; /* (c counts the boundary sample itself: c * S is one behind it) */
-    }
-    for (int round = 0; round < 3; round++) { /* (a sample equal to the boundary key merged behind it: one stretch further; the list's tail: one more) */
-      u64 e[NWAY_MAX], kk[NWAY_MAX];
-#pragma unroll
-      for (int i = 0; i < NWAY_MAX; i++) {
-        e[i] = a[i] + NWAY_SAMPLE < p.n[i] ? a[i] + NWAY_SAMPLE : p.n[i];
-        kk[i] = need[i] && e[i] > a[i] ? load_key (p.list[i], e[i] - 1) : 0ull;
-      }
-#pragma unroll
-      for (int i = 0; i < NWAY_MAX; i++) {
-        if (!need[i]) continue;
-        if (e[i] == a[i]) { /* the list ends here */
-          h[i] = a[i];
-          need[i] = false;
-        } else if (kk[i] <= x) { /* the whole stretch belongs to earlier tiles */
-          a[i] = h[i] = e[i];
-        } else {
-          h[i] = e[i] - 1;
-          need[i] = false;
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NWAY_MAX; i++)
-      if (need[i]) h[i] = p.n[i]; /* (cannot happen: keys are unique inside a list; searched in full all the same) */
-    for (;;) {
-      bool any = false;
-      u64 km[NWAY_MAX];
-#pragma unroll
-      for (int i = 0; i < NWAY_MAX; i++) km[i] = a[i] < h[i] ? load_key (p.list[i], (a[i] + h[i]) >> 1) : 0ull;
-#pragma unroll
-      for (int i = 0; i < NWAY_MAX; i++) {
-        if (a[i] >= h[i]) continue;
-        const u64 mid = (a[i] + h[i]) >> 1;
-        if (km[i] <= x) a[i] = mid + 1;
-        else h[i] = mid;
-        any |= a[i] < h[i];
-      }
-      if (!any) break;
-    }
-#pragma unroll
-    for (int i = 0; i < NWAY_MAX; i++) part[t * NWAY_PSTRIDE + i] = (u32) i < p.k && t > 0 ? a[i] : 0ull;
+    for (int i = 0; i < NWAY_MAX; i++) part[t * NWAY_PSTRIDE + i] = a[i];
     part[t * NWAY_PSTRIDE + NWAY_MAX] = lo_key;
     part[t * NWAY_PSTRIDE + NWAY_MAX + 1] = bk;
   } else if (row) { /* t == num_tiles: the lists' ends */

@@ -228,7 +228,7 @@ __global__ __launch_bounds__ (MM_THREADS) void k_index_split (const u64 *__restr
 /* k_tile_scan of 64-bit counts: the locations of a tile's hits do not fit 32 bits */
 __global__ __launch_bounds__ (1024) void k_tile_scan64 (const u64 *tile_cnt, u64 n_tiles, u64 *tile_off, unsigned long long *total)
 {
-  tile_scan (tile_cnt, n_tiles, tile_off, total);
+  workgroup_scan<1> ({tile_cnt}, {tile_off}, n_tiles, total);
 }
 
 /* how a packed location comes apart (index_map_get_location, src/index-map.c:197-208) */

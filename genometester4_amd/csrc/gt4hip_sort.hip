@@ -570,25 +570,7 @@ __global__ __launch_bounds__ (INDEX_NT) void k_index_sums (const u32 *__restrict
 /* exclusive scan of both tile sums in place (one workgroup); total[0] = words kept, total[1] = their occurrences */
 __global__ __launch_bounds__ (1024) void k_index_scan (u64 *__restrict__ tile_kept, u64 *__restrict__ tile_locs, u64 tiles, unsigned long long *__restrict__ total)
 {
-  __shared__ u64 wa[1024 / WAVE], wb[1024 / WAVE];
-  __shared__ u64 carry[2];
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-  if (threadIdx.x == 0) carry[0] = carry[1] = 0;
-  __syncthreads ();
-  for (u64 base = 0; base < tiles; base += 1024) {
-    const u64 i = base + threadIdx.x;
-    const u64 a = i < tiles ? tile_kept[i] : 0, b = i < tiles ? tile_locs[i] : 0;
-    const u64 ai = wave_inclusive_scan (a, lane), bi = wave_inclusive_scan (b, lane);
-    if (lane == WAVE - 1) wa[wv] = ai, wb[wv] = bi;
-    __syncthreads ();
-    u64 ab = carry[0], bb = carry[1];
-    for (int w = 0; w < wv; w++) ab += wa[w], bb += wb[w];
-    if (i < tiles) tile_kept[i] = ab + ai - a, tile_locs[i] = bb + bi - b;
-    __syncthreads ();
-    if (threadIdx.x == 1023) carry[0] = ab + ai, carry[1] = bb + bi;
-    __syncthreads ();
-  }
-  if (threadIdx.x == 0) total[0] = carry[0], total[1] = carry[1];
+  workgroup_scan<2> ({tile_kept, tile_locs}, {tile_kept, tile_locs}, tiles, total);
 }
 
 /* kmers[2 j], kmers[2 j + 1] = the j-th kept word and the occurrences of the kept words in front of it */

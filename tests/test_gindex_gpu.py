@@ -133,6 +133,32 @@ def test_fold_with_the_cut_offs(ctx, folded_input, lo, hi):
     assert locs.tolist() == exp_locs.tolist()
 
 
+@pytest.fixture(scope="module")
+def two_million_words():
+    """2 x 1024 x 1024 + 5 distinct words with one or two occurrences each: 2049 tiles of the index kernels, so the scan of
+    the tiles' sums (k_index_scan: one workgroup, rounds of 1024 tiles) carries both sums over two rounds into a third of
+    one tile"""
+    rng = np.random.default_rng(2049)
+    n = 2 * 1024 * 1024 + 5
+    keys = rng.permutation(np.unique(rng.integers(0, 1 << 50, size=n + n // 4, dtype=np.uint64)))[:n]
+    assert len(keys) == n
+    words = np.concatenate([keys, keys[rng.random(n) < 0.5]])
+    return words[rng.permutation(len(words))], np.arange(len(words), dtype=np.uint64)
+
+
+@pytest.mark.parametrize("lo", [1, 2])
+def test_fold_of_more_tiles_than_two_rounds_of_the_scan(ctx, two_million_words, lo):
+    words, values = two_million_words
+    w, v = on_device(words), on_device(values)
+    kmers, n_locations, locs = ctx.pairs_to_index(w.data_ptr(), v.data_ptr(), len(words), 25, lo)
+    exp_kmers, exp_n, exp_locs = IM.sections(words, values, lo)
+    exp_kmers = np.array(exp_kmers, dtype=np.uint64).reshape(-1, 2)
+    assert len(exp_kmers) > 1024 * 1024 // 2 and kmers.shape == exp_kmers.shape
+    assert (kmers == exp_kmers).all()
+    assert n_locations == exp_n
+    assert (locs == exp_locs).all()
+
+
 @pytest.mark.parametrize("case", GOLDEN["cases"], ids=[c["id"] for c in GOLDEN["cases"]])
 def test_table_step_gives_the_reference_s_sections(ctx, case):
     """the reference's own `glistmaker --index` files: the words and packed locations of the texts (tests/index_model.py, in

@@ -141,6 +141,35 @@ def test_lookup_all_hits_and_order(ctx, iid25):
     ix.free()
 
 
+def test_lookup_all_of_more_tiles_than_two_rounds_of_the_scan(ctx):
+    """The scan of the tiles' hit counts (k_tile_scan: one workgroup, rounds of 1024 tiles with the sum so far carried
+    from round to round): a batch of 2 x 1024 x 2048 + 3 words is 2049 tiles of 2048 words -- two full rounds and a
+    third of one tile.  Exact lookups against a list of a few thousand words; about half of the queries hit."""
+    rng = np.random.default_rng(2049)
+    k = 16
+    keys = np.unique(M.canonical_np(rng.integers(0, 1 << 32, size=5000, dtype=np.uint64), k))
+    counts = rng.integers(1, 200, size=len(keys), dtype=np.uint32)
+    n = 2 * 1024 * 2048 + 3
+    words = rng.integers(0, 1 << 32, size=n, dtype=np.uint64)
+    take = rng.random(n) < 0.5
+    words[take] = keys[rng.integers(0, len(keys), size=int(take.sum()))]
+    words[[0, n - 1]] = keys[[1, 2]]
+    lst = ctx.upload(make_records(keys, counts), k)
+    ix = lst.query_index()
+    try:
+        hits = ix.lookup_all(words, 0, 0, capacity=n)
+    finally:
+        ix.free()
+        lst.free()
+    val, found = M.lookup_np(keys, counts, words, k, 0, 0)
+    at = np.flatnonzero(found)
+    assert len(at) > n // 4 and len(hits) == len(at)
+    assert (hits["query"] == at.astype(np.uint64)).all()
+    assert (hits["rank"] == 0).all()
+    assert (hits["word"] == M.canonical_np(words[at], k)).all()
+    assert (hits["count"] == val[at]).all()
+
+
 def test_k32_extreme_keys(ctx):
     rng = np.random.default_rng(32)
     k = 32

@@ -214,6 +214,27 @@ def test_tiles_that_do_not_fit_are_cut_in_two(ctx, g):
         ctx.set_option("kway_g", 0)
 
 
+def test_tiles_of_the_thirty_two_list_instance_are_cut_in_two(ctx):
+    """The same for twelve lists in the 32-list instance (option kway_max = 33; its k_nway_need takes half a wavefront
+    per tile, its k_nway_emit rows of 34 entries).  There a sample stands for 64 records and a tile has 4096 positions,
+    so kway_g = 64 samples per tile fills a tile on average and about half of them are cut (259 tiles of these lists, before
+    the partition's rules were written once and after; neither retried with fewer samples)."""
+    rng = np.random.default_rng(12)
+    lists = _random_lists(rng, 12, 400000, zero_counts=False)
+    ctx.set_option("kway_max", 33)
+    ctx.set_option("kway_g", 64)
+    try:
+        before = ctx.get_counter("kway_overflows")
+        _check(ctx, lists, k=20)
+        assert ctx.get_counter("kway_width") == 32
+        assert ctx.get_counter("kway_splits") > 0
+        _check(ctx, lists, k=20, rule=4, cutoff=2)
+        assert ctx.get_counter("kway_overflows") == before
+    finally:
+        ctx.set_option("kway_g", 0)
+        ctx.set_option("kway_max", 32)
+
+
 def test_default_setting_hands_clustered_keys_to_the_tree(ctx):
     """Option kway = 1 (the default): a probe of the longest list's keys sees stretches of adjacent keys between
     wide gaps and the call takes the pairwise tree -- same bytes, counter kway_declined; evenly spread keys of the
@@ -465,17 +486,23 @@ def test_count_table_of_clustered_keys(ctx):
             ctx.set_option("kway_vt", 0)
 
 
-@pytest.mark.parametrize("n_lists", [3, 8])
+@pytest.mark.parametrize("n_lists", [3, 8, 12])
 def test_partition_by_bracket_searches_gives_the_same_tiles_result(ctx, n_lists):
     """The tile boundaries come from the merged samples' list numbers (prefix counts + a search inside
     one sample stretch); option kway_vt = 97 keeps the older partition (binary searches over brackets of
     64 tiles).  Both against the oracle, on lists with many equal keys (ties at the boundaries: a sample
-    equal to the boundary key merged behind it)."""
+    equal to the boundary key merged behind it).  Twelve lists with option kway_max = 33: both partitions of
+    the 32-list instance."""
     rng = np.random.default_rng(97 + n_lists)
     lists = _random_lists(rng, n_lists, 400000, k_bits=19)  # dense: most keys are in several lists
-    _check(ctx, lists, rule=1, cutoff=2)
-    ctx.set_option("kway_vt", 97)
+    if n_lists > 8:
+        ctx.set_option("kway_max", 33)
     try:
         _check(ctx, lists, rule=1, cutoff=2)
+        ctx.set_option("kway_vt", 97)
+        _check(ctx, lists, rule=1, cutoff=2)
+        if n_lists > 8:
+            assert ctx.get_counter("kway_width") == 32
     finally:
         ctx.set_option("kway_vt", 0)
+        ctx.set_option("kway_max", 32)
