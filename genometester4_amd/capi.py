@@ -70,6 +70,12 @@ class GmerStats(C.Structure):
                 ("n_kmer_gc", C.c_uint64)]
 
 
+class CallerModel(C.Structure):
+    """gt4hip_caller_model: the seven parameters of gmer_caller's model and the B allele frequency, as floats"""
+    _fields_ = [("l_viga", C.c_float), ("p_0", C.c_float), ("p_1", C.c_float), ("p_2", C.c_float), ("lam", C.c_float),
+                ("size", C.c_float), ("size2", C.c_float), ("pB", C.c_float)]
+
+
 class Subseq(C.Structure):
     _fields_ = [("name_pos", C.c_uint64), ("name_len", C.c_uint64), ("seq_pos", C.c_uint64), ("seq_len", C.c_uint64)]
 
@@ -134,6 +140,8 @@ SYMBOLS = [
     "gt4hip_gmer_count_text", "gt4hip_gmer_counts_download", "gt4hip_gmer_counts_reset",
     "gt4hip_select_multi", "gt4hip_table_select",
     "gt4hip_table_pairwise", "gt4hip_pairwise_multi",
+    "gt4hip_caller_set_create", "gt4hip_caller_set_free", "gt4hip_caller_set_n", "gt4hip_caller_set_last_ms", "gt4hip_caller_mlogl",
+    "gt4hip_caller_probabilities",
 ]
 
 _lib = None
@@ -259,6 +267,12 @@ def lib():
             "gt4hip_table_select": (C.c_int, [vp, C.POINTER(CountTable), u32, u32, u32, i32, u32, i32, C.POINTER(MultiResult)]),
             "gt4hip_table_pairwise": (C.c_int, [vp, C.POINTER(CountTable), vp, vp, C.POINTER(C.c_float)]),
             "gt4hip_pairwise_multi": (C.c_int, [vp, C.POINTER(vp), u32, vp, vp, C.POINTER(C.c_float)]),
+            "gt4hip_caller_set_create": (C.c_int, [vp, vp, vp, u64, C.POINTER(vp)]),
+            "gt4hip_caller_set_free": (None, [vp]),
+            "gt4hip_caller_set_n": (u64, [vp]),
+            "gt4hip_caller_set_last_ms": (C.c_double, [vp]),
+            "gt4hip_caller_mlogl": (C.c_int, [vp, vp, u64, u64, C.POINTER(CallerModel), C.POINTER(C.c_double)]),
+            "gt4hip_caller_probabilities": (C.c_int, [vp, vp, u64, u64, C.POINTER(CallerModel), vp, vp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -562,6 +576,47 @@ class GmerDb:
             self.h = None
 
 
+class CallerSet:
+    """The count pairs of a run's markers resident on the device (gt4hip_caller_set)."""
+
+    def __init__(self, ctx: "Context", a_counts, b_counts):
+        a, b = np.ascontiguousarray(a_counts, dtype=np.uint32), np.ascontiguousarray(b_counts, dtype=np.uint32)
+        if a.shape != b.shape or a.ndim != 1:
+            raise ValueError("two count columns of one length")
+        self.ctx, self.h = ctx, C.c_void_p()
+        ctx._chk(lib().gt4hip_caller_set_create(ctx.h, a.ctypes.data if len(a) else None, b.ctypes.data if len(b) else None, len(a), C.byref(self.h)))
+        ctx._lists.add(self)
+
+    @property
+    def n(self):
+        return lib().gt4hip_caller_set_n(self.h)
+
+    def mlogl(self, model: "CallerModel", first=0, n=None) -> float:
+        """-(sum of log (max (sum of the 15 likelihoods, 1e-30))) over markers [first, first + n) (gt4hip_caller_mlogl)"""
+        n = self.n - first if n is None else n
+        out = C.c_double()
+        self.ctx._chk(lib().gt4hip_caller_mlogl(self.ctx.h, self.h, first, n, C.byref(model), C.byref(out)))
+        return out.value
+
+    def probabilities(self, model: "CallerModel", first=0, n=None, all15=False):
+        """(best index, its likelihood, the sum, all 15 or None) per marker of [first, first + n) (gt4hip_caller_probabilities)"""
+        n = self.n - first if n is None else n
+        best, a_best, a_sum = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.float64), np.empty(n, dtype=np.float64)
+        a_all = np.empty((n, 15), dtype=np.float64) if all15 else None
+        self.ctx._chk(lib().gt4hip_caller_probabilities(self.ctx.h, self.h, first, n, C.byref(model), best.ctypes.data if n else None,
+                                                         a_best.ctypes.data if n else None, a_sum.ctypes.data if n else None,
+                                                         a_all.ctypes.data if all15 else None))
+        return best, a_best, a_sum, a_all
+
+    def last_ms(self):
+        return lib().gt4hip_caller_set_last_ms(self.h)
+
+    def free(self):
+        if self.h:
+            lib().gt4hip_caller_set_free(self.h)
+            self.h = None
+
+
 class DeviceTable:
     """Owning handle of a gt4hip_count_table of gt4hip_union_table that stays on the device."""
 
@@ -657,6 +712,10 @@ class Context:
     def gmer_db(self, words, word_length) -> "GmerDb":
         """Database k-mers (one word each, either strand) -> a device db with a counter per k-mer (gt4hip_gmer_db_create)."""
         return GmerDb(self, words, word_length)
+
+    def caller_set(self, a_counts, b_counts) -> "CallerSet":
+        """The two count columns of a marker table -> a set resident on the device (gt4hip_caller_set_create)."""
+        return CallerSet(self, a_counts, b_counts)
 
     def words_to_list(self, words, word_length) -> "DeviceList":
         """Packed k-mer words (any order, repeats) -> sorted (word, occurrences) list on the device."""

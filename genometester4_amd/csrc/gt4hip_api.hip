@@ -121,7 +121,7 @@ extern "C" void gt4hip_destroy (gt4hip_context *ctx)
     pool_flush (ctx);
     delete ctx->pool;
   }
-  void *const dev[] = { ctx->part, ctx->kway_part, ctx->kway_cnt, ctx->kway_part2, ctx->kway_need, ctx->desc, ctx->block_sums, ctx->ctl, ctx->scratch };
+  void *const dev[] = { ctx->part, ctx->kway_part, ctx->kway_cnt, ctx->kway_part2, ctx->kway_need, ctx->desc, ctx->block_sums, ctx->ctl, ctx->scratch, ctx->caller_tab };
   for (void *p : dev)
     if (p) hipFree (p);
   if (ctx->ctl_host) hipHostFree (ctx->ctl_host);

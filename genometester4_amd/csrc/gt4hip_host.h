@@ -85,6 +85,7 @@ struct gt4hip_context {
   double subset_ms;             /* counter "subset_us": its kernels (HIP events) */
   int select_vec;               /* option "select_vec": gt4hip_table_select reads rows of a multiple of four counts 16 bytes per lane (0) / every row a dword per lane (-1) */
   uint64_t select_wide;         /* counter "select_wide": the last gt4hip_table_select read 16 bytes per lane */
+  void *caller_tab;             /* gt4hip_caller.hip: the log-factorial table, the workgroups' partial sums and their ticket; NULL until a set is made */
   char err[512];
   char info[256];
 };

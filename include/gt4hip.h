@@ -692,6 +692,46 @@ int gt4hip_gmer_count_text (gt4hip_context *ctx, gt4hip_gmer_db *db, const void 
 int gt4hip_gmer_counts_download (gt4hip_context *ctx, const gt4hip_gmer_db *db, uint64_t first, uint64_t n, uint64_t *host_counts);
 int gt4hip_gmer_counts_reset (gt4hip_context *ctx, gt4hip_gmer_db *db);
 
+/* ---------------------------------------------------------------- gmer_caller: genotype likelihoods of k-mer count pairs */
+
+/* The model of genotype_probabilities (reference src/genotypes.c:9-124), as gmer_caller holds it: seven `float`
+ * parameters and the B allele frequency.  They are promoted to double where C promotes them in the reference. */
+typedef struct {
+  float l_viga;  /* mean count of a k-mer that is not in the genome (errors)   */
+  float p_0, p_1, p_2;  /* probability of 0, 1, 2 copies                        */
+  float lambda;  /* mean count of a k-mer of two copies (the coverage)          */
+  float size, size2;  /* negative-binomial size = size + size2 x mean           */
+  float pB;      /* frequency of the B allele                                   */
+} gt4hip_caller_model;
+#define GT4HIP_CALLER_GENOTYPES 15u  /* -, A, B, AA, AB, BB, AAA, AAB, BBA, BBB, AAAA, AAAB, BBBA, AABB, BBBB */
+
+/* The markers of a run resident in HBM: n pairs (a_counts[i], b_counts[i]), uploaded once; every call below reads them
+ * there.  Free the set before its context. */
+typedef struct gt4hip_caller_set gt4hip_caller_set;
+int gt4hip_caller_set_create (gt4hip_context *ctx, const uint32_t *a_counts, const uint32_t *b_counts, uint64_t n, gt4hip_caller_set **set);
+void gt4hip_caller_set_free (gt4hip_caller_set *set);
+uint64_t gt4hip_caller_set_n (const gt4hip_caller_set *set);
+/* Device time (HIP events) of the kernel of the last gt4hip_caller_mlogl / of the kernels of the last
+ * gt4hip_caller_probabilities on this set, copies excluded. */
+double gt4hip_caller_set_last_ms (const gt4hip_caller_set *set);
+
+/* mlogL3 (src/gmer_caller.c:821-843) over markers [first, first + n): *sum = -(sum over the markers of
+ * log (max (a[0] + ... + a[14], 1e-30))), a[] the 15 likelihoods of the marker under `m`.  What depends on the model alone
+ * (the 15 priors, and per mean the size, p, log p, size x log (1 - p), lgamma (size) and the "size <= 0 or mean <= 0 gives
+ * 0" verdict) is computed by the call on the host with libm; per marker the device computes ten negative-binomial terms
+ * and the 15 products q0 * q1 * p[j].  One launch and one read-back of 8 bytes.  The sum is reproducible bit for bit: the
+ * grid depends on n alone, a thread adds its markers in ascending order, a workgroup adds its threads by a fixed tree, and
+ * the workgroup that finishes last adds the workgroups' sums in index order by the same tree; no floating-point atomics.
+ * n = 0 gives -0.0, as the reference's loop does. */
+int gt4hip_caller_mlogl (gt4hip_context *ctx, gt4hip_caller_set *set, uint64_t first, uint64_t n, const gt4hip_caller_model *m, double *sum);
+
+/* calc_run (src/gmer_caller.c:365-388) over markers [first, first + n), into HOST arrays of n entries: best[i] = the index
+ * of the largest likelihood (the first of equals: a strict > scan from 0, so 0 where all are NaN), a_best[i] that
+ * likelihood, a_sum[i] = a[0] + ... + a[14] in that order, and where a_all is not NULL a_all[15 i + j] = a[j].  Large n
+ * goes through the device in pieces sized to what the context's pool gives. */
+int gt4hip_caller_probabilities (gt4hip_context *ctx, gt4hip_caller_set *set, uint64_t first, uint64_t n, const gt4hip_caller_model *m,
+                                 uint8_t *best, double *a_best, double *a_sum, double *a_all);
+
 /* ---------------------------------------------------------------- synthetic lists (bench) */
 
 /* Fills `list` (capacity >= n) with n strictly ascending keys < 4^word_length and counts in

@@ -14,7 +14,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-amdg
 
 
 PER_SOURCE = {"gt4hip_kernels.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],      # = csrc/Makefile's KERNELS_SCHED
-              "gt4hip_nway.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"]}      # ... NWAY_SCHED
+              "gt4hip_nway.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"],      # ... NWAY_SCHED
+              "gt4hip_caller.hip": ["-mllvm", "-disable-machine-licm"]}                      # ... CALLER_LICM
 
 
 def table(source="gt4hip_kernels.hip", extra=()):
