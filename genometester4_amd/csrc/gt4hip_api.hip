@@ -177,6 +177,9 @@ extern "C" int gt4hip_set_option (gt4hip_context *ctx, const char *name, int64_t
   else if (!strcmp (name, "a_rows")) ctx->a_rows = (int) value;
   else if (!strcmp (name, "part_guided")) ctx->part_guided = (int) value;
   else if (!strcmp (name, "select_vec")) ctx->select_vec = (int) value;
+  else if (!strcmp (name, "grid_cap")) ctx->grid_limit.cap = value > 0 ? value : 0;
+  else if (!strcmp (name, "poison")) ctx->poison = value != 0;
+  else if (!strcmp (name, "caller_piece")) ctx->caller_piece = value > 0 ? (uint64_t) value : 0;
   else if (!strcmp (name, "kway")) ctx->kway_enabled = (int) value;
   else if (!strcmp (name, "kway_max")) ctx->kway_max = value == 8 ? 8 : (value == 33 ? 33 : 32);
   else if (!strcmp (name, "kway_g")) ctx->kway_g = value;
@@ -212,8 +215,20 @@ extern "C" int gt4hip_get_counter (gt4hip_context *ctx, const char *name, uint64
   else if (!strcmp (name, "mm_unskipped_levels")) *value = ctx->mm_unskipped_levels;
   else if (!strcmp (name, "subset_passes")) *value = ctx->subset_passes;
   else if (!strcmp (name, "subset_tile")) *value = GT4HIP_SUBSET_TILE;
+  else if (!strcmp (name, "subset_scan_tile")) *value = 256u * GT4HIP_SUBSET_SCAN_V;
+  else if (!strcmp (name, "pack_threads")) *value = GT4HIP_PACK_THREADS;
   else if (!strcmp (name, "subset_us")) *value = (uint64_t) (ctx->subset_ms * 1000.0);
   else if (!strcmp (name, "select_wide")) *value = ctx->select_wide;
+  else if (!strcmp (name, "select_segment")) *value = GT4HIP_SELECT_SEGMENT;
+  else if (!strcmp (name, "grid_capped")) *value = ctx->grid_limit.capped;
+  else if (!strcmp (name, "mm_threads")) *value = GT4HIP_MM_THREADS;
+  else if (!strcmp (name, "mm_tile")) *value = (uint64_t) GT4HIP_MM_THREADS * GT4HIP_MM_ROUNDS;
+  else if (!strcmp (name, "gather_tile")) *value = (uint64_t) GT4HIP_MM_THREADS * GT4HIP_GATHER_ROUNDS;
+  else if (!strcmp (name, "hist_lds_bins")) *value = GT4HIP_HIST_LDS_BINS;
+  else if (!strcmp (name, "list_threads")) *value = GT4HIP_LIST_THREADS;
+  else if (!strcmp (name, "caller_threads")) *value = GT4HIP_CALLER_THREADS;
+  else if (!strcmp (name, "caller_max_grid")) *value = GT4HIP_CALLER_MAX_GRID;
+  else if (!strcmp (name, "sort_hist_chunk")) *value = (uint64_t) GT4HIP_SORT_HIST_THREADS * GT4HIP_SORT_HIST_ITEMS;
   else return gt4hip_fail (ctx, GT4HIP_EINVAL, "unknown counter %s", name);
   return GT4HIP_OK;
 }
@@ -235,6 +250,15 @@ static void pool_flush (gt4hip_context *ctx)
   ctx->pool_bytes = 0;
 }
 
+/* Option "poison" (tests): a block as it is handed out holds 0xA5 bytes, not what the call before left there -- as likely as
+ * not the results this call is to compute, which would then pass for them where a kernel skips an item.  Waited for: the
+ * staging threads of gt4hip_io.hip copy on streams of their own. */
+static void poison (gt4hip_context *ctx, void *p, size_t bytes)
+{
+  if (!ctx->poison || !bytes) return;
+  if (hipMemsetAsync (p, 0xA5, bytes, ctx->stream) != hipSuccess || hipStreamSynchronize (ctx->stream) != hipSuccess) (void) hipGetLastError ();
+}
+
 /* Every device allocation of the library goes through here: when the driver is out of memory the
  * pooled blocks (freed list storage kept for reuse) are given back and the allocation is retried. */
 hipError_t gt4hip_dev_alloc (gt4hip_context *ctx, void **p, size_t bytes)
@@ -246,6 +270,7 @@ hipError_t gt4hip_dev_alloc (gt4hip_context *ctx, void **p, size_t bytes)
     e = hipMalloc (p, bytes);
   }
   if (e != hipSuccess) (void) hipGetLastError ();
+  else poison (ctx, *p, bytes);
   return e;
 }
 
@@ -278,6 +303,7 @@ int gt4hip_list_new (gt4hip_context *ctx, uint64_t capacity, uint32_t word_lengt
       l->bytes = best;
       ctx->pool_bytes -= best;
       ctx->pool->erase (ctx->pool->begin () + (long) best_i);
+      poison (ctx, l->dev, l->bytes);
     }
   }
   if (!l->dev) {
@@ -334,7 +360,7 @@ extern "C" int gt4hip_list_upload_index (gt4hip_context *ctx, const void *host_k
       return gt4hip_fail (ctx, GT4HIP_ENOMEM, "hipMalloc of %llu bytes for the index table failed", (unsigned long long) n_words * 16);
     }
     e = hipMemcpyAsync (tmp, host_kmers, (size_t) n_words * 16, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = launch_decode_index (ctx->stream, (const unsigned long long *) tmp, n_words, num_locations, (uint32_t *) l->dev);
+    if (e == hipSuccess) e = launch_decode_index (ctx->stream, ctx->grid_limit, (const unsigned long long *) tmp, n_words, num_locations, (uint32_t *) l->dev);
     if (e == hipSuccess) e = hipStreamSynchronize (ctx->stream);
     hipFree (tmp);
     if (e != hipSuccess) {
@@ -447,7 +473,7 @@ extern "C" int gt4hip_list_sum_counts (gt4hip_context *ctx, const gt4hip_list *l
   if (!ctx || !l || !sum) return GT4HIP_EINVAL;
   HIPCHK (ctx, hipSetDevice (ctx->device));
   HIPCHK (ctx, hipMemsetAsync (ctx->scratch, 0, 64, ctx->stream));
-  if (l->n_words) HIPCHK (ctx, launch_sum_counts (ctx->stream, (const uint32_t *) l->dev, l->n_words, ctx->scratch));
+  if (l->n_words) HIPCHK (ctx, launch_sum_counts (ctx->stream, ctx->grid_limit, (const uint32_t *) l->dev, l->n_words, ctx->scratch));
   int rc = gt4hip_read_scratch (ctx, 1);
   if (rc) return rc;
   *sum = ctx->scratch_host[0];
@@ -459,7 +485,7 @@ extern "C" int gt4hip_list_is_sorted (gt4hip_context *ctx, const gt4hip_list *l,
   if (!ctx || !l || !sorted) return GT4HIP_EINVAL;
   HIPCHK (ctx, hipSetDevice (ctx->device));
   HIPCHK (ctx, hipMemsetAsync (ctx->scratch, 0, 64, ctx->stream));
-  if (l->n_words > 1) HIPCHK (ctx, launch_check_sorted (ctx->stream, (const uint32_t *) l->dev, l->n_words, (unsigned int *) ctx->scratch));
+  if (l->n_words > 1) HIPCHK (ctx, launch_check_sorted (ctx->stream, ctx->grid_limit, (const uint32_t *) l->dev, l->n_words, (unsigned int *) ctx->scratch));
   int rc = gt4hip_read_scratch (ctx, 1);
   if (rc) return rc;
   *sorted = (ctx->scratch_host[0] & 0xffffffffu) == 0;
@@ -506,7 +532,7 @@ extern "C" int gt4hip_generate_ex (gt4hip_context *ctx, gt4hip_list *l, uint64_t
   if (st > 0xffffffffffffffffull) st = 0xffffffffffffffffull;
   const uint64_t stride = (uint64_t) st;
   if (!stride) return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_generate: %llu keys do not fit k=%u", (unsigned long long) n, l->word_length);
-  HIPCHK (ctx, launch_generate (ctx->stream, (uint32_t *) l->dev, n, stride, key_seed, count_seed, max_count, mult, add));
+  HIPCHK (ctx, launch_generate (ctx->stream, ctx->grid_limit, (uint32_t *) l->dev, n, stride, key_seed, count_seed, max_count, mult, add));
   HIPCHK (ctx, hipStreamSynchronize (ctx->stream));
   return GT4HIP_OK;
 }

@@ -31,6 +31,7 @@ namespace {
 
 constexpr int CL_THREADS = 256;
 constexpr int CL_MAX_GRID = 1024;      /* workgroups of k_caller_mlogl at most: their sums are added by one workgroup */
+static_assert (CL_THREADS == GT4HIP_CALLER_THREADS && CL_MAX_GRID == GT4HIP_CALLER_MAX_GRID, "counters \"caller_threads\" and \"caller_max_grid\" (gt4hip_host.h)");
 constexpr u32 CL_MAX_PROD = 16384;     /* entries of the log-factorial table (MAX_PROD, src/binomial.c:11) */
 constexpr int CL_MEANS = 5;
 constexpr int CL_GENOTYPES = (int) GT4HIP_CALLER_GENOTYPES;
@@ -388,7 +389,8 @@ extern "C" int gt4hip_caller_probabilities (gt4hip_context *ctx, gt4hip_caller_s
   model_args (m, &g);
   /* a piece: its results in one block -- sums, best likelihoods, on request all 15, the indices last */
   const size_t per = 8 + 8 + (a_all ? 8 * (size_t) CL_GENOTYPES : 0) + 1;
-  u64 piece = n < (a_all ? 1ull << 20 : 1ull << 22) ? n : (a_all ? 1ull << 20 : 1ull << 22);
+  const u64 piece_max = ctx->caller_piece ? ctx->caller_piece : a_all ? 1ull << 20 : 1ull << 22;
+  u64 piece = n < piece_max ? n : piece_max;
   TempBlocks blk;
   char *d = NULL;
   for (;;) {

@@ -85,6 +85,9 @@ struct gt4hip_context {
   double subset_ms;             /* counter "subset_us": its kernels (HIP events) */
   int select_vec;               /* option "select_vec": gt4hip_table_select reads rows of a multiple of four counts 16 bytes per lane (0) / every row a dword per lane (-1) */
   uint64_t select_wide;         /* counter "select_wide": the last gt4hip_table_select read 16 bytes per lane */
+  gt4::GridLimit grid_limit;    /* option "grid_cap" (tests): workgroups at most of every kernel that strides over its work, 0 = the built-in caps alone; counter "grid_capped": launches whose grid had fewer workgroups than blocks of work */
+  int poison;                   /* option "poison" (tests): every device block handed out, new or from the pool, is filled with 0xA5 bytes first */
+  uint64_t caller_piece;        /* option "caller_piece" (tests): markers per piece of gt4hip_caller_probabilities, 0 = 2^22, with all 15 likelihoods 2^20 */
   void *caller_tab;             /* gt4hip_caller.hip: the log-factorial table, the workgroups' partial sums and their ticket; NULL until a set is made */
   char err[512];
   char info[256];
@@ -171,14 +174,14 @@ struct GT4HIP_LOCAL TempBlocks {
   }
 };
 
-/* workgroups of a kernel that strides over `blocks` blocks of work: one each, at most eight per compute unit, at least one */
-inline int gt4hip_grid (const gt4hip_context *ctx, uint64_t blocks)
-{
-  const uint64_t cap = (uint64_t) (ctx->n_cus > 0 ? ctx->n_cus : 256) * 8;
-  return (int) (blocks < 1 ? 1 : blocks < cap ? blocks : cap);
-}
+/* workgroups of a kernel that strides over `blocks` blocks of work: one each, at most eight per compute unit and at most
+ * option "grid_cap", at least one (gt4::strided_grid, which also keeps counter "grid_capped").  Only for kernels whose
+ * workgroups never wait for one another: under "grid_cap" = 1 a single workgroup does all the work. */
+inline int gt4hip_grid (gt4hip_context *ctx, uint64_t blocks) { return gt4::strided_grid (ctx->grid_limit, blocks, (uint64_t) (ctx->n_cus > 0 ? ctx->n_cus : 256) * 8); }
+/* one more launch with the grid gt4hip_grid gave for `blocks` blocks of work: counted in "grid_capped" as the first was */
+inline void gt4hip_grid_again (gt4hip_context *ctx, uint64_t blocks, int grid) { ctx->grid_limit.capped += blocks > (uint64_t) grid; }
 /* ... over `items` items, `per_block` to a block */
-inline int gt4hip_grid (const gt4hip_context *ctx, uint64_t items, uint64_t per_block) { return gt4hip_grid (ctx, (items + per_block - 1) / per_block); }
+inline int gt4hip_grid (gt4hip_context *ctx, uint64_t items, uint64_t per_block) { return gt4hip_grid (ctx, (items + per_block - 1) / per_block); }
 
 /* *out = the caller's list `given` if it holds `need` records (an error if not; `s`: the output stream named in the
  * text, < 0 where the call has one output), else a new list of that capacity, which `made` then owns */
@@ -236,10 +239,27 @@ GT4HIP_LOCAL int gt4hip_union_table_checked (gt4hip_context *ctx, const gt4hip_l
 #define GT4HIP_PAIRWISE_UNROLL 4u
 #define GT4HIP_PAIRWISE_BLOCK 32u
 void gt4hip_io_destroy (gt4hip_context *ctx);
+/* threads per workgroup, which is items per block of work, of the item loops of gt4hip_query / _mismatch / _gmer.hip and
+ * gt4hip_index.h (counter "mm_threads") and of gt4hip_caller.hip (counter "caller_threads"); workgroups of k_caller_mlogl
+ * at most (counter "caller_max_grid"); words per block of the radix sort's histogram kernel (counter "sort_hist_chunk") */
+#define GT4HIP_MM_THREADS 256
+/* items per thread and tile of the compaction and hit passes (counter "mm_tile": items per tile), locations per thread and
+ * tile of the gather (counter "gather_tile"), and the most bins gt4hip_list_count_histogram keeps in LDS (counter "hist_lds_bins") */
+#define GT4HIP_MM_ROUNDS 8
+#define GT4HIP_GATHER_ROUNDS 8
+#define GT4HIP_HIST_LDS_BINS 4096u
+#define GT4HIP_CALLER_THREADS 256
+#define GT4HIP_CALLER_MAX_GRID 1024
+#define GT4HIP_SORT_HIST_THREADS 256
+#define GT4HIP_SORT_HIST_ITEMS 16
 /* bytes of text, and codes, per tile of gt4hip_maker.hip's kernels (counters "maker_text_tile", "maker_code_tile") */
 #define GT4HIP_MAKER_TILE 4096u
-/* items per tile of gt4hip_subset.hip's decision kernels (counter "subset_tile") */
+/* items per tile of gt4hip_subset.hip's decision kernels (counter "subset_tile") and elements per thread of its scans
+ * (counter "subset_scan_tile": elements per tile of a scan, 256 threads' worth) */
 #define GT4HIP_SUBSET_TILE 4096u
+#define GT4HIP_SUBSET_SCAN_V 8
+/* raw locations per block of k_pack_locations (counter "pack_threads") */
+#define GT4HIP_PACK_THREADS 256
 /* gt4hip_text_to_words (gt4hip_maker.hip) for gt4hip_gmer.hip: with `counts`, one more pass over the piece's bytes and codes
  * sets counts[0..2] = 'N' / 'n' among the bytes the reference's reader loop takes (all in front of a NUL but FastQ '+'
  * lines), bases of sequence lines, and C / G among those (read_character and read_nucleotide, src/gmer_counter.c:917-936) */

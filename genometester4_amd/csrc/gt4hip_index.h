@@ -13,6 +13,7 @@ namespace {
 constexpr int MM_THREADS = 256;
 constexpr int MM_ROUNDS = 8;                        /* compaction: items per thread and tile */
 constexpr u64 MM_TILE = (u64) MM_THREADS * MM_ROUNDS; /* items per compaction tile */
+static_assert (MM_THREADS == GT4HIP_MM_THREADS && MM_ROUNDS == GT4HIP_MM_ROUNDS, "counters \"mm_threads\" and \"mm_tile\" (gt4hip_host.h)");
 constexpr u32 MM_MAX_INDEX_BITS = 22;               /* 32 MiB of offsets at most: well inside the Infinity Cache */
 
 /* C(n, r) for n, r <= 32 */

@@ -46,6 +46,25 @@ struct PartZero {
   uint64_t rows;
 };
 
+/* A context's limit on the grids of its striding kernels: option "grid_cap" (tests; 0 = none) and counter "grid_capped". */
+struct GridLimit {
+  int64_t cap;
+  uint64_t capped;
+};
+
+/* workgroups of a kernel that strides over `blocks` blocks of work: one each, at most `most` and at most the context's
+ * "grid_cap", at least one; a launch that gets fewer than it has blocks is counted in "grid_capped" */
+inline int strided_grid (GridLimit &lim, uint64_t blocks, uint64_t most)
+{
+  if (lim.cap > 0 && (uint64_t) lim.cap < most) most = (uint64_t) lim.cap;
+  const uint64_t g = blocks < 1 ? 1 : blocks < most ? blocks : most;
+  if (blocks > g) lim.capped++;
+  return (int) g;
+}
+
+/* threads per workgroup of the list utilities at the end of gt4hip_kernels.hip (counter "list_threads") */
+#define GT4HIP_LIST_THREADS 256
+
 /* guided: the co-rank searches place their probes from the coarse neighbours (gt4hip_corank.h); false: plain bisection */
 hipError_t launch_partition (hipStream_t s, const uint32_t *A, uint64_t nA, const uint32_t *B, uint64_t nB,
                              uint64_t num_tiles, uint64_t tile_records, uint64_t *part, bool guided, const PartZero &zero);
@@ -55,15 +74,15 @@ hipError_t launch_pair_merge (hipStream_t s, const PairVariant &v, int grid, con
                               PairControl *ctl);
 hipError_t launch_scan_tiles (hipStream_t s, unsigned long long *desc, uint64_t num_tiles,
                               unsigned long long *block_sums);
-hipError_t launch_generate (hipStream_t s, uint32_t *rec, uint64_t n, uint64_t stride, uint64_t seed,
+hipError_t launch_generate (hipStream_t s, GridLimit &lim, uint32_t *rec, uint64_t n, uint64_t stride, uint64_t seed,
                             uint64_t count_seed, uint32_t max_count, uint64_t mult, uint64_t add);
-hipError_t launch_sum_counts (hipStream_t s, const uint32_t *rec, uint64_t n, unsigned long long *sum);
-hipError_t launch_check_sorted (hipStream_t s, const uint32_t *rec, uint64_t n, unsigned int *bad);
+hipError_t launch_sum_counts (hipStream_t s, GridLimit &lim, const uint32_t *rec, uint64_t n, unsigned long long *sum);
+hipError_t launch_check_sorted (hipStream_t s, GridLimit &lim, const uint32_t *rec, uint64_t n, unsigned int *bad);
 hipError_t launch_lower_bound (hipStream_t s, const uint32_t *rec, uint64_t n, uint64_t key,
                                unsigned long long *idx);
-hipError_t launch_extract_column (hipStream_t s, const uint32_t *rec, uint64_t n, uint32_t *counts, uint32_t n_lists, uint32_t column);
-hipError_t launch_extract_keys (hipStream_t s, const uint32_t *rec, uint64_t n, unsigned long long *keys);
-hipError_t launch_decode_index (hipStream_t s, const unsigned long long *kmers, uint64_t n, uint64_t num_locations, uint32_t *rec);
+hipError_t launch_extract_column (hipStream_t s, GridLimit &lim, const uint32_t *rec, uint64_t n, uint32_t *counts, uint32_t n_lists, uint32_t column);
+hipError_t launch_extract_keys (hipStream_t s, GridLimit &lim, const uint32_t *rec, uint64_t n, unsigned long long *keys);
+hipError_t launch_decode_index (hipStream_t s, GridLimit &lim, const unsigned long long *kmers, uint64_t n, uint64_t num_locations, uint32_t *rec);
 
 int merge_blocks_per_cu (const PairVariant &v);
 

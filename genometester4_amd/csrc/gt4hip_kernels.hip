@@ -1289,13 +1289,8 @@ __global__ void k_decode_index (const u64 *__restrict__ kmers, u64 n, u64 num_lo
   }
 }
 
-inline int grid_for (u64 n, int block, int cap)
-{
-  u64 g = (n + block - 1) / block;
-  if (g < 1) g = 1;
-  if (g > (u64) cap) g = cap;
-  return (int) g;
-}
+/* workgroups of a list utility over n records: GT4HIP_LIST_THREADS records to a block, `cap` workgroups at most */
+inline int grid_for (GridLimit &lim, u64 n, int cap) { return strided_grid (lim, (n + GT4HIP_LIST_THREADS - 1) / GT4HIP_LIST_THREADS, (u64) cap); }
 
 }  // namespace
 
@@ -1388,22 +1383,22 @@ hipError_t launch_scan_tiles (hipStream_t s, unsigned long long *desc, uint64_t 
   return hipGetLastError ();
 }
 
-hipError_t launch_generate (hipStream_t s, uint32_t *rec, uint64_t n, uint64_t stride, uint64_t seed, uint64_t count_seed,
+hipError_t launch_generate (hipStream_t s, GridLimit &lim, uint32_t *rec, uint64_t n, uint64_t stride, uint64_t seed, uint64_t count_seed,
                             uint32_t max_count, uint64_t mult, uint64_t add)
 {
-  hipLaunchKernelGGL (k_generate, dim3 (grid_for (n, 256, 8192)), dim3 (256), 0, s, rec, n, stride, seed, count_seed, max_count, mult, add);
+  hipLaunchKernelGGL (k_generate, dim3 (grid_for (lim, n, 8192)), dim3 (GT4HIP_LIST_THREADS), 0, s, rec, n, stride, seed, count_seed, max_count, mult, add);
   return hipGetLastError ();
 }
 
-hipError_t launch_sum_counts (hipStream_t s, const uint32_t *rec, uint64_t n, unsigned long long *sum)
+hipError_t launch_sum_counts (hipStream_t s, GridLimit &lim, const uint32_t *rec, uint64_t n, unsigned long long *sum)
 {
-  hipLaunchKernelGGL (k_sum_counts, dim3 (grid_for (n, 256, 4096)), dim3 (256), 0, s, rec, n, sum);
+  hipLaunchKernelGGL (k_sum_counts, dim3 (grid_for (lim, n, 4096)), dim3 (GT4HIP_LIST_THREADS), 0, s, rec, n, sum);
   return hipGetLastError ();
 }
 
-hipError_t launch_check_sorted (hipStream_t s, const uint32_t *rec, uint64_t n, unsigned int *bad)
+hipError_t launch_check_sorted (hipStream_t s, GridLimit &lim, const uint32_t *rec, uint64_t n, unsigned int *bad)
 {
-  hipLaunchKernelGGL (k_check_sorted, dim3 (grid_for (n, 256, 4096)), dim3 (256), 0, s, rec, n, bad);
+  hipLaunchKernelGGL (k_check_sorted, dim3 (grid_for (lim, n, 4096)), dim3 (GT4HIP_LIST_THREADS), 0, s, rec, n, bad);
   return hipGetLastError ();
 }
 
@@ -1413,21 +1408,21 @@ hipError_t launch_lower_bound (hipStream_t s, const uint32_t *rec, uint64_t n, u
   return hipGetLastError ();
 }
 
-hipError_t launch_extract_column (hipStream_t s, const uint32_t *rec, uint64_t n, uint32_t *counts, uint32_t n_lists, uint32_t column)
+hipError_t launch_extract_column (hipStream_t s, GridLimit &lim, const uint32_t *rec, uint64_t n, uint32_t *counts, uint32_t n_lists, uint32_t column)
 {
-  hipLaunchKernelGGL (k_extract_column, dim3 (grid_for (n, 256, 4096)), dim3 (256), 0, s, rec, n, counts, n_lists, column);
+  hipLaunchKernelGGL (k_extract_column, dim3 (grid_for (lim, n, 4096)), dim3 (GT4HIP_LIST_THREADS), 0, s, rec, n, counts, n_lists, column);
   return hipGetLastError ();
 }
 
-hipError_t launch_extract_keys (hipStream_t s, const uint32_t *rec, uint64_t n, unsigned long long *keys)
+hipError_t launch_extract_keys (hipStream_t s, GridLimit &lim, const uint32_t *rec, uint64_t n, unsigned long long *keys)
 {
-  hipLaunchKernelGGL (k_extract_keys, dim3 (grid_for (n, 256, 4096)), dim3 (256), 0, s, rec, n, keys);
+  hipLaunchKernelGGL (k_extract_keys, dim3 (grid_for (lim, n, 4096)), dim3 (GT4HIP_LIST_THREADS), 0, s, rec, n, keys);
   return hipGetLastError ();
 }
 
-hipError_t launch_decode_index (hipStream_t s, const unsigned long long *kmers, uint64_t n, uint64_t num_locations, uint32_t *rec)
+hipError_t launch_decode_index (hipStream_t s, GridLimit &lim, const unsigned long long *kmers, uint64_t n, uint64_t num_locations, uint32_t *rec)
 {
-  hipLaunchKernelGGL (k_decode_index, dim3 (grid_for (n, 256, 4096)), dim3 (256), 0, s, (const u64 *) kmers, n, num_locations, rec);
+  hipLaunchKernelGGL (k_decode_index, dim3 (grid_for (lim, n, 4096)), dim3 (GT4HIP_LIST_THREADS), 0, s, (const u64 *) kmers, n, num_locations, rec);
   return hipGetLastError ();
 }
 

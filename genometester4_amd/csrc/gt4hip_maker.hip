@@ -369,9 +369,9 @@ __global__ __launch_bounds__ (MK_THREADS) void k_mk_emit_loc (const unsigned cha
 }
 
 /* raw locations of one file -> the words of the location section (reference :1066): file | ordinal | position | strand */
-__global__ __launch_bounds__ (256) void k_pack_locations (u64 *__restrict__ raw, u64 n, u64 file, u32 sb, u32 pb)
+__global__ __launch_bounds__ (GT4HIP_PACK_THREADS) void k_pack_locations (u64 *__restrict__ raw, u64 n, u64 file, u32 sb, u32 pb)
 {
-  for (u64 i = (u64) blockIdx.x * 256 + threadIdx.x; i < n; i += (u64) gridDim.x * 256) {
+  for (u64 i = (u64) blockIdx.x * GT4HIP_PACK_THREADS + threadIdx.x; i < n; i += (u64) gridDim.x * GT4HIP_PACK_THREADS) {
     const u64 r = raw[i];
     raw[i] = (file << (sb + pb + 1)) | ((r >> 33) << (pb + 1)) | (r & 0x1ffffffffull);
   }
@@ -603,11 +603,14 @@ int maker_classify_count (MakerCall &m)
   hipLaunchKernelGGL (k_mk_summary, dim3 (m.grid), dim3 (MK_THREADS), 0, st, m.d_text, (u64) m.n_bytes, tiles, m.tile_cnt, m.tile_info, m.info);
   hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, st, m.tile_cnt, tiles, m.tile_off, &m.info->n_words);
   hipLaunchKernelGGL (k_mk_state_scan, dim3 (1), dim3 (1024), 0, st, m.tile_info, tiles, m.c.in_name, m.c.line_phase, m.tile_state);
+  gt4hip_grid_again (ctx, tiles, m.grid);
   hipLaunchKernelGGL (m.kern->codes, dim3 (m.grid), dim3 (MK_THREADS), 0, st, m.d_text, (u64) m.n_bytes, tiles, m.tile_off, m.tile_state, m.c.at_line_start, m.buf + MK_HALO, m.info);
   /* count: words per tile of codes and where each tile's go; with locations the same for the events of each tile of text */
+  gt4hip_grid_again (ctx, tiles, m.grid);
   hipLaunchKernelGGL (k_mk_emit<false>, dim3 (m.grid), dim3 (MK_THREADS), 0, st, m.buf, m.info, m.tiles, m.k, 0u, m.emit_cnt, m.emit_off, (u64 *) NULL);
   hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, st, m.emit_cnt, m.tiles, m.emit_off, &m.info->n_words);
   if (m.loc) {
+    gt4hip_grid_again (ctx, tiles, m.grid);
     hipLaunchKernelGGL (m.kern->count_events, dim3 (m.grid), dim3 (MK_THREADS), 0, st, m.d_text, (u64) m.n_bytes, m.tiles, m.tile_off, m.tile_state, m.file_off, m.ev_cnt, m.ev_off, m.ev, m.info);
     hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, st, m.ev_cnt, m.tiles, m.ev_off, &m.info->n_events);
   }
@@ -642,6 +645,7 @@ int maker_text_counts (MakerCall &m, uint64_t counts[3])
   const int rc = m.blk.get (ctx, 3 * 8, (void **) &d);
   if (rc) return rc;
   HIPCHK (ctx, hipMemsetAsync (d, 0, 3 * 8, ctx->stream));
+  gt4hip_grid_again (ctx, m.tiles, m.grid);
   gt4hip_launch_text_counts (ctx->stream, m.grid, m.c.file_type == GT4HIP_MAKER_FASTQ, m.d_text, m.n_bytes, m.tiles, m.tile_state, m.buf + MK_HALO, m.info, d);
   HIPCHK (ctx, hipGetLastError ());
   return gt4hip_read_back (ctx, counts, d, 3 * 8, "reading the text's statistics back failed");
@@ -665,6 +669,7 @@ int maker_emit_words (MakerCall &m)
     return gt4hip_fail (ctx, GT4HIP_ENOMEM, "gt4hip_text_to_words: %llu words", (unsigned long long) m.h.n_words);
   ctx->maker_words = (gt4hip_list *) owner;
   hipEventRecord (ctx->ev[2], st);
+  gt4hip_grid_again (ctx, m.tiles, m.grid);
   hipLaunchKernelGGL (k_mk_emit<true>, dim3 (m.grid), dim3 (MK_THREADS), 0, st, m.buf, m.info, m.tiles, m.k, (u32) ((m.flags & GT4HIP_MAKER_FORWARD_ONLY) != 0), m.emit_cnt, m.emit_off, (u64 *) w);
   hipError_t e = hipGetLastError ();
   hipEventRecord (ctx->ev[3], st);
@@ -691,10 +696,13 @@ int maker_emit_locations (MakerCall &m)
   int rc;
   if ((rc = m.blk.get (ctx, (size_t) h.n_events * 16, (void **) &m.ev))) return rc;
   hipEventRecord (ctx->ev[2], st);
-  if (h.n_events)
+  if (h.n_events) {
+    gt4hip_grid_again (ctx, m.tiles, m.grid);
     hipLaunchKernelGGL (m.kern->write_events, dim3 (m.grid), dim3 (MK_THREADS), 0, st, m.d_text, (u64) m.n_bytes, m.tiles, m.tile_off, m.tile_state, m.file_off, m.ev_cnt, m.ev_off, m.ev, m.info);
+  }
   if (h.n_words) {
     const u64 g0 = loc->in ? loc->in->n_events : 0, ord0 = loc->in && loc->in->n_subseqs ? loc->in->n_subseqs - 1 : 0, codes0 = loc->in ? loc->in->seq_codes : 0;
+    gt4hip_grid_again (ctx, m.tiles, m.grid);
     hipLaunchKernelGGL (m.kern->emit_loc, dim3 (m.grid), dim3 (MK_THREADS), 0, st, m.buf, m.info, m.tiles, m.k, m.emit_off, loc->dst_words, loc->dst_raw, m.ev, h.n_events, g0, ord0, codes0);
   }
   hipEventRecord (ctx->ev[3], st);
@@ -766,7 +774,7 @@ extern "C" int gt4hip_pack_locations (gt4hip_context *ctx, uint64_t *d_raw, uint
     return gt4hip_fail (ctx, GT4HIP_EINVAL, "gt4hip_pack_locations: file %llu with %u + %u + 1 bits behind it does not fit 64 bits", (unsigned long long) file, subseq_bits, pos_bits);
   HIPCHK (ctx, hipSetDevice (ctx->device));
   if (!n) return GT4HIP_OK;
-  hipLaunchKernelGGL (k_pack_locations, dim3 (gt4hip_grid (ctx, n, 256)), dim3 (256), 0, ctx->stream, (u64 *) d_raw, (u64) n, (u64) file, subseq_bits, pos_bits);
+  hipLaunchKernelGGL (k_pack_locations, dim3 (gt4hip_grid (ctx, n, GT4HIP_PACK_THREADS)), dim3 (GT4HIP_PACK_THREADS), 0, ctx->stream, (u64 *) d_raw, (u64) n, (u64) file, subseq_bits, pos_bits);
   HIPCHK (ctx, hipGetLastError ());
   HIPCHK (ctx, hipStreamSynchronize (ctx->stream));
   return GT4HIP_OK;

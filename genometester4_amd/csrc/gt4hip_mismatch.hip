@@ -220,6 +220,7 @@ int compact (gt4hip_context *ctx, const u32 *keep, u64 n, u32 *tile_cnt, u64 *ti
   const int grid = gt4hip_grid (ctx, tiles, 1);
   hipLaunchKernelGGL (k_tile_count, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, keep, n, tiles, tile_cnt);
   hipLaunchKernelGGL (k_tile_scan, dim3 (1), dim3 (1024), 0, ctx->stream, tile_cnt, tiles, tile_off, ctx->scratch);
+  gt4hip_grid_again (ctx, tiles, grid);
   hipLaunchKernelGGL ((k_scatter<SRC_REC, DST_REC>), dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, keep, n, tiles, tile_off, src_keys, cnt, dst_keys,
                       dst_cnt, sum ? ctx->scratch + 1 : (unsigned long long *) NULL);
   HIPCHK (ctx, hipGetLastError ());

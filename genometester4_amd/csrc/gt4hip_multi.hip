@@ -354,8 +354,8 @@ extern "C" int gt4hip_shard_cuts (gt4hip_context *ctx, const gt4hip_list *const 
   for (uint32_t i = 0; i < n; i++) {
     const uint64_t m = lists[i]->n_words / stride;
     if (!m) continue;
-    const unsigned grid = (unsigned) ((m + 255) / 256 < 4096 ? (m + 255) / 256 : 4096);
-    hipLaunchKernelGGL (k_sample_stride, dim3 (grid), dim3 (256), 0, ctx->stream, (const uint32_t *) lists[i]->dev, lists[i]->n_words, stride, (unsigned long long *) dev + at);
+    const int grid = gt4hip_grid (ctx, m, GT4HIP_LIST_THREADS); /* (m < 2 * target: 512 blocks at most) */
+    hipLaunchKernelGGL (k_sample_stride, dim3 (grid), dim3 (GT4HIP_LIST_THREADS), 0, ctx->stream, (const uint32_t *) lists[i]->dev, lists[i]->n_words, stride, (unsigned long long *) dev + at);
     at += m;
   }
   rc = gt4hip_read_back (ctx, host.data (), dev, (size_t) m_total * 8, "gt4hip_shard_cuts");

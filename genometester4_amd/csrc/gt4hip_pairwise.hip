@@ -177,6 +177,7 @@ int table_pairwise (gt4hip_context *ctx, const gt4hip_count_table *table, uint64
       const u32 ci = bi * PW_BLOCK, cj = bj * PW_BLOCK;
       const PwPass b = { ci, n - ci < PW_BLOCK ? n - ci : PW_BLOCK, cj, n - cj < PW_BLOCK ? n - cj : PW_BLOCK };
       const bool same = bi == bj;
+      if (bi || bj) gt4hip_grid_again (ctx, t.segments, (int) grid.x);
       switch (g) {
         case 2: launch_partial<2> (same, grid, st, t, b, ws); break;
         case 4: launch_partial<4> (same, grid, st, t, b, ws); break;

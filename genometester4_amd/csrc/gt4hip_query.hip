@@ -239,6 +239,7 @@ struct LocationBits {
 
 constexpr int GATHER_ROUNDS = 8;
 constexpr u32 GATHER_TILE = MM_THREADS * GATHER_ROUNDS; /* output locations per tile */
+static_assert (GATHER_ROUNDS == GT4HIP_GATHER_ROUNDS, "counter \"gather_tile\" (gt4hip_host.h)");
 constexpr u32 GATHER_LDS_SEGS = GATHER_TILE + 1;        /* segments of a tile kept in LDS: every tile without zero-length ones fits */
 
 /* The first index i of the ascending a[0..n) with a[i] > o (n when there is none), by a whole wavefront: every step
@@ -392,6 +393,7 @@ __global__ __launch_bounds__ (MM_THREADS) void k_count_split (const u32 *rec, u6
 }
 
 constexpr u32 HIST_LDS_BINS = 4096;
+static_assert (HIST_LDS_BINS == GT4HIP_HIST_LDS_BINS, "counter \"hist_lds_bins\" (gt4hip_host.h)");
 
 /* hist[c - 1] += 1 for every record with 1 <= count c <= max.  LDS: up to HIST_LDS_BINS bins per workgroup (u32: a
  * workgroup sees fewer than 2^32 records), flushed with one u64 atomic per used bin; above that global atomics. */
@@ -855,6 +857,7 @@ int hits_fill (HitCall &c, gt4hip_query_hit *hits, gt4hip_location *locations)
   if (c.li && ((rc = c.blk.get (ctx, total_hits * 8, (void **) &c.P.seg_off)) || (rc = c.blk.get (ctx, total_hits * 8, (void **) &c.P.seg_src)) ||
                (rc = c.blk.get (ctx, total_locs * sizeof (gt4hip_location), (void **) &d_locs))))
     return rc;
+  gt4hip_grid_again (ctx, c.P.n_tiles, c.grid);
   launch_hits<true> (c);
   HIPCHK (ctx, hipGetLastError ());
   if (c.li) {

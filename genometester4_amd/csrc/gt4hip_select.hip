@@ -341,6 +341,7 @@ int table_select (gt4hip_context *ctx, const gt4hip_count_table *table, uint32_t
   if ((rc = gt4hip_output_list (ctx, -1, res->out, n_words, word_length, made, &o))) return rc;
   if (n_words) {
     HIPCHK (ctx, hipEventRecord (ctx->ev[2], st));
+    gt4hip_grid_again (ctx, t.segments, (int) grid.x);
     hipLaunchKernelGGL (k_select_emit, grid, dim3 (SEL_THREADS), 0, st, t, (const u32 *) row_cnt, (const unsigned char *) row_keep, (const u32 *) seg_cnt,
                         (const u64 *) seg_off, (u32 *) o->dev);
     HIPCHK (ctx, hipGetLastError ());

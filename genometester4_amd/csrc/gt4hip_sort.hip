@@ -60,6 +60,7 @@ constexpr int RADIX_MAX_PASSES = 8;
 constexpr int RADIX_LOOK = GT4_RADIX_LOOK; /* earlier tiles inspected per round trip of the look-back */
 constexpr int HIST_NT = 256;
 constexpr int HIST_ITEMS = 16;
+static_assert (HIST_NT == GT4HIP_SORT_HIST_THREADS && HIST_ITEMS == GT4HIP_SORT_HIST_ITEMS, "counter \"sort_hist_chunk\" (gt4hip_host.h)");
 
 /* Tile states of the chained scan, one 64-bit word per (tile, digit): what the tile holds of the digit
  * (AGG) or what all tiles up to and including it hold (PREFIX), tagged with the pass so that the words

@@ -39,8 +39,9 @@ static_assert ((u64) SUBSET_THREADS * SUBSET_V == GT4HIP_SUBSET_TILE, "the count
  * fastest, rows 4 apart) both spread over the banks. */
 constexpr int STAGE_ROW = SUBSET_THREADS + 4;
 constexpr int SCAN_THREADS = 256;
-constexpr int SCAN_V = 8;
+constexpr int SCAN_V = GT4HIP_SUBSET_SCAN_V;
 constexpr u64 SCAN_TILE = (u64) SCAN_THREADS * SCAN_V;
+static_assert (SCAN_TILE == 256u * GT4HIP_SUBSET_SCAN_V, "counter \"subset_scan_tile\" (gt4hip_api.hip)");
 
 constexpr u64 LCG_A = 0x5DEECE66Dull, LCG_C = 0xBull, LCG_MASK = (1ull << 48) - 1;
 

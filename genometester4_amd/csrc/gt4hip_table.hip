@@ -140,7 +140,7 @@ static int table_column_by_union (gt4hip_context *ctx, const gt4hip_list *keys, 
   int rc = gt4hip_run_pair (ctx, (const uint32_t *) keys->dev, keys->n_words, (const uint32_t *) lj->dev, lj->n_words, p, false, dst, &run);
   if (rc) return rc;
   if (run.n_words[0] != keys->n_words) return gt4hip_fail (ctx, GT4HIP_EINTERNAL, "count table: a list holds keys outside the key list");
-  HIPCHK (ctx, launch_extract_column (ctx->stream, (const uint32_t *) tmp->dev, keys->n_words, (uint32_t *) t->device_counts, t->n_lists, column));
+  HIPCHK (ctx, launch_extract_column (ctx->stream, ctx->grid_limit, (const uint32_t *) tmp->dev, keys->n_words, (uint32_t *) t->device_counts, t->n_lists, column));
   return GT4HIP_OK;
 }
 
@@ -216,7 +216,7 @@ extern "C" int gt4hip_union_table (gt4hip_context *ctx, const gt4hip_list *const
   rc = gt4hip_table_alloc (ctx, table, n, n_lists);
   if (!rc) rc = gt4hip_list_new (ctx, n + longest, lists[0]->word_length, &tmp);
   if (!rc) {
-    hipError_t e = launch_extract_keys (ctx->stream, (const uint32_t *) u.out->dev, n, (unsigned long long *) table->device_keys);
+    hipError_t e = launch_extract_keys (ctx->stream, ctx->grid_limit, (const uint32_t *) u.out->dev, n, (unsigned long long *) table->device_keys);
     if (e != hipSuccess) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "count table kernels failed: %s", hipGetErrorString (e));
   }
   for (uint32_t j = 0; j < n_lists && !rc; j++) rc = table_column_by_union (ctx, u.out, lists[j], tmp, table, j);
@@ -274,7 +274,7 @@ extern "C" int gt4hip_probe_table_ex (gt4hip_context *ctx, const gt4hip_list *co
   if (!rc) rc = gt4hip_list_new (ctx, 2 * n, base->word_length, &tmp);
   if (!rc) rc = gt4hip_list_new (ctx, n, base->word_length, &inter);
   if (!rc) {
-    hipError_t e = launch_extract_keys (ctx->stream, (const uint32_t *) base->dev, n, (unsigned long long *) table->device_keys);
+    hipError_t e = launch_extract_keys (ctx->stream, ctx->grid_limit, (const uint32_t *) base->dev, n, (unsigned long long *) table->device_keys);
     if (e != hipSuccess) rc = gt4hip_fail (ctx, GT4HIP_EHIP, "count table kernels failed: %s", hipGetErrorString (e));
   }
   for (uint32_t j = 0; j < n_lists && !rc; j++) {

@@ -779,6 +779,17 @@ int gt4hip_synchronize (gt4hip_context *ctx);
  *                      ranges are the same either way
  *   "select_vec" = 0 / -1  gt4hip_table_select reads rows of a multiple of four counts (in 16-byte aligned arrays) 16 bytes
  *                      per lane / every row a dword per lane, as all other rows are read (bench, tests)
+ *   "grid_cap" = n     (tests) every kernel that walks its work in a loop stepping by its grid -- items, tiles or segments:
+ *                      the query, mismatch, maker, gmer, subset, select, pairwise and caller kernels, the radix sort's
+ *                      histogram, the list utilities -- is launched with n workgroups at most, so that small inputs take the
+ *                      second and later trips of those loops; 0 (default): the built-in caps alone.  Results do not change.
+ *                      Not followed by kernels launched one workgroup per tile or whose workgroups wait for one another
+ *                      (the merge and N-way kernels keep "grid"; radix scatter, fold, index and partition kernels), nor
+ *                      by gt4hip_caller_mlogl, whose grid is a function of the number of markers alone
+ *   "poison" = 1       (tests) every device block the library hands out, new or from its pool, is filled with 0xA5 bytes
+ *                      first: a block from the pool holds what an earlier call left there, often the very results the
+ *                      next call is to compute, and an item a kernel skips would keep them
+ *   "caller_piece" = n (tests) markers per piece of gt4hip_caller_probabilities (0: 2^22, with all 15 likelihoods 2^20)
  *   "geom0" / "geom1"  force the 512- / 1024-thread geometry (experiments). */
 int gt4hip_set_option (gt4hip_context *ctx, const char *name, int64_t value);
 /* Diagnostic counters of a context.  "single_pass_fallbacks": calls whose single-pass merge gave up a
@@ -799,7 +810,16 @@ int gt4hip_set_option (gt4hip_context *ctx, const char *name, int64_t value);
  * "subset_passes": passes of the last gt4hip_list_subset until a scan changed no tile's carry-in (0: it had nothing to walk);
  * "subset_tile": items per tile of its kernels; "subset_us": its device time (HIP events around the kernels, the one
  * word read back per pass included); "select_wide": 1 when the context's last gt4hip_table_select (gt4hip_select_multi's too)
- * read 16 bytes per lane, else 0. */
+ * read 16 bytes per lane, else 0; "grid_capped": launches of the context, since it was made, of a kernel that strides over its
+ * work with fewer workgroups than blocks of work (by option "grid_cap" or by a built-in cap): the loops of those took a second
+ * trip.  Sizes the tests build their inputs from: "mm_threads": items per block of work of the item loops of the query,
+ * mismatch and gmer kernels (a quarter of the records per block of the list statistics); "mm_tile": items per tile of the
+ * hit and compaction passes; "gather_tile": locations per tile of gt4hip_query_lookup_locations' gather; "hist_lds_bins": the
+ * most bins gt4hip_list_count_histogram keeps in LDS; "list_threads": records per block of gt4hip_generate, _list_sum_counts,
+ * _list_is_sorted, _list_upload_index and the count table's column kernels; "sort_hist_chunk": words per block of the
+ * radix sort's histogram; "select_segment": rows per segment of a contiguous count table; "subset_scan_tile": elements per tile of
+ * gt4hip_list_subset's scans; "pack_threads": locations per block of gt4hip_pack_locations; "caller_threads": markers per
+ * block of the caller kernels; "caller_max_grid": workgroups of gt4hip_caller_mlogl at most. */
 int gt4hip_get_counter (gt4hip_context *ctx, const char *name, uint64_t *value);
 /* Diagnostic: the partition launch of a pair merge alone, with tiles of tile_records merged records (any length: tests cut
  * small lists into many tiles).  host_part receives 2 x (tiles + 1) words, tiles = ceil ((|a| + |b|) / tile_records):

@@ -74,7 +74,6 @@ def test_model_sets_are_what_they_claim():
 @pytest.mark.parametrize("name", list(MODELS))
 @pytest.mark.parametrize("size", SIZES)
 def test_probabilities_against_the_model(ctx, name, size):
-    _, ref = _ref(name)
     pairs = [PAIRS[(7 * size + i) % len(PAIRS)] for i in range(size)] if size < len(PAIRS) else [PAIRS[i % len(PAIRS)] for i in range(size)]
     s = ctx.caller_set([p[0] for p in pairs], [p[1] for p in pairs])
     cm = _capi_model(name)
@@ -82,6 +81,13 @@ def test_probabilities_against_the_model(ctx, name, size):
     best2, a_best2, a_sum2, none = s.probabilities(cm)
     s.free()
     assert none is None and best.tobytes() == best2.tobytes() and a_best.tobytes() == a_best2.tobytes() and a_sum.tobytes() == a_sum2.tobytes()
+    check_probabilities(name, pairs, best, a_best, a_sum, a_all)
+
+
+def check_probabilities(name, pairs, best, a_best, a_sum, a_all):
+    """what gt4hip_caller_probabilities gave for `pairs` (of PAIRS) under MODELS[name], all 15 likelihoods included, against
+    the model: every marker"""
+    _, ref = _ref(name)
     for i, p in enumerate(pairs):
         a, rel = ref[p]
         tol = [M.tolerance(a[j], rel[j]) for j in range(M.N_GT)]
@@ -176,6 +182,74 @@ def test_mlogl_clamps_a_vanishing_likelihood_and_sums_nothing_to_minus_zero(ctx,
     before = s.mlogl(cm)
     s.mlogl(_capi_model("haploid"))
     assert struct.pack("d", s.mlogl(cm)) == struct.pack("d", before)
+
+
+def _cycled(n):
+    """n markers, the 121 PAIRS over and over: the model evaluates 121 markers, not n"""
+    return [PAIRS[i % len(PAIRS)] for i in range(n)]
+
+
+def _cycled_mlogl(name, n):
+    """(sum, bound) of caller_model.mlogl over _cycled (n): math.fsum of a pair's value x the times it occurs, and the sum of
+    the per-marker bounds the model defines, a pair's bound x the times it occurs"""
+    m = _ref(name)[0]
+    times = [n // len(PAIRS) + (j < n % len(PAIRS)) for j in range(len(PAIRS))]
+    each = [M.mlogl(m, [p]) for p in PAIRS]
+    return math.fsum(v * t for (v, _), t in zip(each, times)), math.fsum(b * t for (_, b), t in zip(each, times))
+
+
+@pytest.mark.parametrize("which", ["tree_second_trip", "max_grid"])
+def test_mlogl_above_256_workgroups_and_at_the_largest_grid(ctx, which):
+    """k_caller_mlogl adds the workgroups' sums with a loop over the grid in steps of a workgroup's threads: 65,536 + 257
+    markers are 258 workgroups, so that loop takes a second trip; 262,144 + 257 markers are more than the 1024 workgroups
+    the grid has at most, so the marker loop does (some threads add two markers).  Bit for bit repeatable, within the
+    summed bound of the model, and bitwise the same under "grid_cap" = 1: the grid is a function of n alone.
+
+    Largest error over its bound seen on an MI355X: 1.3e-5 at both sizes (profiles/caller/README.md)."""
+    threads, most = ctx.get_counter("caller_threads"), ctx.get_counter("caller_max_grid")
+    n = {"tree_second_trip": threads * threads, "max_grid": threads * most}[which] + threads + 1
+    assert n == {"tree_second_trip": 65_536 + 257, "max_grid": 262_144 + 257}[which]
+    assert ((n + threads - 1) // threads > threads) and ((n + threads - 1) // threads > most) == (which == "max_grid")
+    pairs = _cycled(n)
+    s = ctx.caller_set([p[0] for p in pairs], [p[1] for p in pairs])
+    cm = _capi_model("diploid_lambda30")
+    want, bound = _cycled_mlogl("diploid_lambda30", n)
+    got = s.mlogl(cm)
+    again = s.mlogl(cm)
+    cut = ctx.get_counter("grid_capped")
+    ctx.set_option("grid_cap", 1)
+    try:
+        capped = s.mlogl(cm)
+    finally:
+        ctx.set_option("grid_cap", 0)
+    s.free()
+    print("mlogl of %d markers: %.17g against %.17g, error %.3g of %.3g allowed (%.4f)" % (n, got, want, abs(got - want), bound, abs(got - want) / bound))
+    assert struct.pack("d", got) == struct.pack("d", again)
+    assert struct.pack("d", got) == struct.pack("d", capped) and ctx.get_counter("grid_capped") == cut
+    assert abs(got - want) <= bound, (got, want, bound)
+
+
+@pytest.mark.parametrize("name", ["diploid_lambda30", "size_nonpositive_at_2_lambda"])
+def test_probabilities_in_pieces(ctx, name):
+    """option "caller_piece" = 300 on 3 x 300 + 1 markers: three full pieces and one marker, byte for byte what the call gives
+    in one piece, with and without all 15 likelihoods, and every marker against the model"""
+    pairs = _cycled(3 * 300 + 1)
+    s = ctx.caller_set([p[0] for p in pairs], [p[1] for p in pairs])
+    cm = _capi_model(name)
+    whole = s.probabilities(cm, all15=True), s.probabilities(cm)
+    ctx.set_option("caller_piece", 300)
+    ctx.set_option("poison", 1)  # (the device block of the pieces is not to hold the results of the whole)
+    try:
+        pieced = s.probabilities(cm, all15=True), s.probabilities(cm)
+    finally:
+        ctx.set_option("caller_piece", 0)
+        ctx.set_option("poison", 0)
+    s.free()
+    for a, b in zip(whole, pieced):
+        assert b[3] is None or b[3].shape == (len(pairs), M.N_GT)
+        assert [x is None or x.tobytes() for x in a] == [x is None or x.tobytes() for x in b]
+    assert [x.tobytes() for x in pieced[0][:3]] == [x.tobytes() for x in pieced[1][:3]]
+    check_probabilities(name, pairs, *pieced[0])
 
 
 def test_ranges_outside_the_set_are_refused(ctx, training):
