@@ -91,6 +91,14 @@ class LocationsPiece(C.Structure):
                 ("closed_seq_len", C.c_uint64), ("closed", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class SeqProfile(C.Structure):
+    """gt4hip_seq_profile: the words of a sequence, those that hit, and the sum of the hits' values"""
+    _fields_ = [("n_words", C.c_uint64), ("n_hits", C.c_uint64), ("sum", C.c_uint64)]
+
+
+SEQ_PROFILE_DTYPE = np.dtype([("n_words", "<u8"), ("n_hits", "<u8"), ("sum", "<u8")])
+
+
 class IndexArrays(C.Structure):
     _fields_ = [("n_kmers", C.c_uint64), ("n_locations", C.c_uint64), ("n_values", C.c_uint64),
                 ("d_kmers", C.c_void_p), ("d_locations", C.c_void_p)]
@@ -135,6 +143,7 @@ SYMBOLS = [
     "gt4hip_sort_pairs", "gt4hip_pairs_to_index", "gt4hip_index_free",
     "gt4hip_list_subset", "gt4hip_subset_state_at",
     "gt4hip_text_to_locations", "gt4hip_locations_free", "gt4hip_pack_locations", "gt4hip_pairs_reserve", "gt4hip_pairs_release",
+    "gt4hip_query_profile_words", "gt4hip_query_profile_text",
     "gt4hip_pair_partition",
     "gt4hip_gmer_db_create", "gt4hip_gmer_db_free", "gt4hip_gmer_db_n_kmers", "gt4hip_gmer_db_last_ms", "gt4hip_gmer_count_words",
     "gt4hip_gmer_count_text", "gt4hip_gmer_counts_download", "gt4hip_gmer_counts_reset",
@@ -251,6 +260,9 @@ def lib():
             "gt4hip_pack_locations": (C.c_int, [vp, vp, u64, u64, C.c_uint, C.c_uint]),
             "gt4hip_pairs_reserve": (C.c_int, [vp, u64, C.POINTER(vp), C.POINTER(vp)]),
             "gt4hip_pairs_release": (None, [vp]),
+            "gt4hip_query_profile_words": (C.c_int, [vp, vp, vp, vp, u64, u64, u64, C.POINTER(QueryParams), u32, u32, vp]),
+            "gt4hip_query_profile_text": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_uint, C.POINTER(QueryParams), u32, u32, C.POINTER(LocationsCarry),
+                                                    C.POINTER(LocationsCarry), C.POINTER(LocationsPiece), vp, u64, C.POINTER(u64), C.POINTER(u64)]),
             "gt4hip_list_subset": (C.c_int, [vp, vp, C.POINTER(SubsetParams), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]),
             "gt4hip_subset_state_at": (u64, [u64, u64]),
             "gt4hip_pair_partition": (C.c_int, [vp, vp, vp, u64, vp]),
@@ -781,6 +793,64 @@ class Context:
         finally:
             lib().gt4hip_locations_free(self.h)
             lib().gt4hip_pairs_release(self.h)
+
+    def query_profile_words(self, qindex, words_ptr, raw_ptr, n_words, first_ordinal, n_seqs, n_mm=0, pm_3=0, lo=1, hi=0xFFFFFFFF):
+        """n_words words and raw locations in device memory -> a SEQ_PROFILE_DTYPE array of n_seqs entries, entry s for
+        the words of ordinal first_ordinal + s (gt4hip_query_profile_words).  The array is preset to 0xA5 bytes."""
+        out = np.empty(n_seqs, dtype=SEQ_PROFILE_DTYPE)
+        out.view(np.uint8)[:] = 0xA5
+        prm = QueryParams(n_mm, pm_3, 1)
+        self._chk(lib().gt4hip_query_profile_words(self.h, qindex.h, C.c_void_p(words_ptr), C.c_void_p(raw_ptr), n_words, first_ordinal, n_seqs, C.byref(prm),
+                                                   lo, hi, out.ctypes.data if n_seqs else None))
+        return out
+
+    def query_profile_text(self, qindex, pieces, n_mm=0, pm_3=0, lo=1, hi=0xFFFFFFFF, capacity=64):
+        """The pieces of one file, in order -> (SEQ_PROFILE_DTYPE array with one entry per sequence of the file, subsequence
+        records as Context.text_to_locations gives them) (gt4hip_query_profile_text, one call per piece and a second where
+        the entries did not fit `capacity`, the carry handed on; entry 0 of a piece is added to the sequence the piece
+        before left open).  Malformed text raises Gt4HipError with `error_offset` (in the piece) and `kind`.
+        self.profile_call_s: seconds spent inside the library's calls."""
+        import time
+        prm = QueryParams(n_mm, pm_3, 1)
+        carry, prof, subs, total = None, [], [], 0
+        self.profile_call_s = 0.0
+        try:
+            for p in pieces:
+                buf = (C.c_char * max(len(p), 1)).from_buffer_copy(bytes(p) or b"\0")
+                cap = capacity
+                while True:
+                    out, piece, err, n = LocationsCarry(), LocationsPiece(), C.c_uint64(), C.c_uint64()
+                    got = np.empty(cap, dtype=SEQ_PROFILE_DTYPE)
+                    got.view(np.uint8)[:] = 0xA5
+                    t0 = time.time()
+                    rc = lib().gt4hip_query_profile_text(self.h, qindex.h, buf, len(p), 0, C.byref(prm), lo, hi, C.byref(carry) if carry is not None else None,
+                                                         C.byref(out), C.byref(piece), got.ctypes.data if cap else None, cap, C.byref(n), C.byref(err))
+                    self.profile_call_s += time.time() - t0
+                    if rc:
+                        e = Gt4HipError(rc, lib().gt4hip_last_error(self.h).decode())
+                        e.error_offset, e.kind = err.value, out.reader.error
+                        raise e
+                    if n.value <= cap:
+                        break
+                    cap = n.value
+                got = got[:n.value]
+                if carry is not None and carry.seq_open:
+                    for f in SEQ_PROFILE_DTYPE.names:
+                        prof[-1][f][-1] += got[f][0]
+                    got = got[1:]
+                if len(got):
+                    prof.append(got.copy())
+                if piece.closed:
+                    subs[-1][-1][3] = piece.closed_seq_len
+                if piece.n_subseqs:
+                    subs.append(np.frombuffer(C.string_at(piece.subseqs, piece.n_subseqs * 32), dtype=np.uint64).reshape(-1, 4).copy())
+                total += len(p)
+                carry = out
+            if carry is not None and carry.seq_open:
+                subs[-1][-1][3] = total - subs[-1][-1][2]
+            return (np.concatenate(prof) if prof else np.zeros(0, dtype=SEQ_PROFILE_DTYPE)), [[int(x) for x in r] for a in subs for r in a]
+        finally:
+            lib().gt4hip_locations_free(self.h)
 
     def pack_locations(self, raw_ptr, n, file, subseq_bits, pos_bits):
         """n raw locations of file number `file` (device memory) -> location words, in place (gt4hip_pack_locations)."""

@@ -51,6 +51,14 @@ int gt4_cli_refuse_gzip (const char *name, int c0, int c1)
   return 1;
 }
 
+uint64_t gt4_cli_name_length (const unsigned char *data, uint64_t size, uint64_t name_pos)
+{
+  uint64_t len = 0;
+  if (!data || name_pos >= size) return 0;
+  while (name_pos + len < size && data[name_pos + len] > ' ') len++;
+  return len;
+}
+
 int gt4_cli_write_list_file (gt4hip_context *ctx, const gt4hip_list *list, unsigned int word_length, uint64_t n_words, uint64_t total_count,
                              const char *final_name, unsigned int mode, const char *prefix)
 {

@@ -33,6 +33,10 @@ void gt4_cli_read_environment (int *device, int *verbose);
 /* 1 after the refusal message if c0, c1 (the first two bytes of `name`; EOF where there is none) are the gzip magic */
 int gt4_cli_refuse_gzip (const char *name, int c0, int c1);
 
+/* bytes of the sequence name that starts at `name_pos` of the `size` bytes of a FastA / FastQ file: up to the first byte
+ * <= ' ' or the end of the file; 0 where name_pos lies behind the file */
+uint64_t gt4_cli_name_length (const unsigned char *data, uint64_t size, uint64_t name_pos);
+
 /* Device list (NULL with n_words 0: a header alone) -> "<final_name>.tmp" -> rename.  `prefix` ("Error: " or "") goes
  * before the two messages the reference words differently per tool: "Cannot create output file", "Cannot rename".
  * 0: written and renamed; 1: failed after a message, no temporary left; 2: written, the rename failed (message

@@ -32,7 +32,19 @@
  *     Everything else fails without a usable GPU: there is no CPU path;
  *   - the list must fit one device (as for glistcompare -mm); larger is an out-of-memory error;
  *   - --words-only (not in the reference) prints the packed query words -q / -f / -s / -l would look up,
- *     one decimal number per line, and opens no device: for tests of the parsers.
+ *     one decimal number per line, and opens no device: for tests of the parsers;
+ *   - -s FILE --per_sequence [--min_hits H] (not in the reference) prints one line per sequence of FILE, in file order:
+ *     NAME, the number of its words, the number of those that hit, and the sum of the hits' values (64 bits), tab-separated.
+ *     A word's value is what -s looks up for it under the same -mm / -p; it is a hit when max (-min, 1) <= value <= -max:
+ *     the lines the reference prints for that sequence alone with `-min max (A, 1) -max B`.  NAME runs from behind the tag to
+ *     the first byte <= ' '.  --min_hits H keeps the sequences with at least H hits.  The file is mapped and goes through the
+ *     device in pieces of GT4HIP_QUERY_CHUNK=<bytes>[K|M|G] (default: 1/64 of the free device memory, 1 MiB to 1 GiB), cut
+ *     anywhere: the reader, the lookups and the sums per sequence run there (gt4hip_query_profile_text) and a sequence is
+ *     printed when the next one begins.  After a reader error the sequences read so far are printed with the words in
+ *     front of the error, as -s prints those words, then the reader's message; the exit status is -s's.  Refused with one
+ *     "Error:" line and exit 1 in front of any device: --per_sequence without -s, with another query or a statistics
+ *     option, with --all or --locations, with more than one list; --min_hits without --per_sequence.  -h stays the
+ *     reference's usage screen byte for byte (it is a golden transcript): these two options are described here and in README.md.
  * With --locations the queries go through gt4hip_query_lookup_locations, batch by batch: every hit is printed as
  * WORD, count, REVERSE and one line per location (search_one_word / cb_print / print_index_info, :469-476, :528-568).
  * REVERSE is the reference's sticky flag: set by the first query whose reverse complement is the smaller word and never
@@ -73,7 +85,7 @@ enum { CMD_QUERY, CMD_STATS, CMD_GC, CMD_MEDIAN, CMD_DISTRO, CMD_FILES, CMD_SEQU
 
 enum { OPT_VERSION, OPT_HELP, OPT_SEQFILE, OPT_LISTFILE, OPT_QUERYFILE, OPT_QUERY, OPT_PM, OPT_MM, OPT_MIN, OPT_MAX, OPT_DEBUG, OPT_ALL,
        OPT_STATS, OPT_MEDIAN, OPT_DISTRO, OPT_GC, OPT_FILES, OPT_SEQUENCES, OPT_LOCATIONS, OPT_3P, OPT_5P, OPT_HEADER, OPT_BLOOM,
-       OPT_IS_UNION, OPT_NOSCOUTS, OPT_WORDS_ONLY };
+       OPT_IS_UNION, OPT_NOSCOUTS, OPT_WORDS_ONLY, OPT_PER_SEQUENCE, OPT_MIN_HITS };
 
 static const GT4CliOption OPTIONS[] = {
   { "-v", OPT_VERSION }, { "--version", OPT_VERSION }, { "-h", OPT_HELP }, { "--help", OPT_HELP }, { "-?", OPT_HELP },
@@ -87,6 +99,7 @@ static const GT4CliOption OPTIONS[] = {
   { "--3p", OPT_3P }, { "--5p", OPT_5P }, { "--header", OPT_HEADER }, { "--bloom", OPT_BLOOM }, { "--is_union", OPT_IS_UNION },
   { "--disable_scouts", OPT_NOSCOUTS },
   { "--words-only", OPT_WORDS_ONLY }, /* not in the reference: print the parsed query words, no device */
+  { "--per_sequence", OPT_PER_SEQUENCE }, { "--min_hits", OPT_MIN_HITS }, /* not in the reference: -s, summed per sequence */
 };
 
 static const char *const HELP_LINES[] = {
@@ -123,6 +136,8 @@ typedef struct {
   const char *querystring, *queryfilename, *seqfilename, *querylistfilename;
   unsigned int nmm, pm3, minfreq, maxfreq, distro, command;
   int printall, print_header, locations, is_union, use_3p, use_5p, words_only, debug;
+  int per_sequence, have_min_hits; /* --per_sequence, --min_hits H */
+  uint64_t min_hits;
 } Options;
 
 static void print_help (int exit_value)
@@ -784,6 +799,20 @@ static void parse_argv (int argc, const char *argv[], Options *o)
     case OPT_NOSCOUTS: break; /* accepted and ignored */
     case OPT_IS_UNION: o->is_union = 1; break;
     case OPT_WORDS_ONLY: o->words_only = 1; break;
+    case OPT_PER_SEQUENCE: o->per_sequence = 1; break;
+    case OPT_MIN_HITS:
+      argidx += 1;
+      if (argidx >= argc || !argv[argidx][0] || argv[argidx][0] == '-') {
+        fprintf (stderr, "Error: --min_hits needs a number\n");
+        exit (1);
+      }
+      o->min_hits = strtoull (argv[argidx], &end, 10);
+      if (*end) {
+        fprintf (stderr, "Error: Invalid number of hits: %s\n", argv[argidx]);
+        exit (1);
+      }
+      o->have_min_hits = 1;
+      break;
     default:
       if (arg[0] != '-') {
         if (o->n_lists == MAX_LISTS) {
@@ -805,6 +834,27 @@ static void validate (const Options *o)
     fprintf (stderr, "No list/index files specified!\n");
     print_help (1);
   }
+  /* --per_sequence stands with -s alone; one line, in front of every file and device */
+  const char *with = NULL;
+  if (o->have_min_hits && !o->per_sequence) {
+    fprintf (stderr, "Error: --min_hits needs --per_sequence\n");
+    exit (1);
+  }
+  if (!o->per_sequence) return;
+  if (o->querystring) with = "-q";
+  else if (o->queryfilename) with = "-f";
+  else if (o->querylistfilename) with = "-l";
+  else if (o->printall) with = "--all";
+  else if (o->locations) with = "--locations";
+  else if (o->command == CMD_FILES) with = "--files";
+  else if (o->command == CMD_SEQUENCES) with = "--sequences";
+  else if (o->command != CMD_QUERY) with = "the statistics options";
+  else if (o->words_only) with = "--words-only";
+  if (with) fprintf (stderr, "Error: --per_sequence cannot be combined with %s\n", with);
+  else if (!o->seqfilename) fprintf (stderr, "Error: --per_sequence needs a sequence file (-s)\n");
+  else if (o->n_lists != 1) fprintf (stderr, "Error: --per_sequence takes one list or index, %u were given\n", o->n_lists);
+  else return;
+  exit (1);
 }
 
 /* what needs an index, checked behind open_inputs and in front of every device */
@@ -1110,6 +1160,179 @@ static int run_lookups (const Options *o, unsigned int wlen, const Input *index,
   return v;
 }
 
+/* ------------------------------------------------------------------ -s FILE --per_sequence */
+
+/* the sequence whose line is still to come: its words may go on in the next piece */
+typedef struct {
+  const Options *o;
+  const unsigned char *data; /* the mapped file */
+  uint64_t size;
+  int have;
+  uint64_t name_pos;
+  gt4hip_seq_profile sum;
+} PendingSequence;
+
+static void pending_print (PendingSequence *p)
+{
+  if (!p->have) return;
+  p->have = 0;
+  if (p->sum.n_hits < p->o->min_hits) return;
+  fwrite (p->data + p->name_pos, 1, gt4_cli_name_length (p->data, p->size, p->name_pos), stdout);
+  fprintf (stdout, "\t%llu\t%llu\t%llu\n", (unsigned long long) p->sum.n_words, (unsigned long long) p->sum.n_hits, (unsigned long long) p->sum.sum);
+}
+
+/* the reference's line for a reader error (src/fasta.c:136, :202, :211, :277), as search_fasta prints them */
+static void print_reader_error (const char *fname, const unsigned char *data, uint64_t size, uint32_t kind, uint64_t at)
+{
+  const int found = at < size ? data[at] : 0;
+  const unsigned long long cpos = at ? at - 1 : 0;
+  switch (kind) {
+    case GT4HIP_MAKER_ERR_START: fprintf (stderr, "fasta_reader_read_nwords: Reader %s invalid start tag '%c'\n", fname, found); break;
+    case GT4HIP_MAKER_ERR_PLUS: fprintf (stderr, "fasta_reader_read_nwords: Reader %s tag '+' missing, found '%c' instead at %llu\n", fname, found, cpos); break;
+    case GT4HIP_MAKER_ERR_AT: fprintf (stderr, "fasta_reader_read_nwords: Reader %s tag '@' missing, found '%c' instead at %llu\n", fname, found, cpos); break;
+    default: fprintf (stderr, "fasta_reader_read_nwords: Reader %s invalid character '%c' after '+' %llu\n", fname, found, (unsigned long long) at); break;
+  }
+}
+
+/* One piece through gt4hip_query_profile_text, its sums into `pend` and onto stdout.  0, or the library's code with the
+ * reader's error in next->reader.error and its offset in the piece in *at; `prof` grows to what a piece needs. */
+static int profile_piece (gt4hip_context *ctx, gt4hip_query_index *qindex, const Options *o, const unsigned char *text, size_t len, const gt4hip_locations_carry *carry,
+                          gt4hip_locations_carry *next, gt4hip_seq_profile **prof, uint64_t *prof_cap, PendingSequence *pend, uint64_t *at, uint64_t *n_words)
+{
+  const gt4hip_query_params prm = { .n_mm = o->nmm, .pm_3 = o->pm3, .canonize = 1 };
+  const uint32_t lo = o->minfreq > 1 ? o->minfreq : 1;
+  gt4hip_locations_piece piece;
+  uint64_t n = 0;
+  int rc = gt4hip_query_profile_text (ctx, qindex, text, len, 0, &prm, lo, o->maxfreq, carry, next, &piece, *prof, *prof_cap, &n, at);
+  if (!rc && n > *prof_cap) {
+    free (*prof);
+    *prof_cap = n + n / 2;
+    *prof = (gt4hip_seq_profile *) or_oom (malloc ((size_t) *prof_cap * sizeof **prof), "%llu sequences of one piece", (unsigned long long) n);
+    rc = gt4hip_query_profile_text (ctx, qindex, text, len, 0, &prm, lo, o->maxfreq, carry, next, &piece, *prof, *prof_cap, &n, at);
+  }
+  if (rc) return rc;
+  uint64_t e = 0;
+  if (carry && carry->seq_open) {
+    pend->sum.n_words += (*prof)[0].n_words, pend->sum.n_hits += (*prof)[0].n_hits, pend->sum.sum += (*prof)[0].sum;
+    e = 1;
+  }
+  for (uint64_t i = 0; i < piece.n_subseqs; i++) {
+    pending_print (pend);
+    pend->have = 1;
+    pend->name_pos = piece.subseqs[i].name_pos;
+    pend->sum = (*prof)[e + i];
+  }
+  *n_words = piece.n_words;
+  return GT4HIP_OK;
+}
+
+static int run_per_sequence (const Options *o)
+{
+  const char *fname = o->seqfilename;
+  int device = 0, verbose = 0;
+  gt4_cli_read_environment (&device, &verbose);
+  struct stat st;
+  const int fd = open (fname, O_RDONLY);
+  if (fd < 0 || fstat (fd, &st)) {
+    fprintf (stderr, "search_fasta: Cannot open %s\n", fname);
+    if (fd >= 0) close (fd);
+    return 1;
+  }
+  const uint64_t size = (uint64_t) st.st_size;
+  const unsigned char *data = NULL;
+  if (size) {
+    void *m = mmap (NULL, (size_t) size, PROT_READ, MAP_PRIVATE, fd, 0);
+    if (m == MAP_FAILED) {
+      fprintf (stderr, "Error: cannot map %s: %s\n", fname, strerror (errno));
+      close (fd);
+      return 1;
+    }
+    data = (const unsigned char *) m;
+  }
+  close (fd);
+  if (gt4_cli_refuse_gzip (fname, size > 0 ? data[0] : EOF, size > 1 ? data[1] : EOF)) return 1;
+  if (!size) return 0;
+  gt4hip_context *ctx = NULL;
+  const gt4hip_list *dev = NULL;
+  gt4hip_query_index *qindex = NULL;
+  GT4HipWordList *l = to_device (o->lists[0], &ctx, &dev);
+  CHK (ctx, gt4hip_query_index_create (ctx, dev, &qindex));
+  uint64_t chunk = gt4_cli_parse_bytes (getenv ("GT4HIP_QUERY_CHUNK"));
+  if (!chunk) {
+    uint64_t free_b = 0, total_b = 0;
+    CHK (ctx, gt4hip_device_memory (ctx, &free_b, &total_b));
+    chunk = free_b / 64;
+    if (chunk > (1ull << 30)) chunk = 1ull << 30;
+    if (chunk < (1ull << 20)) chunk = 1ull << 20;
+  }
+  if (verbose) fprintf (stderr, "Device: %s; pieces of %llu bytes\n", gt4hip_device_info (ctx), (unsigned long long) chunk);
+  PendingSequence pend = { .o = o, .data = data, .size = size };
+  gt4hip_locations_carry carry, next;
+  gt4hip_seq_profile *prof = NULL;
+  uint64_t prof_cap = 0, pos = 0;
+  unsigned int pieces = 0;
+  int have = 0, result = 0;
+  double profile_ms = 0, reader_ms = 0;
+  while (pos < size) {
+    size_t len = (size_t) (size - pos);
+    if (len > chunk) {
+      len = (size_t) chunk;
+      /* behind the last '\n' of the chunk's second half, where there is one */
+      const unsigned char *nl = (const unsigned char *) memrchr (data + pos + len / 2, '\n', len - len / 2);
+      if (nl) len = (size_t) (nl - (data + pos)) + 1;
+    }
+    uint64_t at = 0, n_words = 0, us = 0;
+    int rc = profile_piece (ctx, qindex, o, data + pos, len, have ? &carry : NULL, &next, &prof, &prof_cap, &pend, &at, &n_words);
+    if (rc == GT4HIP_EFORMAT) {
+      /* the words in front of the error count, as -s looks them up: the piece again, up to the offending byte */
+      const uint32_t kind = next.reader.error;
+      uint64_t none = 0;
+      if (at && (rc = profile_piece (ctx, qindex, o, data + pos, (size_t) at, have ? &carry : NULL, &next, &prof, &prof_cap, &pend, &none, &n_words))) {
+        fprintf (stderr, "Error: %s\n", gt4hip_last_error (ctx));
+        exit (1);
+      }
+      pending_print (&pend);
+      fflush (stdout);
+      print_reader_error (fname, data, size, kind, pos + at);
+      result = -1;
+      break;
+    }
+    if (rc) {
+      fflush (stdout);
+      fprintf (stderr, "Error: %s\n", gt4hip_last_error (ctx));
+      exit (1);
+    }
+    carry = next;
+    have = 1;
+    pos += len;
+    pieces++;
+    if (verbose) {
+      const double ms = gt4hip_query_index_last_ms (qindex);
+      gt4hip_get_counter (ctx, "extract_us", &us);
+      profile_ms += ms, reader_ms += us / 1000.0;
+      fprintf (stderr, "%s: piece %u ends at byte %llu: %llu words, reader %.3f ms, lookups and sums %.3f ms\n", fname, pieces, (unsigned long long) pos,
+               (unsigned long long) n_words, us / 1000.0, ms);
+    }
+    if (carry.reader.ended) break;
+  }
+  if (!result) {
+    pending_print (&pend);
+    fflush (stdout);
+    /* the end of the file behind a FastQ sequence line or inside a '+' line (src/fasta.c:200-213) */
+    if (have && !carry.reader.ended && carry.reader.file_type == GT4HIP_MAKER_FASTQ && carry.reader.line_phase == 2) {
+      print_reader_error (fname, data, size, carry.reader.at_line_start ? GT4HIP_MAKER_ERR_PLUS : GT4HIP_MAKER_ERR_PLUS_EOF, size);
+      result = -1;
+    }
+  }
+  if (verbose) fprintf (stderr, "%s: %llu bytes in %u piece(s); reader %.3f ms, lookups and sums %.3f ms\n", fname, (unsigned long long) size, pieces, reader_ms, profile_ms);
+  free (prof);
+  gt4hip_locations_free (ctx);
+  gt4hip_query_index_free (qindex);
+  gt4_hip_word_list_delete (l);
+  munmap ((void *) data, (size_t) size);
+  return result;
+}
+
 int main (int argc, const char *argv[])
 {
   static Options o;
@@ -1133,6 +1356,7 @@ int main (int argc, const char *argv[])
     fprintf (stderr, "Error: Number of mismatches (%u) and 3' perfect match (%u) are longer than word length %u\n", o.nmm, o.pm3, wlen);
     return 1;
   }
+  if (o.per_sequence) return run_per_sequence (&o);
   if (!o.querystring && !o.queryfilename && !o.seqfilename && !o.nmm && !o.words_only && !o.locations) return run_zipper (&o, wlen);
   return run_lookups (&o, wlen, &maps[0], &query_input);
 }

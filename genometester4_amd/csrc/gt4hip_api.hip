@@ -224,6 +224,7 @@ extern "C" int gt4hip_get_counter (gt4hip_context *ctx, const char *name, uint64
   else if (!strcmp (name, "mm_threads")) *value = GT4HIP_MM_THREADS;
   else if (!strcmp (name, "mm_tile")) *value = (uint64_t) GT4HIP_MM_THREADS * GT4HIP_MM_ROUNDS;
   else if (!strcmp (name, "gather_tile")) *value = (uint64_t) GT4HIP_MM_THREADS * GT4HIP_GATHER_ROUNDS;
+  else if (!strcmp (name, "profile_tile")) *value = (uint64_t) GT4HIP_MM_THREADS * GT4HIP_PROFILE_ROUNDS;
   else if (!strcmp (name, "hist_lds_bins")) *value = GT4HIP_HIST_LDS_BINS;
   else if (!strcmp (name, "list_threads")) *value = GT4HIP_LIST_THREADS;
   else if (!strcmp (name, "caller_threads")) *value = GT4HIP_CALLER_THREADS;

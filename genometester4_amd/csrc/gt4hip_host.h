@@ -1,7 +1,7 @@
 /* gt4hip_host.h -- host-side internals shared by the C-ABI implementation files: the context and list objects, the
  * owners of a call's temporaries (TempLists, TempBlocks, TempTable), the grid size of the striding kernels, and what the
  * units of the library host (gt4hip_api.hip, gt4hip_pair.hip, gt4hip_multi.hip, gt4hip_table.hip, gt4hip_nway.hip) and
- * gt4hip_io / _comm / _sort / _maker / _mismatch / _query / _gmer / _subset / _select / _pairwise.hip call in one another. */
+ * gt4hip_io / _comm / _sort / _maker / _mismatch / _query / _seqprofile / _gmer / _subset / _select / _pairwise.hip call in one another. */
 #ifndef GT4HIP_HOST_H
 #define GT4HIP_HOST_H
 
@@ -248,6 +248,8 @@ void gt4hip_io_destroy (gt4hip_context *ctx);
 #define GT4HIP_MM_ROUNDS 8
 #define GT4HIP_GATHER_ROUNDS 8
 #define GT4HIP_HIST_LDS_BINS 4096u
+/* words per thread and tile of gt4hip_seqprofile.hip's kernel (counter "profile_tile": words per tile) */
+#define GT4HIP_PROFILE_ROUNDS 8
 #define GT4HIP_CALLER_THREADS 256
 #define GT4HIP_CALLER_MAX_GRID 1024
 #define GT4HIP_SORT_HIST_THREADS 256
@@ -269,6 +271,16 @@ GT4HIP_LOCAL int gt4hip_text_to_words_counted (gt4hip_context *ctx, const void *
 /* gt4hip_gmer.hip: k_mk_text_counts on the arrays of a reader call (text, tile states, codes, MakerInfo); out: three zeroed device words */
 GT4HIP_LOCAL void gt4hip_launch_text_counts (hipStream_t stream, int grid, bool fastq, const unsigned char *d_text, size_t n_bytes, uint64_t tiles,
                                              const uint32_t *tile_state, const unsigned char *codes, const void *info, unsigned long long *out);
+/* gt4hip_query.hip for gt4hip_seqprofile.hip.  The argument rules of the lookups (`who` in the message); the list an index
+ * was made of and its bucket offsets; the device time a call on the index reports (gt4hip_query_index_last_ms) */
+GT4HIP_LOCAL int gt4hip_query_check_params (gt4hip_context *ctx, const char *who, const gt4hip_query_index *qindex, const gt4hip_query_params *params);
+GT4HIP_LOCAL const gt4hip_list *gt4hip_query_index_list (const gt4hip_query_index *qindex);
+GT4HIP_LOCAL const uint64_t *gt4hip_query_index_offsets (const gt4hip_query_index *qindex);
+GT4HIP_LOCAL void gt4hip_query_index_set_ms (gt4hip_query_index *qindex, double ms);
+/* The kernels of gt4hip_query_lookup on n > 0 words in DEVICE memory, enqueued on the context's stream and not waited for:
+ * d_values[i] (and d_found[i]; may be NULL where n_mm > 0) as gt4hip_query_lookup defines them.  Sets counter "query_wide". */
+GT4HIP_LOCAL int gt4hip_query_lookup_device (gt4hip_context *ctx, const char *who, gt4hip_query_index *qindex, const gt4hip_query_params *params,
+                                             const uint64_t *d_words, uint64_t n, uint32_t *d_values, unsigned char *d_found);
 int gt4hip_io_download (gt4hip_context *ctx, const void *dev, void *host, size_t bytes);
 /* host memory (a file mapping, say) -> device memory, waited for: large extents in pieces through the staging threads */
 int gt4hip_io_upload (gt4hip_context *ctx, const void *host, void *dev, size_t bytes);

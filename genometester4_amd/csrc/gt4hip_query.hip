@@ -569,6 +569,37 @@ extern "C" int gt4hip_query_variant_mask (uint32_t word_length, const gt4hip_que
   return GT4HIP_OK;
 }
 
+int gt4hip_query_check_params (gt4hip_context *ctx, const char *who, const gt4hip_query_index *qi, const gt4hip_query_params *prm) { return check_params (ctx, who, qi, prm); }
+const gt4hip_list *gt4hip_query_index_list (const gt4hip_query_index *qi) { return qi->list; }
+const uint64_t *gt4hip_query_index_offsets (const gt4hip_query_index *qi) { return (const uint64_t *) qi->ix.off; }
+void gt4hip_query_index_set_ms (gt4hip_query_index *qi, double ms) { qi->last_ms = ms; }
+
+int gt4hip_query_lookup_device (gt4hip_context *ctx, const char *who, gt4hip_query_index *qi, const gt4hip_query_params *prm, const uint64_t *d_words, uint64_t n,
+                                uint32_t *d_values, unsigned char *d_found)
+{
+  Query Q;
+  int rc;
+  if ((rc = fill_query (ctx, who, qi, prm, (const u64 *) d_words, n, &Q))) return rc;
+  ctx->query_wide = 0;
+  if (!prm->n_mm) {
+    hipLaunchKernelGGL (k_query_exact, dim3 (gt4hip_grid (ctx, n, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, Q.words, (u64) n, Q.ix, Q.k, Q.canonize, d_values,
+                        d_found);
+  } else {
+    HIPCHK (ctx, hipMemsetAsync (d_values, 0, n * 4, ctx->stream));
+    const int grid = gt4hip_grid (ctx, Q.total, MM_THREADS);
+    const u64 stride = (u64) grid * MM_THREADS;
+    Q.stride_w = stride / Q.n_var;
+    Q.stride_r = stride % Q.n_var;
+    ctx->query_wide = !(Q.n_var + stride < 0xffffffffull);
+    if (!ctx->query_wide) hipLaunchKernelGGL (k_query<false>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, Q, d_values);
+    else hipLaunchKernelGGL (k_query<true>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, Q, d_values);
+    HIPCHK (ctx, hipGetLastError ());
+    if (d_found) hipLaunchKernelGGL (k_query_found, dim3 (gt4hip_grid (ctx, n, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, (const u32 *) d_values, (u64) n, d_found);
+  }
+  HIPCHK (ctx, hipGetLastError ());
+  return GT4HIP_OK;
+}
+
 extern "C" int gt4hip_query_lookup (gt4hip_context *ctx, gt4hip_query_index *qi, const uint64_t *words, uint64_t n, const gt4hip_query_params *prm,
                                     uint32_t *values, uint8_t *found)
 {
@@ -584,29 +615,14 @@ extern "C" int gt4hip_query_lookup (gt4hip_context *ctx, gt4hip_query_index *qi,
   u32 *d_values = NULL;
   unsigned char *d_found = NULL;
   if ((rc = blk.get (ctx, n * 8, (void **) &d_words)) || (rc = blk.get (ctx, n * 4, (void **) &d_values)) || (rc = blk.get (ctx, n, (void **) &d_found))) return rc;
-  Query Q;
+  Query Q; /* (a batch that cannot be ranked is refused before anything is enqueued) */
   if ((rc = fill_query (ctx, "gt4hip_query_lookup", qi, prm, d_words, n, &Q))) return rc;
   Timer tm;
   HIPCHK (ctx, hipEventCreate (&tm.e0));
   HIPCHK (ctx, hipEventCreate (&tm.e1));
   HIPCHK (ctx, hipMemcpyAsync (d_words, words, n * 8, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK (ctx, hipEventRecord (tm.e0, ctx->stream));
-  if (!prm->n_mm) {
-    hipLaunchKernelGGL (k_query_exact, dim3 (gt4hip_grid (ctx, n, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, d_words, n, Q.ix, Q.k, Q.canonize, d_values,
-                        d_found);
-  } else {
-    HIPCHK (ctx, hipMemsetAsync (d_values, 0, n * 4, ctx->stream));
-    const int grid = gt4hip_grid (ctx, Q.total, MM_THREADS);
-    const u64 stride = (u64) grid * MM_THREADS;
-    Q.stride_w = stride / Q.n_var;
-    Q.stride_r = stride % Q.n_var;
-    ctx->query_wide = !(Q.n_var + stride < 0xffffffffull);
-    if (!ctx->query_wide) hipLaunchKernelGGL (k_query<false>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, Q, d_values);
-    else hipLaunchKernelGGL (k_query<true>, dim3 (grid), dim3 (MM_THREADS), 0, ctx->stream, Q, d_values);
-    HIPCHK (ctx, hipGetLastError ());
-    hipLaunchKernelGGL (k_query_found, dim3 (gt4hip_grid (ctx, n, MM_THREADS)), dim3 (MM_THREADS), 0, ctx->stream, d_values, n, d_found);
-  }
-  HIPCHK (ctx, hipGetLastError ());
+  if ((rc = gt4hip_query_lookup_device (ctx, "gt4hip_query_lookup", qi, prm, (const uint64_t *) d_words, n, d_values, d_found))) return rc;
   HIPCHK (ctx, hipEventRecord (tm.e1, ctx->stream));
   HIPCHK (ctx, hipMemcpyAsync (values, d_values, n * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK (ctx, hipMemcpyAsync (found, d_found, n, hipMemcpyDeviceToHost, ctx->stream));

@@ -642,6 +642,37 @@ int gt4hip_pack_locations (gt4hip_context *ctx, uint64_t *d_raw, uint64_t n, uin
 int gt4hip_pairs_reserve (gt4hip_context *ctx, uint64_t n_pairs, uint64_t **d_words, uint64_t **d_values);
 void gt4hip_pairs_release (gt4hip_context *ctx);
 
+/* ---------------------------------------------------------------- glistquery --per_sequence: the hits of every sequence of a text */
+
+/* The words of a text looked up in a list (gt4hip_query_index, above) and the results added up per sequence.
+ * value (w) is what gt4hip_query_lookup gives for the word (n_mm == 0: the stored count; n_mm > 0: the wrapping 32-bit sum
+ * over the variants found) and `found` its found; a word is a HIT when it is found and min_value <= value <= max_value.
+ * With n_mm == 0 an absent word is never a hit, also with min_value 0; a stored count of 0 is found.  n_hits counts the
+ * hits of a sequence, sum adds their values in 64 bits, n_words counts every word. */
+typedef struct { uint64_t n_words, n_hits, sum; } gt4hip_seq_profile;
+
+/* words and raw locations already on the device (what gt4hip_text_to_locations leaves): the words' ordinals
+ * (raw >> 33) ascend and lie in [first_ordinal, first_ordinal + n_seqs); profiles[s] (HOST, n_seqs entries) is
+ * SET to what the words of ordinal first_ordinal + s give; a sequence without words gives {0, 0, 0}.  The words are looked
+ * up as they stand (the reader's words are canonical); the word length is the index's list's.  Ordinals that descend or
+ * leave the range are GT4HIP_EINVAL: the kernel checks every ordinal before it addresses anything with it and raises one
+ * flag word.  The device holds 24 bytes per sequence for the call, with n_mm > 0 four more per word.  One kernel over tiles of
+ * "profile_tile" words: a tile adds to a sequence's three sums once, with 64-bit integer adds, so the
+ * result does not depend on the order; the sums are zeroed by a launch of the call.  gt4hip_query_index_last_ms: the call's kernels. */
+int gt4hip_query_profile_words (gt4hip_context *ctx, gt4hip_query_index *qindex, const uint64_t *d_words, const uint64_t *d_raw,
+                                uint64_t n_words, uint64_t first_ordinal, uint64_t n_seqs, const gt4hip_query_params *params,
+                                uint32_t min_value, uint32_t max_value, gt4hip_seq_profile *profiles);
+
+/* one piece of a file: gt4hip_text_to_locations into a block of the call, then the above.  Entry 0 is what the piece
+ * adds to the sequence left open by the piece before (only when in && in->seq_open); then one entry per sequence
+ * that begins in the piece (piece->n_subseqs).  *n_profiles is always set; the array is filled only when it fits `capacity`.
+ * `flags`: GT4HIP_MAKER_TEXT_ON_DEVICE.  The carry, `piece` (its records last as gt4hip_text_to_locations says), the errors
+ * of the text and the reader's limits are gt4hip_text_to_locations's.  The device holds 16 bytes per byte of the piece. */
+int gt4hip_query_profile_text (gt4hip_context *ctx, gt4hip_query_index *qindex, const void *text, size_t n_bytes, unsigned flags,
+                               const gt4hip_query_params *params, uint32_t min_value, uint32_t max_value,
+                               const gt4hip_locations_carry *in, gt4hip_locations_carry *out, gt4hip_locations_piece *piece,
+                               gt4hip_seq_profile *profiles, uint64_t capacity, uint64_t *n_profiles, uint64_t *error_offset);
+
 /* ---------------------------------------------------------------- gmer_counter: database k-mers counted in reads */
 
 /* A k-mer database resident in HBM (reference src/database.c, src/gmer_counter.c:751-815, without the trie): the
@@ -780,7 +811,7 @@ int gt4hip_synchronize (gt4hip_context *ctx);
  *   "select_vec" = 0 / -1  gt4hip_table_select reads rows of a multiple of four counts (in 16-byte aligned arrays) 16 bytes
  *                      per lane / every row a dword per lane, as all other rows are read (bench, tests)
  *   "grid_cap" = n     (tests) every kernel that walks its work in a loop stepping by its grid -- items, tiles or segments:
- *                      the query, mismatch, maker, gmer, subset, select, pairwise and caller kernels, the radix sort's
+ *                      the query, per-sequence profile, mismatch, maker, gmer, subset, select, pairwise and caller kernels, the radix sort's
  *                      histogram, the list utilities -- is launched with n workgroups at most, so that small inputs take the
  *                      second and later trips of those loops; 0 (default): the built-in caps alone.  Results do not change.
  *                      Not followed by kernels launched one workgroup per tile or whose workgroups wait for one another
@@ -814,7 +845,8 @@ int gt4hip_set_option (gt4hip_context *ctx, const char *name, int64_t value);
  * work with fewer workgroups than blocks of work (by option "grid_cap" or by a built-in cap): the loops of those took a second
  * trip.  Sizes the tests build their inputs from: "mm_threads": items per block of work of the item loops of the query,
  * mismatch and gmer kernels (a quarter of the records per block of the list statistics); "mm_tile": items per tile of the
- * hit and compaction passes; "gather_tile": locations per tile of gt4hip_query_lookup_locations' gather; "hist_lds_bins": the
+ * hit and compaction passes; "profile_tile": words per tile of gt4hip_query_profile_words' kernel (its sums are zeroed in blocks of
+ * "mm_threads" words, three per sequence and one more); "gather_tile": locations per tile of gt4hip_query_lookup_locations' gather; "hist_lds_bins": the
  * most bins gt4hip_list_count_histogram keeps in LDS; "list_threads": records per block of gt4hip_generate, _list_sum_counts,
  * _list_is_sorted, _list_upload_index and the count table's column kernels; "sort_hist_chunk": words per block of the
  * radix sort's histogram; "select_segment": rows per segment of a contiguous count table; "subset_scan_tile": elements per tile of
