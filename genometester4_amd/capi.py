@@ -99,6 +99,15 @@ class SeqProfile(C.Structure):
 SEQ_PROFILE_DTYPE = np.dtype([("n_words", "<u8"), ("n_hits", "<u8"), ("sum", "<u8")])
 
 
+class MaskPiece(C.Structure):
+    """gt4hip_mask_piece: words that end in a piece, the hits among them, the piece's own covered bases, and how many of the
+    last bytes >= ' ' in front of the piece a hit word of it covers"""
+    _fields_ = [("n_words", C.c_uint64), ("n_hits", C.c_uint64), ("n_covered", C.c_uint64), ("back", C.c_uint32), ("pad", C.c_uint32)]
+
+
+MASK_SOFT = 4  # GT4HIP_MASK_SOFT
+
+
 class IndexArrays(C.Structure):
     _fields_ = [("n_kmers", C.c_uint64), ("n_locations", C.c_uint64), ("n_values", C.c_uint64),
                 ("d_kmers", C.c_void_p), ("d_locations", C.c_void_p)]
@@ -143,7 +152,7 @@ SYMBOLS = [
     "gt4hip_sort_pairs", "gt4hip_pairs_to_index", "gt4hip_index_free",
     "gt4hip_list_subset", "gt4hip_subset_state_at",
     "gt4hip_text_to_locations", "gt4hip_locations_free", "gt4hip_pack_locations", "gt4hip_pairs_reserve", "gt4hip_pairs_release",
-    "gt4hip_query_profile_words", "gt4hip_query_profile_text",
+    "gt4hip_query_profile_words", "gt4hip_query_profile_text", "gt4hip_query_mask_text",
     "gt4hip_pair_partition",
     "gt4hip_gmer_db_create", "gt4hip_gmer_db_free", "gt4hip_gmer_db_n_kmers", "gt4hip_gmer_db_last_ms", "gt4hip_gmer_count_words",
     "gt4hip_gmer_count_text", "gt4hip_gmer_counts_download", "gt4hip_gmer_counts_reset",
@@ -263,6 +272,8 @@ def lib():
             "gt4hip_query_profile_words": (C.c_int, [vp, vp, vp, vp, u64, u64, u64, C.POINTER(QueryParams), u32, u32, vp]),
             "gt4hip_query_profile_text": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_uint, C.POINTER(QueryParams), u32, u32, C.POINTER(LocationsCarry),
                                                     C.POINTER(LocationsCarry), C.POINTER(LocationsPiece), vp, u64, C.POINTER(u64), C.POINTER(u64)]),
+            "gt4hip_query_mask_text": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_uint, C.POINTER(QueryParams), u32, u32, C.c_ubyte, C.POINTER(MakerCarry),
+                                                 C.POINTER(MakerCarry), vp, C.POINTER(MaskPiece), C.POINTER(u64)]),
             "gt4hip_list_subset": (C.c_int, [vp, vp, C.POINTER(SubsetParams), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]),
             "gt4hip_subset_state_at": (u64, [u64, u64]),
             "gt4hip_pair_partition": (C.c_int, [vp, vp, vp, u64, vp]),
@@ -851,6 +862,37 @@ class Context:
             return (np.concatenate(prof) if prof else np.zeros(0, dtype=SEQ_PROFILE_DTYPE)), [[int(x) for x in r] for a in subs for r in a]
         finally:
             lib().gt4hip_locations_free(self.h)
+
+    def query_mask_text(self, qindex, pieces, n_mm=0, pm_3=0, lo=1, hi=0xFFFFFFFF, soft=False, mask_byte=b"N"):
+        """The pieces of one file, in order -> (the whole text with every covered base replaced, one record
+        {"n_words", "n_hits", "n_covered", "back"} per piece) (gt4hip_query_mask_text, one call per piece, the carry handed
+        on).  A piece's `back` is applied here: the last `back` bytes >= ' ' of the text in front of the piece are replaced
+        as the library replaces the piece's own.  Malformed text raises Gt4HipError with `error_offset` (in the piece) and
+        `kind`."""
+        prm = QueryParams(n_mm, pm_3, 1)
+        carry, done, recs = None, bytearray(), []
+        for p in pieces:
+            out, piece, err = MakerCarry(), MaskPiece(), C.c_uint64()
+            buf = (C.c_char * max(len(p), 1)).from_buffer_copy(bytes(p) or b"\0")
+            got = (C.c_char * max(len(p), 1))()
+            rc = lib().gt4hip_query_mask_text(self.h, qindex.h, buf, len(p), MASK_SOFT if soft else 0, C.byref(prm), lo, hi, mask_byte[0],
+                                              C.byref(carry) if carry is not None else None, C.byref(out), got, C.byref(piece), C.byref(err))
+            if rc:
+                e = Gt4HipError(rc, lib().gt4hip_last_error(self.h).decode())
+                e.error_offset, e.kind = err.value, out.error
+                raise e
+            i, left = len(done), piece.back
+            while left:
+                i -= 1
+                if i < 0:
+                    raise Gt4HipError(EINVAL, "gt4hip_query_mask_text: back = %d reaches in front of the text" % piece.back)
+                if done[i] >= 32:
+                    done[i] = (done[i] | 0x20) if soft else mask_byte[0]
+                    left -= 1
+            done += got.raw[:len(p)]
+            recs.append({"n_words": piece.n_words, "n_hits": piece.n_hits, "n_covered": piece.n_covered, "back": piece.back})
+            carry = out
+        return bytes(done), recs
 
     def pack_locations(self, raw_ptr, n, file, subseq_bits, pos_bits):
         """n raw locations of file number `file` (device memory) -> location words, in place (gt4hip_pack_locations)."""

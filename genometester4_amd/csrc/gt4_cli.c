@@ -59,6 +59,76 @@ uint64_t gt4_cli_name_length (const unsigned char *data, uint64_t size, uint64_t
   return len;
 }
 
+void gt4_mask_tail_init (GT4MaskTail *t, int soft, unsigned char mask_byte, GT4MaskWrite write, void *arg)
+{
+  memset (t, 0, sizeof *t);
+  t->soft = soft, t->mask_byte = mask_byte, t->write = write, t->arg = arg;
+}
+
+/* where the tail to hold begins in b[0 .. n): at the (k - 1)-th last byte >= ' '; n when k is 1; (size_t) -1 when b holds
+ * fewer (*seen: how many it holds) */
+static size_t mask_hold_point (const unsigned char *b, size_t n, unsigned int want, unsigned int *seen)
+{
+  size_t i = n;
+  *seen = 0;
+  if (!want) return n;
+  while (i) {
+    i--;
+    if (b[i] >= ' ' && ++*seen == want) return i;
+  }
+  return (size_t) -1;
+}
+
+static int mask_tail_keep (GT4MaskTail *t, const unsigned char *bytes, size_t n, int append)
+{
+  const size_t at = append ? t->n : 0;
+  if (n > (size_t) -1 - at) return 1;
+  if (at + n > t->cap) {
+    const size_t cap = at + n + (at + n) / 2 + 64;
+    unsigned char *h = (unsigned char *) realloc (t->held, cap > at + n ? cap : at + n);
+    if (!h) return 1;
+    t->held = h, t->cap = cap > at + n ? cap : at + n;
+  }
+  if (n) memmove (t->held + at, bytes, n); /* (bytes may lie in t->held) */
+  t->n = at + n;
+  return 0;
+}
+
+int gt4_mask_tail_push (GT4MaskTail *t, const unsigned char *masked, size_t len, unsigned int back, unsigned int k)
+{
+  size_t i = t->n;
+  while (back) {
+    if (!i) return 1;
+    i--;
+    if (t->held[i] >= ' ') {
+      t->held[i] = t->soft ? (unsigned char) (t->held[i] | 0x20) : t->mask_byte;
+      back--;
+    }
+  }
+  const unsigned int want = k ? k - 1 : 0;
+  unsigned int in_piece = 0, in_tail = 0;
+  size_t hold = mask_hold_point (masked, len, want, &in_piece);
+  if (hold != (size_t) -1) { /* the piece alone holds the new tail: the old one and the piece's front go out */
+    if (t->n && t->write (t->held, t->n, t->arg)) return 1;
+    if (hold && t->write (masked, hold, t->arg)) return 1;
+    return mask_tail_keep (t, masked + hold, len - hold, 0);
+  }
+  hold = mask_hold_point (t->held, t->n, want - in_piece, &in_tail);
+  if (hold != (size_t) -1 && hold) {
+    if (t->write (t->held, hold, t->arg)) return 1;
+    if (mask_tail_keep (t, t->held + hold, t->n - hold, 0)) return 1;
+  }
+  return mask_tail_keep (t, masked, len, 1);
+}
+
+int gt4_mask_tail_finish (GT4MaskTail *t)
+{
+  const int failed = t->n && t->write (t->held, t->n, t->arg);
+  free (t->held);
+  t->held = NULL, t->n = t->cap = 0;
+  return failed;
+}
+
 int gt4_cli_write_list_file (gt4hip_context *ctx, const gt4hip_list *list, unsigned int word_length, uint64_t n_words, uint64_t total_count,
                              const char *final_name, unsigned int mode, const char *prefix)
 {

@@ -37,6 +37,25 @@ int gt4_cli_refuse_gzip (const char *name, int c0, int c1);
  * <= ' ' or the end of the file; 0 where name_pos lies behind the file */
 uint64_t gt4_cli_name_length (const unsigned char *data, uint64_t size, uint64_t name_pos);
 
+/* glistquery --mask writes a stream, and a hit word of the next piece may still cover the end of what has been masked so
+ * far: the tail from the (k - 1)-th last byte >= ' ' on is held back.  push: the last `back` bytes >= ' ' of the held tail are
+ * replaced (by mask_byte, soft: by byte | 0x20), the piece's masked bytes follow them, and everything in front of the new hold
+ * point goes to `write`.  With k = 1 nothing is ever held; a run of bytes < ' ' of any length is held with the bases in front
+ * of it.  finish writes what is held.  Both return 0, or 1 when `write` failed (returned non-zero), memory ran out or
+ * `back` reaches in front of the held tail; the unit calls nothing but `write`, malloc and free. */
+typedef int (*GT4MaskWrite) (const void *bytes, size_t n, void *arg);
+typedef struct {
+  unsigned char *held;
+  size_t n, cap;
+  GT4MaskWrite write;
+  void *arg;
+  int soft;
+  unsigned char mask_byte;
+} GT4MaskTail;
+void gt4_mask_tail_init (GT4MaskTail *t, int soft, unsigned char mask_byte, GT4MaskWrite write, void *arg);
+int gt4_mask_tail_push (GT4MaskTail *t, const unsigned char *masked, size_t len, unsigned int back, unsigned int k);
+int gt4_mask_tail_finish (GT4MaskTail *t);
+
 /* Device list (NULL with n_words 0: a header alone) -> "<final_name>.tmp" -> rename.  `prefix` ("Error: " or "") goes
  * before the two messages the reference words differently per tool: "Cannot create output file", "Cannot rename".
  * 0: written and renamed; 1: failed after a message, no temporary left; 2: written, the rename failed (message

@@ -45,6 +45,18 @@
  *     "Error:" line and exit 1 in front of any device: --per_sequence without -s, with another query or a statistics
  *     option, with --all or --locations, with more than one list; --min_hits without --per_sequence.  -h stays the
  *     reference's usage screen byte for byte (it is a golden transcript): these two options are described here and in README.md.
+ *   - -s FILE --mask [--soft_mask] (not in the reference; its authors' stub is src/gmasker.c) writes FILE to stdout byte for byte,
+ *     except that every base that lies inside a word of the list is written as N, with --soft_mask as its lower-case letter
+ *     (U becomes u, a lower-case base stays).  The words are -s's, a word counts when max (-min, 1) <= value <= -max under the
+ *     same -mm / -p (--per_sequence's rule), and a base is covered when it is one of the k bases of such a word.  Names, '+' and
+ *     quality lines, '\r', control and high bytes and runs shorter than k stay as they are; so does everything from a NUL
+ *     on.  The file goes through the device in pieces of GT4HIP_QUERY_CHUNK as for --per_sequence (gt4hip_query_mask_text);
+ *     the output is a stream, so the tail a later piece may still cover -- from the (k - 1)-th last byte >= ' ' on -- is held
+ *     back (GT4MaskTail, gt4_cli.c) and the result does not depend on where the cuts fall.  After a reader error stdout holds the
+ *     masked bytes in front of the offending byte, then comes the reader's message and -s's exit status.  Refused with one
+ *     "Error:" line and exit 1 in front of any device: --mask without -s, with -q / -f / -l, --all, --locations, --files,
+ *     --sequences, --per_sequence, --min_hits or a statistics option, with more than one list, with a gzip file; --soft_mask
+ *     without --mask.  Neither option is on the -h screen.
  * With --locations the queries go through gt4hip_query_lookup_locations, batch by batch: every hit is printed as
  * WORD, count, REVERSE and one line per location (search_one_word / cb_print / print_index_info, :469-476, :528-568).
  * REVERSE is the reference's sticky flag: set by the first query whose reverse complement is the smaller word and never
@@ -85,7 +97,7 @@ enum { CMD_QUERY, CMD_STATS, CMD_GC, CMD_MEDIAN, CMD_DISTRO, CMD_FILES, CMD_SEQU
 
 enum { OPT_VERSION, OPT_HELP, OPT_SEQFILE, OPT_LISTFILE, OPT_QUERYFILE, OPT_QUERY, OPT_PM, OPT_MM, OPT_MIN, OPT_MAX, OPT_DEBUG, OPT_ALL,
        OPT_STATS, OPT_MEDIAN, OPT_DISTRO, OPT_GC, OPT_FILES, OPT_SEQUENCES, OPT_LOCATIONS, OPT_3P, OPT_5P, OPT_HEADER, OPT_BLOOM,
-       OPT_IS_UNION, OPT_NOSCOUTS, OPT_WORDS_ONLY, OPT_PER_SEQUENCE, OPT_MIN_HITS };
+       OPT_IS_UNION, OPT_NOSCOUTS, OPT_WORDS_ONLY, OPT_PER_SEQUENCE, OPT_MIN_HITS, OPT_MASK, OPT_SOFT_MASK };
 
 static const GT4CliOption OPTIONS[] = {
   { "-v", OPT_VERSION }, { "--version", OPT_VERSION }, { "-h", OPT_HELP }, { "--help", OPT_HELP }, { "-?", OPT_HELP },
@@ -100,6 +112,7 @@ static const GT4CliOption OPTIONS[] = {
   { "--disable_scouts", OPT_NOSCOUTS },
   { "--words-only", OPT_WORDS_ONLY }, /* not in the reference: print the parsed query words, no device */
   { "--per_sequence", OPT_PER_SEQUENCE }, { "--min_hits", OPT_MIN_HITS }, /* not in the reference: -s, summed per sequence */
+  { "--mask", OPT_MASK }, { "--soft_mask", OPT_SOFT_MASK },               /* not in the reference: -s, the covered bases masked */
 };
 
 static const char *const HELP_LINES[] = {
@@ -137,6 +150,7 @@ typedef struct {
   unsigned int nmm, pm3, minfreq, maxfreq, distro, command;
   int printall, print_header, locations, is_union, use_3p, use_5p, words_only, debug;
   int per_sequence, have_min_hits; /* --per_sequence, --min_hits H */
+  int mask, soft_mask;             /* --mask, --soft_mask */
   uint64_t min_hits;
 } Options;
 
@@ -800,6 +814,8 @@ static void parse_argv (int argc, const char *argv[], Options *o)
     case OPT_IS_UNION: o->is_union = 1; break;
     case OPT_WORDS_ONLY: o->words_only = 1; break;
     case OPT_PER_SEQUENCE: o->per_sequence = 1; break;
+    case OPT_MASK: o->mask = 1; break;
+    case OPT_SOFT_MASK: o->soft_mask = 1; break;
     case OPT_MIN_HITS:
       argidx += 1;
       if (argidx >= argc || !argv[argidx][0] || argv[argidx][0] == '-') {
@@ -834,14 +850,19 @@ static void validate (const Options *o)
     fprintf (stderr, "No list/index files specified!\n");
     print_help (1);
   }
-  /* --per_sequence stands with -s alone; one line, in front of every file and device */
-  const char *with = NULL;
-  if (o->have_min_hits && !o->per_sequence) {
-    fprintf (stderr, "Error: --min_hits needs --per_sequence\n");
+  /* --mask and --per_sequence stand with -s alone; one line, in front of every file and device */
+  const char *with = NULL, *what = o->mask ? "--mask" : "--per_sequence";
+  if (o->soft_mask && !o->mask) {
+    fprintf (stderr, "Error: --soft_mask needs --mask\n");
     exit (1);
   }
-  if (!o->per_sequence) return;
-  if (o->querystring) with = "-q";
+  if (o->have_min_hits && !o->per_sequence) {
+    fprintf (stderr, o->mask ? "Error: --mask cannot be combined with --min_hits\n" : "Error: --min_hits needs --per_sequence\n");
+    exit (1);
+  }
+  if (!o->per_sequence && !o->mask) return;
+  if (o->mask && o->per_sequence) with = "--per_sequence";
+  else if (o->querystring) with = "-q";
   else if (o->queryfilename) with = "-f";
   else if (o->querylistfilename) with = "-l";
   else if (o->printall) with = "--all";
@@ -850,9 +871,9 @@ static void validate (const Options *o)
   else if (o->command == CMD_SEQUENCES) with = "--sequences";
   else if (o->command != CMD_QUERY) with = "the statistics options";
   else if (o->words_only) with = "--words-only";
-  if (with) fprintf (stderr, "Error: --per_sequence cannot be combined with %s\n", with);
-  else if (!o->seqfilename) fprintf (stderr, "Error: --per_sequence needs a sequence file (-s)\n");
-  else if (o->n_lists != 1) fprintf (stderr, "Error: --per_sequence takes one list or index, %u were given\n", o->n_lists);
+  if (with) fprintf (stderr, "Error: %s cannot be combined with %s\n", what, with);
+  else if (!o->seqfilename) fprintf (stderr, "Error: %s needs a sequence file (-s)\n", what);
+  else if (o->n_lists != 1) fprintf (stderr, "Error: %s takes one list or index, %u were given\n", what, o->n_lists);
   else return;
   exit (1);
 }
@@ -1226,11 +1247,17 @@ static int profile_piece (gt4hip_context *ctx, gt4hip_query_index *qindex, const
   return GT4HIP_OK;
 }
 
-static int run_per_sequence (const Options *o)
+/* ---- what --per_sequence and --mask share: the file of -s mapped whole, the list and its index on the device, the pieces */
+
+typedef struct {
+  const char *name;
+  const unsigned char *data;
+  uint64_t size;
+} SeqFile;
+
+/* 0: mapped (size 0: there is nothing to read); 1 after a message: the file cannot be opened or mapped, or is gzip-compressed */
+static int seqfile_map (const char *fname, SeqFile *f)
 {
-  const char *fname = o->seqfilename;
-  int device = 0, verbose = 0;
-  gt4_cli_read_environment (&device, &verbose);
   struct stat st;
   const int fd = open (fname, O_RDONLY);
   if (fd < 0 || fstat (fd, &st)) {
@@ -1238,50 +1265,111 @@ static int run_per_sequence (const Options *o)
     if (fd >= 0) close (fd);
     return 1;
   }
-  const uint64_t size = (uint64_t) st.st_size;
-  const unsigned char *data = NULL;
-  if (size) {
-    void *m = mmap (NULL, (size_t) size, PROT_READ, MAP_PRIVATE, fd, 0);
+  f->name = fname, f->data = NULL, f->size = (uint64_t) st.st_size;
+  if (f->size) {
+    void *m = mmap (NULL, (size_t) f->size, PROT_READ, MAP_PRIVATE, fd, 0);
     if (m == MAP_FAILED) {
       fprintf (stderr, "Error: cannot map %s: %s\n", fname, strerror (errno));
       close (fd);
       return 1;
     }
-    data = (const unsigned char *) m;
+    f->data = (const unsigned char *) m;
   }
   close (fd);
-  if (gt4_cli_refuse_gzip (fname, size > 0 ? data[0] : EOF, size > 1 ? data[1] : EOF)) return 1;
-  if (!size) return 0;
-  gt4hip_context *ctx = NULL;
+  return gt4_cli_refuse_gzip (fname, f->size > 0 ? f->data[0] : EOF, f->size > 1 ? f->data[1] : EOF);
+}
+
+typedef struct {
+  gt4hip_context *ctx;
+  gt4hip_query_index *qindex;
+  GT4HipWordList *list;
+  uint64_t chunk; /* bytes of a piece: GT4HIP_QUERY_CHUNK, or 1/64 of the free device memory, 1 MiB to 1 GiB */
+  int verbose;
+  unsigned int pieces;
+  double reader_ms, device_ms;
+} Streamer;
+
+static void streamer_open (const Options *o, Streamer *s)
+{
+  int device = 0;
   const gt4hip_list *dev = NULL;
-  gt4hip_query_index *qindex = NULL;
-  GT4HipWordList *l = to_device (o->lists[0], &ctx, &dev);
-  CHK (ctx, gt4hip_query_index_create (ctx, dev, &qindex));
-  uint64_t chunk = gt4_cli_parse_bytes (getenv ("GT4HIP_QUERY_CHUNK"));
-  if (!chunk) {
+  memset (s, 0, sizeof *s);
+  gt4_cli_read_environment (&device, &s->verbose);
+  s->list = to_device (o->lists[0], &s->ctx, &dev);
+  CHK (s->ctx, gt4hip_query_index_create (s->ctx, dev, &s->qindex));
+  s->chunk = gt4_cli_parse_bytes (getenv ("GT4HIP_QUERY_CHUNK"));
+  if (!s->chunk) {
     uint64_t free_b = 0, total_b = 0;
-    CHK (ctx, gt4hip_device_memory (ctx, &free_b, &total_b));
-    chunk = free_b / 64;
-    if (chunk > (1ull << 30)) chunk = 1ull << 30;
-    if (chunk < (1ull << 20)) chunk = 1ull << 20;
+    CHK (s->ctx, gt4hip_device_memory (s->ctx, &free_b, &total_b));
+    s->chunk = free_b / 64;
+    if (s->chunk > (1ull << 30)) s->chunk = 1ull << 30;
+    if (s->chunk < (1ull << 20)) s->chunk = 1ull << 20;
   }
-  if (verbose) fprintf (stderr, "Device: %s; pieces of %llu bytes\n", gt4hip_device_info (ctx), (unsigned long long) chunk);
+  if (s->verbose) fprintf (stderr, "Device: %s; pieces of %llu bytes\n", gt4hip_device_info (s->ctx), (unsigned long long) s->chunk);
+}
+
+/* bytes of the piece that starts at `pos`: a chunk, cut behind the last '\n' of its second half where there is one */
+static size_t piece_length (const SeqFile *f, uint64_t pos, uint64_t chunk)
+{
+  size_t len = (size_t) (f->size - pos);
+  if (len > chunk) {
+    len = (size_t) chunk;
+    const unsigned char *nl = (const unsigned char *) memrchr (f->data + pos + len / 2, '\n', len - len / 2);
+    if (nl) len = (size_t) (nl - (f->data + pos)) + 1;
+  }
+  return len;
+}
+
+/* GT4HIP_VERBOSE: the piece that ends at `pos`; `what`: what the device did behind the reader */
+static void piece_done (Streamer *s, const SeqFile *f, uint64_t pos, uint64_t n_words, const char *what)
+{
+  s->pieces++;
+  if (!s->verbose) return;
+  uint64_t us = 0;
+  const double ms = gt4hip_query_index_last_ms (s->qindex);
+  gt4hip_get_counter (s->ctx, "extract_us", &us);
+  s->device_ms += ms, s->reader_ms += us / 1000.0;
+  fprintf (stderr, "%s: piece %u ends at byte %llu: %llu words, reader %.3f ms, %s %.3f ms\n", f->name, s->pieces, (unsigned long long) pos,
+           (unsigned long long) n_words, us / 1000.0, what, ms);
+}
+
+/* the end of the file behind a FastQ sequence line or inside a '+' line (src/fasta.c:200-213): -1 after the reader's line, else 0 */
+static int end_of_file_error (const SeqFile *f, const gt4hip_maker_carry *c)
+{
+  if (c->ended || c->file_type != GT4HIP_MAKER_FASTQ || c->line_phase != 2) return 0;
+  print_reader_error (f->name, f->data, f->size, c->at_line_start ? GT4HIP_MAKER_ERR_PLUS : GT4HIP_MAKER_ERR_PLUS_EOF, f->size);
+  return -1;
+}
+
+static void streamer_close (Streamer *s, const SeqFile *f, const char *what)
+{
+  if (s->verbose)
+    fprintf (stderr, "%s: %llu bytes in %u piece(s); reader %.3f ms, %s %.3f ms\n", f->name, (unsigned long long) f->size, s->pieces, s->reader_ms, what, s->device_ms);
+  gt4hip_query_index_free (s->qindex);
+  gt4_hip_word_list_delete (s->list);
+  munmap ((void *) f->data, (size_t) f->size);
+}
+
+static int run_per_sequence (const Options *o)
+{
+  SeqFile f;
+  if (seqfile_map (o->seqfilename, &f)) return 1;
+  if (!f.size) return 0;
+  const char *fname = f.name;
+  const unsigned char *data = f.data;
+  const uint64_t size = f.size;
+  Streamer s;
+  streamer_open (o, &s);
+  gt4hip_context *ctx = s.ctx;
+  gt4hip_query_index *qindex = s.qindex;
   PendingSequence pend = { .o = o, .data = data, .size = size };
   gt4hip_locations_carry carry, next;
   gt4hip_seq_profile *prof = NULL;
   uint64_t prof_cap = 0, pos = 0;
-  unsigned int pieces = 0;
   int have = 0, result = 0;
-  double profile_ms = 0, reader_ms = 0;
   while (pos < size) {
-    size_t len = (size_t) (size - pos);
-    if (len > chunk) {
-      len = (size_t) chunk;
-      /* behind the last '\n' of the chunk's second half, where there is one */
-      const unsigned char *nl = (const unsigned char *) memrchr (data + pos + len / 2, '\n', len - len / 2);
-      if (nl) len = (size_t) (nl - (data + pos)) + 1;
-    }
-    uint64_t at = 0, n_words = 0, us = 0;
+    const size_t len = piece_length (&f, pos, s.chunk);
+    uint64_t at = 0, n_words = 0;
     int rc = profile_piece (ctx, qindex, o, data + pos, len, have ? &carry : NULL, &next, &prof, &prof_cap, &pend, &at, &n_words);
     if (rc == GT4HIP_EFORMAT) {
       /* the words in front of the error count, as -s looks them up: the piece again, up to the offending byte */
@@ -1305,31 +1393,98 @@ static int run_per_sequence (const Options *o)
     carry = next;
     have = 1;
     pos += len;
-    pieces++;
-    if (verbose) {
-      const double ms = gt4hip_query_index_last_ms (qindex);
-      gt4hip_get_counter (ctx, "extract_us", &us);
-      profile_ms += ms, reader_ms += us / 1000.0;
-      fprintf (stderr, "%s: piece %u ends at byte %llu: %llu words, reader %.3f ms, lookups and sums %.3f ms\n", fname, pieces, (unsigned long long) pos,
-               (unsigned long long) n_words, us / 1000.0, ms);
-    }
+    piece_done (&s, &f, pos, n_words, "lookups and sums");
     if (carry.reader.ended) break;
   }
   if (!result) {
     pending_print (&pend);
     fflush (stdout);
-    /* the end of the file behind a FastQ sequence line or inside a '+' line (src/fasta.c:200-213) */
-    if (have && !carry.reader.ended && carry.reader.file_type == GT4HIP_MAKER_FASTQ && carry.reader.line_phase == 2) {
-      print_reader_error (fname, data, size, carry.reader.at_line_start ? GT4HIP_MAKER_ERR_PLUS : GT4HIP_MAKER_ERR_PLUS_EOF, size);
-      result = -1;
-    }
+    if (have) result = end_of_file_error (&f, &carry.reader);
   }
-  if (verbose) fprintf (stderr, "%s: %llu bytes in %u piece(s); reader %.3f ms, lookups and sums %.3f ms\n", fname, (unsigned long long) size, pieces, reader_ms, profile_ms);
   free (prof);
   gt4hip_locations_free (ctx);
-  gt4hip_query_index_free (qindex);
-  gt4_hip_word_list_delete (l);
-  munmap ((void *) data, (size_t) size);
+  streamer_close (&s, &f, "lookups and sums");
+  return result;
+}
+
+/* ------------------------------------------------------------------ -s FILE --mask [--soft_mask] */
+
+static int write_stdout (const void *bytes, size_t n, void *arg)
+{
+  (void) arg;
+  return fwrite (bytes, 1, n, stdout) != n;
+}
+
+static void mask_or_exit (int failed)
+{
+  if (!failed) return;
+  fflush (stdout);
+  fprintf (stderr, "Error: the masked text could not be written: %s\n", errno ? strerror (errno) : "out of memory");
+  exit (1);
+}
+
+/* The file goes through gt4hip_query_mask_text piece by piece; what a later piece may still cover is held back (GT4MaskTail). */
+static int run_mask (const Options *o)
+{
+  SeqFile f;
+  if (seqfile_map (o->seqfilename, &f)) return 1;
+  if (!f.size) return 0;
+  Streamer s;
+  streamer_open (o, &s);
+  gt4hip_context *ctx = s.ctx;
+  const gt4hip_query_params prm = { .n_mm = o->nmm, .pm_3 = o->pm3, .canonize = 1 };
+  const uint32_t lo = o->minfreq > 1 ? o->minfreq : 1;
+  const unsigned int flags = o->soft_mask ? GT4HIP_MASK_SOFT : 0, k = gt4hip_list_word_length (gt4_hip_word_list_device (s.list));
+  unsigned char *masked = (unsigned char *) or_oom (malloc ((size_t) (f.size < s.chunk ? f.size : s.chunk)), "a piece of %llu bytes", (unsigned long long) s.chunk);
+  GT4MaskTail tail;
+  gt4_mask_tail_init (&tail, o->soft_mask, 'N', write_stdout, NULL);
+  gt4hip_maker_carry carry, next;
+  gt4hip_mask_piece piece;
+  uint64_t pos = 0;
+  int have = 0, result = 0;
+  while (pos < f.size) {
+    const size_t len = piece_length (&f, pos, s.chunk);
+    uint64_t at = 0;
+    int rc = gt4hip_query_mask_text (ctx, s.qindex, f.data + pos, len, flags, &prm, lo, o->maxfreq, 'N', have ? &carry : NULL, &next, masked, &piece, &at);
+    if (rc == GT4HIP_EFORMAT) {
+      /* the words in front of the error count, as -s looks them up: the piece again, up to the offending byte */
+      const uint32_t kind = next.error;
+      uint64_t none = 0;
+      if (at) {
+        if (gt4hip_query_mask_text (ctx, s.qindex, f.data + pos, (size_t) at, flags, &prm, lo, o->maxfreq, 'N', have ? &carry : NULL, &next, masked, &piece, &none)) {
+          fflush (stdout);
+          fprintf (stderr, "Error: %s\n", gt4hip_last_error (ctx));
+          exit (1);
+        }
+        mask_or_exit (gt4_mask_tail_push (&tail, masked, (size_t) at, piece.back, k));
+      }
+      mask_or_exit (gt4_mask_tail_finish (&tail));
+      fflush (stdout);
+      print_reader_error (f.name, f.data, f.size, kind, pos + at);
+      result = -1;
+      break;
+    }
+    if (rc) {
+      fflush (stdout);
+      fprintf (stderr, "Error: %s\n", gt4hip_last_error (ctx));
+      exit (1);
+    }
+    mask_or_exit (gt4_mask_tail_push (&tail, masked, len, piece.back, k));
+    carry = next;
+    have = 1;
+    pos += len;
+    piece_done (&s, &f, pos, piece.n_words, "lookups and masking");
+    if (carry.ended) break;
+  }
+  if (!result) {
+    /* the end of the file, or a NUL: nothing more is covered; the rest of the file as it is */
+    mask_or_exit (gt4_mask_tail_finish (&tail));
+    if (pos < f.size) mask_or_exit (write_stdout (f.data + pos, (size_t) (f.size - pos), NULL));
+    mask_or_exit (fflush (stdout) != 0);
+    if (have) result = end_of_file_error (&f, &carry);
+  }
+  free (masked);
+  streamer_close (&s, &f, "lookups and masking");
   return result;
 }
 
@@ -1357,6 +1512,7 @@ int main (int argc, const char *argv[])
     return 1;
   }
   if (o.per_sequence) return run_per_sequence (&o);
+  if (o.mask) return run_mask (&o);
   if (!o.querystring && !o.queryfilename && !o.seqfilename && !o.nmm && !o.words_only && !o.locations) return run_zipper (&o, wlen);
   return run_lookups (&o, wlen, &maps[0], &query_input);
 }

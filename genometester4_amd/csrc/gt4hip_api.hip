@@ -218,6 +218,8 @@ extern "C" int gt4hip_get_counter (gt4hip_context *ctx, const char *name, uint64
   else if (!strcmp (name, "subset_scan_tile")) *value = 256u * GT4HIP_SUBSET_SCAN_V;
   else if (!strcmp (name, "pack_threads")) *value = GT4HIP_PACK_THREADS;
   else if (!strcmp (name, "subset_us")) *value = (uint64_t) (ctx->subset_ms * 1000.0);
+  else if (!strcmp (name, "mask_ends_us")) *value = (uint64_t) (ctx->mask_ends_ms * 1000.0);
+  else if (!strcmp (name, "mask_apply_us")) *value = (uint64_t) (ctx->mask_apply_ms * 1000.0);
   else if (!strcmp (name, "select_wide")) *value = ctx->select_wide;
   else if (!strcmp (name, "select_segment")) *value = GT4HIP_SELECT_SEGMENT;
   else if (!strcmp (name, "grid_capped")) *value = ctx->grid_limit.capped;

@@ -1,7 +1,7 @@
 /* gt4hip_host.h -- host-side internals shared by the C-ABI implementation files: the context and list objects, the
  * owners of a call's temporaries (TempLists, TempBlocks, TempTable), the grid size of the striding kernels, and what the
  * units of the library host (gt4hip_api.hip, gt4hip_pair.hip, gt4hip_multi.hip, gt4hip_table.hip, gt4hip_nway.hip) and
- * gt4hip_io / _comm / _sort / _maker / _mismatch / _query / _seqprofile / _gmer / _subset / _select / _pairwise.hip call in one another. */
+ * gt4hip_io / _comm / _sort / _maker / _mismatch / _query / _seqprofile / _mask / _gmer / _subset / _select / _pairwise.hip call in one another. */
 #ifndef GT4HIP_HOST_H
 #define GT4HIP_HOST_H
 
@@ -83,6 +83,7 @@ struct gt4hip_context {
   uint64_t query_wide;          /* counter "query_wide": the last gt4hip_query_lookup launched k_query<true> */
   uint64_t subset_passes;       /* counter "subset_passes": passes of the last gt4hip_list_subset (gt4hip_subset.hip) */
   double subset_ms;             /* counter "subset_us": its kernels (HIP events) */
+  double mask_ends_ms, mask_apply_ms; /* counters "mask_ends_us", "mask_apply_us": the last gt4hip_query_mask_text (gt4hip_mask.hip) */
   int select_vec;               /* option "select_vec": gt4hip_table_select reads rows of a multiple of four counts 16 bytes per lane (0) / every row a dword per lane (-1) */
   uint64_t select_wide;         /* counter "select_wide": the last gt4hip_table_select read 16 bytes per lane */
   gt4::GridLimit grid_limit;    /* option "grid_cap" (tests): workgroups at most of every kernel that strides over its work, 0 = the built-in caps alone; counter "grid_capped": launches whose grid had fewer workgroups than blocks of work */
@@ -271,7 +272,26 @@ GT4HIP_LOCAL int gt4hip_text_to_words_counted (gt4hip_context *ctx, const void *
 /* gt4hip_gmer.hip: k_mk_text_counts on the arrays of a reader call (text, tile states, codes, MakerInfo); out: three zeroed device words */
 GT4HIP_LOCAL void gt4hip_launch_text_counts (hipStream_t stream, int grid, bool fastq, const unsigned char *d_text, size_t n_bytes, uint64_t tiles,
                                              const uint32_t *tile_state, const unsigned char *codes, const void *info, unsigned long long *out);
-/* gt4hip_query.hip for gt4hip_seqprofile.hip.  The argument rules of the lookups (`who` in the message); the list an index
+/* gt4hip_text_to_words for gt4hip_mask.hip: what a call of the reader has on the device while it lasts.  `then` runs behind
+ * the words' kernel (the stream is drained, the totals are read back), before the call's blocks go back to the pool; it is
+ * not called when the call fails or has nothing to read (no bytes, a piece behind a NUL, a NUL as the first byte of a file) */
+struct gt4hip_reader_view {
+  const unsigned char *d_text;  /* the piece on the device */
+  size_t n_bytes;
+  uint64_t tiles;               /* of GT4HIP_MAKER_TILE bytes of text; the tiles of codes are no more */
+  const uint64_t *tile_off;     /* codes in front of each tile of text */
+  const uint64_t *emit_off;     /* words that end in front of each tile of codes */
+  const unsigned char *buf;     /* the halo's 32 codes, then the piece's (16-byte aligned, 64 readable bytes behind the last) */
+  const void *info;             /* the device's MakerInfo (gt4hip_maker_tile.h) */
+  uint64_t nul_pos, n_codes;    /* of it, as read back */
+  const uint64_t *d_words;      /* NULL when there is none */
+  uint64_t n_words;
+};
+typedef int (*gt4hip_reader_then) (gt4hip_context *ctx, const gt4hip_reader_view *view, void *arg);
+GT4HIP_LOCAL int gt4hip_text_to_words_then (gt4hip_context *ctx, const void *text, size_t n_bytes, unsigned word_length, unsigned flags,
+                                            const gt4hip_maker_carry *in, gt4hip_maker_carry *out, uint64_t **d_words, uint64_t *n_words,
+                                            uint64_t *error_offset, gt4hip_reader_then then, void *arg);
+/* gt4hip_query.hip for gt4hip_seqprofile.hip and gt4hip_mask.hip.  The argument rules of the lookups (`who` in the message); the list an index
  * was made of and its bucket offsets; the device time a call on the index reports (gt4hip_query_index_last_ms) */
 GT4HIP_LOCAL int gt4hip_query_check_params (gt4hip_context *ctx, const char *who, const gt4hip_query_index *qindex, const gt4hip_query_params *params);
 GT4HIP_LOCAL const gt4hip_list *gt4hip_query_index_list (const gt4hip_query_index *qindex);

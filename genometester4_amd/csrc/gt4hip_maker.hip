@@ -25,8 +25,9 @@
  *
  * What sibling kernels share is written once, as inline functions: tile_head (the reader's state at a thread's first byte:
  * k_mk_codes, k_mk_events), load_word_ends and for_each_word (where words end, and the walk over them: k_mk_emit,
- * k_mk_emit_loc), block_scan (all of them and k_mk_summary).  The tile geometry, tile_head and block_scan live in
- * gt4hip_maker_tile.h, which gt4hip_gmer.hip's statistics pass shares.  The host half is one MakerCall handed through stages.
+ * k_mk_emit_loc), block_scan (all of them and k_mk_summary).  The tile geometry, tile_head, block_scan and load_word_ends
+ * live in gt4hip_maker_tile.h, which gt4hip_gmer.hip's statistics pass and gt4hip_mask.hip's two passes share.  The host half
+ * is one MakerCall handed through stages.
  *
  * k_tile_count of gt4hip_index.h is not used: it counts a 4-byte flag per item, which would cost more traffic than
  * the text itself; the counts here come out of the classification.  Algorithmic bytes per text byte: 1 + 1 read, 1
@@ -169,30 +170,6 @@ __global__ __launch_bounds__ (MK_THREADS) void k_mk_codes (const unsigned char *
     if (threadIdx.x < rest) dst[head + 4 * nd + threadIdx.x] = out[head + 4 * nd + threadIdx.x];
     __syncthreads ();
   }
-}
-
-/* `buf`: the halo's MK_HALO codes, then the text's (16-byte aligned).  w = the thread's 16 codes from j0 on and the MK_HALO
- * in front of them (all 4 where the thread has none); returns bit i set iff a word ends at code j0 + i, that is iff
- * codes j0 + i - k + 1 .. j0 + i are bases. */
-__device__ __forceinline__ u32 load_word_ends (const unsigned char *__restrict__ buf, u64 j0, u64 n_codes, u32 k, u32 w[12])
-{
-  if (j0 < n_codes) {
-#pragma unroll
-    for (int q = 0; q < 3; q++) {
-      const u32x4 v = *(const u32x4 *) (buf + j0 + 16 * q);
-      w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
-    }
-  } else {
-#pragma unroll
-    for (int q = 0; q < 12; q++) w[q] = 0x04040404u;
-  }
-  u32 len = 0, ends = 0;
-#pragma unroll
-  for (int i = 0; i < MK_HALO + MK_PER; i++) {
-    len = MK_BYTE (w, i) < 4u ? len + 1u : 0u;
-    if (i >= MK_HALO && j0 + (u64) (i - MK_HALO) < n_codes && len >= k) ends |= 1u << (i - MK_HALO);
-  }
-  return ends;
 }
 
 /* f (j, forward word masked to 2k bits, reverse complement) for every word of `ends`, j the index of its last code, in order */
@@ -718,7 +695,8 @@ int maker_emit_locations (MakerCall &m)
 /* gt4hip_text_to_words; with `loc`, gt4hip_text_to_locations: the same stages up to the words' count, then the events and
  * k_mk_emit_loc into the caller's arrays instead of k_mk_emit<true> into a block of the context */
 int text_to_words (gt4hip_context *ctx, const void *text, size_t n_bytes, unsigned word_length, unsigned flags, const gt4hip_maker_carry *in,
-                   gt4hip_maker_carry *out, uint64_t **d_words, uint64_t *n_words, uint64_t *error_offset, LocCall *loc, uint64_t *counts = NULL)
+                   gt4hip_maker_carry *out, uint64_t **d_words, uint64_t *n_words, uint64_t *error_offset, LocCall *loc, uint64_t *counts = NULL,
+                   gt4hip_reader_then then = NULL, void *then_arg = NULL)
 {
   gt4hip_maker_carry dummy;
   MakerCall m = { ctx, text, n_bytes, word_length, flags, out ? out : &dummy, d_words, n_words, error_offset, loc };
@@ -727,7 +705,11 @@ int text_to_words (gt4hip_context *ctx, const void *text, size_t n_bytes, unsign
   if (rc == MK_DONE) return loc ? finish_locations (ctx, loc, m.out, NULL, 0, 0, loc->in ? loc->in->offset : 0, 0) : GT4HIP_OK;
   if (rc || (rc = maker_classify_count (m)) || (rc = maker_totals (m))) return rc;
   if (counts && (rc = maker_text_counts (m, counts))) return rc;
-  return loc ? maker_emit_locations (m) : maker_emit_words (m);
+  if (loc) return maker_emit_locations (m);
+  if ((rc = maker_emit_words (m)) || !then) return rc;
+  /* gt4hip_mask.hip's passes, on the arrays of this call */
+  const gt4hip_reader_view view = { m.d_text, m.n_bytes, m.tiles, (const uint64_t *) m.tile_off, (const uint64_t *) m.emit_off, m.buf, m.info, m.h.nul_pos, m.h.n_codes, *m.d_words, *m.n_words };
+  return then (ctx, &view, then_arg);
 }
 
 }  // namespace
@@ -749,6 +731,12 @@ int gt4hip_text_to_words_counted (gt4hip_context *ctx, const void *text, size_t 
                                   gt4hip_maker_carry *out, uint64_t **d_words, uint64_t *n_words, uint64_t *error_offset, uint64_t counts[3])
 {
   return text_to_words (ctx, text, n_bytes, word_length, flags, in, out, d_words, n_words, error_offset, NULL, counts);
+}
+
+int gt4hip_text_to_words_then (gt4hip_context *ctx, const void *text, size_t n_bytes, unsigned word_length, unsigned flags, const gt4hip_maker_carry *in,
+                               gt4hip_maker_carry *out, uint64_t **d_words, uint64_t *n_words, uint64_t *error_offset, gt4hip_reader_then then, void *arg)
+{
+  return text_to_words (ctx, text, n_bytes, word_length, flags, in, out, d_words, n_words, error_offset, NULL, NULL, then, arg);
 }
 
 extern "C" int gt4hip_text_to_locations (gt4hip_context *ctx, const void *text, size_t n_bytes, unsigned word_length, unsigned flags, const gt4hip_locations_carry *in,

@@ -1,6 +1,7 @@
 /* gt4hip_maker_tile.h -- the reader's tile geometry and the state of the reader at a thread's first byte of a tile: what the
- * kernels of gt4hip_maker.hip share with the statistics pass of gt4hip_gmer.hip (k_mk_text_counts), which runs on the arrays
- * a call of the reader has just filled.  Include after gt4hip_device.h and gt4hip_host.h; internal linkage throughout. */
+ * kernels of gt4hip_maker.hip share with the statistics pass of gt4hip_gmer.hip (k_mk_text_counts) and the masking passes of
+ * gt4hip_mask.hip (k_mask_ends, k_mask_apply), which run on the arrays a call of the reader has just filled; and where words
+ * end among a thread's codes (load_word_ends).  Include after gt4hip_device.h and gt4hip_host.h; internal linkage throughout. */
 #ifndef GT4HIP_MAKER_TILE_H
 #define GT4HIP_MAKER_TILE_H
 
@@ -109,6 +110,30 @@ __device__ __forceinline__ TileHead tile_head (const unsigned char *__restrict__
   h.phase = ((st >> 1) + (sc.before >> 16)) & 3u;
   h.n_codes = sc.total & 0xffffu;
   return h;
+}
+
+/* `buf`: the halo's MK_HALO codes, then the text's (16-byte aligned).  w = the thread's 16 codes from j0 on and the MK_HALO
+ * in front of them (all 4 where the thread has none); returns bit i set iff a word ends at code j0 + i, that is iff
+ * codes j0 + i - k + 1 .. j0 + i are bases. */
+__device__ __forceinline__ u32 load_word_ends (const unsigned char *__restrict__ buf, u64 j0, u64 n_codes, u32 k, u32 w[12])
+{
+  if (j0 < n_codes) {
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+      const u32x4 v = *(const u32x4 *) (buf + j0 + 16 * q);
+      w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < 12; q++) w[q] = 0x04040404u;
+  }
+  u32 len = 0, ends = 0;
+#pragma unroll
+  for (int i = 0; i < MK_HALO + MK_PER; i++) {
+    len = MK_BYTE (w, i) < 4u ? len + 1u : 0u;
+    if (i >= MK_HALO && j0 + (u64) (i - MK_HALO) < n_codes && len >= k) ends |= 1u << (i - MK_HALO);
+  }
+  return ends;
 }
 
 }  // namespace

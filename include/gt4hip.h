@@ -673,6 +673,29 @@ int gt4hip_query_profile_text (gt4hip_context *ctx, gt4hip_query_index *qindex, 
                                const gt4hip_locations_carry *in, gt4hip_locations_carry *out, gt4hip_locations_piece *piece,
                                gt4hip_seq_profile *profiles, uint64_t capacity, uint64_t *n_profiles, uint64_t *error_offset);
 
+/* ---------------------------------------------------------------- glistquery --mask: the bases a list's words cover */
+
+/* what a piece gave: words that END in the piece and the hits among them (as gt4hip_seq_profile counts them), the piece's
+ * own covered bases, and how many of the last bytes >= ' ' IN FRONT of the piece a hit word of this piece covers */
+typedef struct { uint64_t n_words, n_hits, n_covered; uint32_t back, pad; } gt4hip_mask_piece;
+enum { GT4HIP_MASK_SOFT = 4 }; /* beside GT4HIP_MAKER_TEXT_ON_DEVICE, which here also says that `masked` is device memory (16-byte aligned) */
+
+/* One piece of a file with every covered base replaced.  The text's words are gt4hip_text_to_words's (canonising); a word is
+ * a HIT by the rule of gt4hip_seq_profile above (found, and min_value <= value <= max_value, under params' n_mm / pm_3); a
+ * base is COVERED when it is one of the word_length bases of at least one hit word.  masked[0 .. n_bytes) = the piece with
+ * its covered bases written as mask_byte, with GT4HIP_MASK_SOFT as byte | 0x20; every other byte, and every byte from a NUL
+ * on, as it is.  A hit word that ends in this piece may begin in front of it: piece->back (0 .. word_length - 1, never more
+ * than the bases the carry holds) says how many of the last bytes >= ' ' in front of the piece it covers -- a suffix of
+ * them, all bases --, which the caller patches; they are not counted in n_covered.  The carry, the errors of the text and
+ * *error_offset are gt4hip_text_to_words's; after an error `masked` holds nothing.  The context's word buffer is released.
+ * On the device the call holds, per byte of the piece: 1 (the codes) + 1/8 (one bit per code) + 8 per word (at most one per
+ * byte), for host text 2 more (the text and the masked text), with n_mm > 0 4 more per word: 11 1/8 bytes at most, 15 1/8 with
+ * mismatches.  gt4hip_query_index_last_ms: the lookups and the two masking kernels. */
+int gt4hip_query_mask_text (gt4hip_context *ctx, gt4hip_query_index *qindex, const void *text, size_t n_bytes, unsigned flags,
+                            const gt4hip_query_params *params, uint32_t min_value, uint32_t max_value, unsigned char mask_byte,
+                            const gt4hip_maker_carry *in, gt4hip_maker_carry *out, void *masked, gt4hip_mask_piece *piece,
+                            uint64_t *error_offset);
+
 /* ---------------------------------------------------------------- gmer_counter: database k-mers counted in reads */
 
 /* A k-mer database resident in HBM (reference src/database.c, src/gmer_counter.c:751-815, without the trie): the
@@ -840,7 +863,8 @@ int gt4hip_set_option (gt4hip_context *ctx, const char *name, int64_t value);
  * "mm_unskipped_levels": levels of it run without the early exit of decided words (more than 2^32 - 1 variants a word, no subtract);
  * "subset_passes": passes of the last gt4hip_list_subset until a scan changed no tile's carry-in (0: it had nothing to walk);
  * "subset_tile": items per tile of its kernels; "subset_us": its device time (HIP events around the kernels, the one
- * word read back per pass included); "select_wide": 1 when the context's last gt4hip_table_select (gt4hip_select_multi's too)
+ * word read back per pass included); "mask_ends_us", "mask_apply_us": the two spans of the last gt4hip_query_mask_text (HIP
+ * events: the lookups with k_mask_ends, and k_mask_apply); "select_wide": 1 when the context's last gt4hip_table_select (gt4hip_select_multi's too)
  * read 16 bytes per lane, else 0; "grid_capped": launches of the context, since it was made, of a kernel that strides over its
  * work with fewer workgroups than blocks of work (by option "grid_cap" or by a built-in cap): the loops of those took a second
  * trip.  Sizes the tests build their inputs from: "mm_threads": items per block of work of the item loops of the query,
