@@ -204,6 +204,7 @@ extern "C" int gt4hip_get_counter (gt4hip_context *ctx, const char *name, uint64
   else if (!strcmp (name, "kway_width")) *value = ctx->kway_width;
   else if (!strcmp (name, "nway_kernel_us")) *value = (uint64_t) (ctx->nway_kernel_ms * 1000.0);
   else if (!strcmp (name, "nway_tiles")) *value = ctx->nway_tiles;
+  else if (!strcmp (name, "nway_sample_tiles")) *value = ctx->nway_sample_tiles;
   else if (!strcmp (name, "nway_one_pass")) *value = (uint64_t) ctx->last_multi_one_pass;
   else if (!strcmp (name, "sort_us")) *value = (uint64_t) (ctx->sort_ms * 1000.0);
   else if (!strcmp (name, "fold_us")) *value = (uint64_t) (ctx->fold_ms * 1000.0);

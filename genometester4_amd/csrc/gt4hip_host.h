@@ -75,6 +75,7 @@ struct gt4hip_context {
   gt4hip_subseq *maker_subseqs;    /* host: the records of the last gt4hip_text_to_locations, until gt4hip_locations_free or the next call */
   double nway_kernel_ms;     /* the last one-pass launch's kernel time (HIP events on the library's stream) and tiles */
   uint64_t nway_tiles;
+  uint64_t nway_sample_tiles; /* counter "nway_sample_tiles": the most tiles of a sample-level launch of the last N-way call (0: it had none) */
   int last_multi_one_pass;   /* the last gt4hip_union_multi was done by the one-pass tile kernel (counter "nway_one_pass") */
   gt4hip_io *io;            /* file <-> HBM staging (gt4hip_io.hip), NULL until first used */
   gt4hip_mismatch_stats mm_stats; /* the last gt4hip_compare_mismatch (gt4hip_mismatch.hip) */

@@ -303,6 +303,7 @@ int nway_launch_level (NwayCall &c, int l, int mode, u64 tiles, const u64 *part_
     const int rc = gt4hip_grow (ctx, (void **) &ctx->desc, &ctx->desc_bytes, gt4hip_lookback_desc_bytes (tiles));
     if (rc) return rc;
     hipMemsetAsync (ctx->desc, 0, gt4hip_lookback_desc_bytes (tiles), st);
+    if (grid < 2) grid = 2; /* the first workgroup to arrive is the scanner: option "grid" = 1 would leave it without a worker */
     if ((u64) grid > tiles + 1) grid = (int) tiles + 1;
   } else if ((u64) grid > tiles) {
     grid = (int) tiles;
@@ -364,6 +365,7 @@ int nway_stages (NwayCall &c, uint64_t *n_words, uint64_t *total_count, double *
   const hipError_t e0 = hipEventRecord (ctx->ev[0], st);
   if (e0 != hipSuccess) return gt4hip_fail (ctx, GT4HIP_EHIP, "hipEventRecord failed: %s", hipGetErrorString (e0));
   hipMemsetAsync (ctx->ctl, 0, sizeof (PairControl), st);
+  ctx->nway_sample_tiles = 0;
   int rc;
   if ((rc = nway_key_probe (c))) return rc;
   if ((rc = nway_sample_levels (c))) return rc;
@@ -374,6 +376,7 @@ int nway_stages (NwayCall &c, uint64_t *n_words, uint64_t *total_count, double *
     const u64 *part_final = NULL;
     u64 tiles = 1;
     if ((rc = nway_partition_level (c, l, mode, &part_final, &tiles))) return rc;
+    if (l > 0 && tiles > ctx->nway_sample_tiles) ctx->nway_sample_tiles = tiles;
     c.merged.clear ();
     u32 *dst = (l > 0 || c.count_only) ? NULL : (u32 *) c.out->dev;
     if (l > 0) {

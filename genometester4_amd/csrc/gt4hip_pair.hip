@@ -104,8 +104,10 @@ int gt4hip_run_pair (gt4hip_context *ctx, const uint32_t *A, uint64_t nA, const 
   }
   int grid = ctx->n_cus * merge_blocks_per_cu (v1);
   if (ctx->grid_override > 0) grid = (int) ctx->grid_override;
+  if (v1.mode == MODE_LOOKBACK && grid < 2) grid = 2; /* the first workgroup to arrive is the scanner: option "grid" = 1 would leave it without a worker */
   if ((uint64_t) grid > tiles + 1) grid = (int) tiles + 1; /* workers + the scanner workgroup */
-  int grid2 = ctx->n_cus * merge_blocks_per_cu (v2);
+  int grid2 = ctx->n_cus * merge_blocks_per_cu (v2); /* (pass 2: no workgroup waits for another) */
+  if (ctx->grid_override > 0) grid2 = (int) ctx->grid_override;
   if ((uint64_t) grid2 > tiles) grid2 = (int) tiles;
 
   PairOutputs outs;

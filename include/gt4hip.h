@@ -809,7 +809,10 @@ int gt4hip_synchronize (gt4hip_context *ctx);
  *   "pool" = 0         release freed list storage to the driver instead of pooling it
  *   "pool_cap_mb" = n  most the pool may hold (default: half of the device memory); every device
  *                      allocation that fails gives the pooled blocks back and retries
- *   "grid" = n         workgroups of the merge kernel (0: one per resident slot)
+ *   "grid" = n         workgroups of the merge kernels, pair and N-way, in every launch of a call, pass 2 of the two-pass
+ *                      path included (0: one per resident slot).  A launch never gets more than it has tiles (and a
+ *                      scanner), and a single-pass launch that writes records never fewer than two: its first workgroup
+ *                      to arrive is the scanner, so n = 1 runs one worker there as n = 2 does
  *   "kway" = 0 / 1 / 2 / 3  N-way unions of three and more lists by the pairwise tree of the pair kernel / by
  *                      the one-pass tile kernel (gt4hip_nway.hip) unless a probe of the keys or the tiles' own
  *                      samples show them clustered -- stretches of adjacent keys between wide gaps, which the
@@ -852,7 +855,8 @@ int gt4hip_set_option (gt4hip_context *ctx, const char *name, int64_t value);
  * "kway_declined": N-way unions handed to the pairwise tree because their keys are clustered;
  * "kway_calls" / "kway_overflows": N-way unions (and count tables) done by the one-pass tile kernel /
  * partitions repeated with fewer samples per tile because a tile would not have fit LDS;
- * "nway_kernel_us", "nway_tiles": the last N-way call's tile kernel; "nway_one_pass": 1 when the last
+ * "nway_kernel_us", "nway_tiles": the last N-way call's tile kernel (its last launch); "nway_sample_tiles": the most tiles
+ * among that call's launches over sample levels, 0 if it had none; "nway_one_pass": 1 when the last
  * gt4hip_union_multi took the one-pass tile kernel, 0 when it took the pairwise tree; "sort_us", "fold_us", "table_us":
  * the last gt4hip_device_words_to_list / gt4hip_union_table call; "extract_us": the kernels of the last gt4hip_text_to_words
  * that gave words (HIP events around the kernels alone: the call's read-back of its totals and the allocation of the

@@ -56,10 +56,14 @@ The sites (`gridDim\\.x` over genometester4_amd/csrc), their launcher, and the t
                      k_extract_keys, k_extract_column grid_for     test_count_table_by_merges
                      k_partition                      NOT capped: one thread per tile boundary by construction (the loop
                                                                    only deals the words it zeroes); a partition kernel
-                     k_pair_merge (n_workers)         NOT capped: its workgroups wait for one another; option "grid"
+                     k_pair_merge (n_workers)         NOT capped: its workgroups wait for one another; option "grid",
+                                                                   under which tests/test_few_workers_gpu.py runs it with
+                                                                   one to three workgroups
   gt4hip_multi.hip   k_sample_stride                  gt4hip_grid  test_shard_cuts
   gt4hip_nway_part.h k_nway_sample                    NOT capped: a partition kernel of the N-way family, which keeps "grid"
-  gt4hip_nway_tile.h k_nway_merge (n_workers)         NOT capped: its workgroups wait for one another; option "grid"
+  gt4hip_nway_tile.h k_nway_merge (n_workers)         NOT capped: its workgroups wait for one another; option "grid",
+                                                                   under which tests/test_few_workers_gpu.py runs it with
+                                                                   one to four workgroups
 """
 import numpy as np
 import pytest
